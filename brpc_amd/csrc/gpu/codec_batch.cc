@@ -58,6 +58,16 @@ struct CBatch {
     std::vector<size_t> comp_first, decomp_first, stream_first, piece_first, scan_row, run_first;
     PinnedArray<PbRunChunk> run_jobs;
     PinnedArray<int32_t> run_err;
+    std::vector<size_t> msg_first, mfield_first, mchunk_first;
+    PinnedArray<PbMsgJob> msg_jobs;
+    PinnedArray<PbMsgField> msg_fields;
+    PinnedArray<PbMsgChunk> msg_chunks;
+    PinnedArray<PbMsgResult> msg_res;
+    PinnedArray<PbMsgFieldResult> msg_fres;
+    uint32_t* msg_prefix = nullptr;  // HBM: per-chunk encoded sizes, scanned, of the message builder
+    size_t msg_prefix_cap = 0;
+    uint64_t* msg_base = nullptr;  // HBM: per-field payload address
+    size_t msg_base_cap = 0;
     std::vector<size_t> dec_first;
     PinnedArray<PbRunDecodeChunk> dec_jobs;
     PinnedArray<uint32_t> dec_counts;
@@ -125,6 +135,7 @@ void retire_done(Engine& e) {
 
 Engine g_engine[kMaxDev];
 std::atomic<int64_t> g_requests{0}, g_launches{0}, g_run_chunks{0}, g_dec_chunks{0}, g_fused_launches{0};
+std::atomic<int64_t> g_msg_chunks{0};
 // per request, summed: waiting for a launch, the batch's launch API time,
 // launch -> completion seen by the poller (device time + queueing + poll),
 // completion seen -> requester running again
@@ -145,6 +156,7 @@ CBatch* new_batch(Engine& e) {
 // sequence; false when nothing could be launched.
 bool launch(CBatch* b, int device) {
     size_t ncomp = 0, ndecomp = 0, nscan = 0, nstreams = 0, npieces = 0, nhpieces = 0, nruns = 0, ndec = 0;
+    size_t nmsgs = 0, nmfields = 0, nmchunks = 0;
     uint32_t comp_max = 1, decomp_max = 1, piece_limit = 0, hpiece_max = 1;
     std::vector<Segment> h2d, d2h;
     b->comp_first.clear();
@@ -154,7 +166,16 @@ bool launch(CBatch* b, int device) {
     b->scan_row.clear();
     b->run_first.clear();
     b->dec_first.clear();
+    b->msg_first.clear();
+    b->mfield_first.clear();
+    b->mchunk_first.clear();
     for (CodecRequest* r : b->reqs) {
+        b->msg_first.push_back(nmsgs);
+        nmsgs += r->msgs.size();
+        b->mfield_first.push_back(nmfields);
+        nmfields += r->msg_fields.size();
+        b->mchunk_first.push_back(nmchunks);
+        nmchunks += r->msg_chunks.size();
         b->run_first.push_back(nruns);
         nruns += r->runs.size();
         b->dec_first.push_back(ndec);
@@ -183,7 +204,9 @@ bool launch(CBatch* b, int device) {
         !b->scan_n.reserve(nscan) || !b->stream_jobs.reserve(nstreams) || !b->stream_err.reserve(nstreams) ||
         !b->piece_err.reserve(npieces) || !b->piece_jobs.reserve(nhpieces) || !b->piece_job_err.reserve(nhpieces) ||
         !b->run_jobs.reserve(nruns) || !b->run_err.reserve(nruns) || !b->dec_jobs.reserve(ndec) ||
-        !b->dec_counts.reserve(ndec) || !b->dec_err.reserve(ndec)) {
+        !b->dec_counts.reserve(ndec) || !b->dec_err.reserve(ndec) || !b->msg_jobs.reserve(nmsgs) ||
+        !b->msg_res.reserve(nmsgs) || !b->msg_fields.reserve(nmfields) || !b->msg_fres.reserve(nmfields) ||
+        !b->msg_chunks.reserve(nmchunks)) {
         return false;
     }
     if (npieces > b->pieces_cap) {
@@ -205,6 +228,23 @@ bool launch(CBatch* b, int device) {
             c.first += (uint32_t)b->dec_first[i];
             b->dec_jobs.p[b->dec_first[i] + k] = c;
         }
+        for (size_t k = 0; k < r->msgs.size(); ++k) {
+            PbMsgJob m = r->msgs[k];
+            m.first_field += (uint32_t)b->mfield_first[i];
+            b->msg_jobs.p[b->msg_first[i] + k] = m;
+        }
+        for (size_t k = 0; k < r->msg_fields.size(); ++k) {
+            PbMsgField f = r->msg_fields[k];
+            f.msg += (uint32_t)b->msg_first[i];
+            f.first_chunk += (uint32_t)b->mchunk_first[i];
+            b->msg_fields.p[b->mfield_first[i] + k] = f;
+        }
+        for (size_t k = 0; k < r->msg_chunks.size(); ++k) {
+            PbMsgChunk c = r->msg_chunks[k];
+            c.field += (uint32_t)b->mfield_first[i];
+            c.first += (uint32_t)b->mchunk_first[i];
+            b->msg_chunks.p[b->mchunk_first[i] + k] = c;
+        }
     }
     for (size_t i = 0, g = 0, first = 0; i < b->reqs.size(); ++i) {
         for (const SnappyStream& st : b->reqs[i]->streams) {
@@ -221,6 +261,20 @@ bool launch(CBatch* b, int device) {
         b->dec_prefix_cap = b->dec_prefix ? cap : 0;
         if (!b->dec_prefix) return false;
     }
+    if (nmsgs && nmchunks + 1 > b->msg_prefix_cap) {
+        if (b->msg_prefix) HbmFree(b->msg_prefix, b->msg_prefix_cap * sizeof(uint32_t), device);
+        const size_t cap = std::max<size_t>(nmchunks + 1, 1024);
+        b->msg_prefix = static_cast<uint32_t*>(HbmAlloc(cap * sizeof(uint32_t), device));
+        b->msg_prefix_cap = b->msg_prefix ? cap : 0;
+        if (!b->msg_prefix) return false;
+    }
+    if (nmsgs && std::max<size_t>(nmfields, 1) > b->msg_base_cap) {
+        if (b->msg_base) HbmFree(b->msg_base, b->msg_base_cap * sizeof(uint64_t), device);
+        const size_t cap = std::max<size_t>(nmfields, 256);
+        b->msg_base = static_cast<uint64_t*>(HbmAlloc(cap * sizeof(uint64_t), device));
+        b->msg_base_cap = b->msg_base ? cap : 0;
+        if (!b->msg_base) return false;
+    }
     if (ncomp && SnappyCompressUsesScratch(comp_max)) {
         const size_t need = ncomp * SnappyCompressScratchPerBlock();
         if (need > b->scratch_bytes) {
@@ -234,8 +288,8 @@ bool launch(CBatch* b, int device) {
     // and headerless pieces that fit the one-launch kernels (the pb scans
     // follow as a second launch unless -codec_fused_scan_in_kernel, which
     // needs every scan to name the pieces forming its message)
-    const bool fused = FLAGS_codec_fused && nruns == 0 && ndec == 0 && h2d.empty() && d2h.empty() && ndecomp == 0 &&
-                       nstreams == 0 && (ncomp || nhpieces) && comp_max <= kFusedMaxBlock && hpiece_max <= kFusedMaxBlock;
+    const bool fused = FLAGS_codec_fused && nruns == 0 && nmsgs == 0 && ndec == 0 && h2d.empty() && d2h.empty() &&
+                       ndecomp == 0 && nstreams == 0 && (ncomp || nhpieces) && comp_max <= kFusedMaxBlock && hpiece_max <= kFusedMaxBlock;
     bool scan_in_kernel = fused && FLAGS_codec_fused_scan_in_kernel && nscan > 0;
     for (size_t i = 0; scan_in_kernel && i < b->reqs.size(); ++i) {
         const CodecRequest* r = b->reqs[i];
@@ -305,6 +359,21 @@ bool launch(CBatch* b, int device) {
     }
     if (rc == 0 && nruns) rc = LaunchPbRunEncode(b->run_jobs.p, (int)nruns, b->run_err.p, s);
     g_run_chunks.fetch_add((int64_t)nruns, std::memory_order_relaxed);
+    if (rc == 0 && nmsgs) {
+        PbMsgTables mt;
+        mt.msgs = b->msg_jobs.p;
+        mt.nmsgs = (int)nmsgs;
+        mt.fields = b->msg_fields.p;
+        mt.nfields = (int)nmfields;
+        mt.chunks = b->msg_chunks.p;
+        mt.nchunks = (int)nmchunks;
+        mt.prefix = b->msg_prefix;
+        mt.base = b->msg_base;
+        mt.res = b->msg_res.p;
+        mt.fres = b->msg_fres.p;
+        rc = LaunchPbMsgEncode(mt, s);
+    }
+    g_msg_chunks.fetch_add((int64_t)nmchunks, std::memory_order_relaxed);
     if (rc == 0 && !h2d.empty()) rc = LaunchBatchedCopy(h2d.data(), (int)h2d.size(), s);
     if (rc == 0 && ncomp) {
         rc = LaunchSnappyCompress(b->comp_jobs.p, (int)ncomp, comp_max, b->scratch, b->comp_len.p, b->comp_err.p, s);
@@ -426,6 +495,9 @@ int RunCodecRequest(CodecRequest* r, int device) {
         r->decomp_err.assign(mine->decomp_err.p + d0, mine->decomp_err.p + d0 + r->decomp.size());
         const size_t r0 = mine->run_first[idx];
         r->run_err.assign(mine->run_err.p + r0, mine->run_err.p + r0 + r->runs.size());
+        const size_t m0 = mine->msg_first[idx], mf0 = mine->mfield_first[idx];
+        r->msg_res.assign(mine->msg_res.p + m0, mine->msg_res.p + m0 + r->msgs.size());
+        r->msg_field_res.assign(mine->msg_fres.p + mf0, mine->msg_fres.p + mf0 + r->msg_fields.size());
         const size_t q0 = mine->dec_first[idx];
         r->dec_counts.assign(mine->dec_counts.p + q0, mine->dec_counts.p + q0 + r->dec_runs.size());
         r->dec_err.assign(mine->dec_err.p + q0, mine->dec_err.p + q0 + r->dec_runs.size());
@@ -461,6 +533,7 @@ CodecBatchStats GetCodecBatchStats() {
     s.run_chunks = g_run_chunks.load(std::memory_order_relaxed);
     s.decode_chunks = g_dec_chunks.load(std::memory_order_relaxed);
     s.fused_launches = g_fused_launches.load(std::memory_order_relaxed);
+    s.msg_chunks = g_msg_chunks.load(std::memory_order_relaxed);
     s.timed = g_timed.load(std::memory_order_relaxed);
     s.queue_us = g_queue_us.load(std::memory_order_relaxed);
     s.api_us = g_api_us.load(std::memory_order_relaxed);

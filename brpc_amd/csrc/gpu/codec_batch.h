@@ -21,6 +21,12 @@ struct CodecRequest {
     // numeric runs encoded first (K2 packed fields / K6 JSON arrays), into
     // buffers the later stages may read (the body the compressor takes)
     std::vector<PbRunChunk> runs;
+    // messages built in device memory from device arrays (LaunchPbMsgEncode),
+    // right after the runs: later stages may read them too. Every index in
+    // the three tables is relative to this request (the batch rebases them)
+    std::vector<PbMsgJob> msgs;
+    std::vector<PbMsgField> msg_fields;
+    std::vector<PbMsgChunk> msg_chunks;
     // staging copies issued before the codec kernels (host/pinned -> HBM)
     std::vector<Segment> h2d;
     // codec jobs; pointers in the jobs are device-accessible
@@ -55,6 +61,8 @@ struct CodecRequest {
     std::vector<int> stream_err;  // 0, or the split / piece decode code
     std::vector<int> piece_err;
     std::vector<int32_t> run_err;  // per chunk: 0, or 1 when the device size disagreed (nothing written)
+    std::vector<PbMsgResult> msg_res;             // per message: length and code
+    std::vector<PbMsgFieldResult> msg_field_res;  // per message field: where its payload went
     std::vector<uint32_t> dec_counts;  // per decode chunk: varints ending in it
     std::vector<int32_t> dec_err;      // per decode chunk: 0, or 1 for a malformed varint
     std::vector<uint64_t> scan_fields;  // 2 * kCodecScanFields per scan
@@ -64,6 +72,9 @@ struct CodecRequest {
     // device codec path issued ~20 allocations per RPC building fresh ones).
     void Reset() {
         runs.clear();
+        msgs.clear();
+        msg_fields.clear();
+        msg_chunks.clear();
         h2d.clear();
         comp.clear();
         decomp.clear();
@@ -84,6 +95,8 @@ struct CodecRequest {
         stream_err.clear();
         piece_err.clear();
         run_err.clear();
+        msg_res.clear();
+        msg_field_res.clear();
         dec_counts.clear();
         dec_err.clear();
         scan_fields.clear();
@@ -98,7 +111,7 @@ constexpr uint32_t kCodecScanFields = 128;
 int RunCodecRequest(CodecRequest* r, int device);
 
 struct CodecBatchStats {
-    int64_t requests = 0, launches = 0, run_chunks = 0, decode_chunks = 0, fused_launches = 0;
+    int64_t requests = 0, launches = 0, run_chunks = 0, decode_chunks = 0, fused_launches = 0, msg_chunks = 0;
     // latency breakdown summed over `timed` requests (us): waiting for a
     // launch, launch API, launch -> completion seen, completion -> resumed
     int64_t timed = 0, queue_us = 0, api_us = 0, gpu_us = 0, wake_us = 0;

@@ -4,9 +4,11 @@
 #include <atomic>
 #include <vector>
 
+#include "base/buf.h"
 #include "base/flags.h"
 #include "base/pool.h"
 #include "gpu/codec_batch.h"
+#include "gpu/gpu.h"
 #include "gpu/hbm_pool.h"
 #include "gpu/kernels.h"
 #include "policy/device_payload.h"
@@ -23,6 +25,7 @@ namespace {
 
 std::atomic<int64_t> g_encodes{0}, g_enc_bytes{0}, g_enc_out{0}, g_decodes{0}, g_dec_bytes{0}, g_bad_tables{0},
     g_dec_err{0}, g_scans{0}, g_runs{0}, g_run_bytes{0}, g_run_elems{0}, g_run_err{0};
+std::atomic<int64_t> g_built{0}, g_built_fields{0}, g_built_bytes{0}, g_build_err{0};
 
 uint32_t varint_len(uint64_t v) {
     uint32_t n = 1;
@@ -249,8 +252,211 @@ int DeviceDecodePackedRuns(DevicePackedRun* runs, int n, int device) {
     return 0;
 }
 
+namespace {
+
+constexpr uint32_t kMaxFieldNumber = (1u << 29) - 1;
+
+uint32_t elem_bytes(uint32_t kind) {
+    return kind == PB_RUN_BOOL || kind == kDeviceFieldBytes ? 1 : (kind <= PB_RUN_SINT32 ? 4 : 8);
+}
+
+// Worst-case payload of a field, or false when the field is refused by what
+// the host can check without its pointers.
+bool field_worst(const DeviceMessageField& f, bool headerless, uint64_t* worst) {
+    if (f.kind > kDeviceFieldBytes) return false;
+    if (!headerless && (f.number == 0 || f.number > kMaxFieldNumber)) return false;
+    const uint64_t per = f.kind == PB_RUN_BOOL || f.kind == kDeviceFieldBytes
+                             ? 1
+                             : (f.kind == PB_RUN_UINT32 || f.kind == PB_RUN_SINT32 ? 5 : 10);
+    if (f.count > 0xFFFFFFFFull / per) return false;
+    *worst = f.count * per;
+    return true;
+}
+
+bool field_emitted(const DeviceMessageField& f) { return f.count > 0 || f.kind == kDeviceFieldBytes; }
+
+// Worst-case size of the whole message; false when refused.
+bool message_worst(const DeviceMessageField* fields, int n, bool headerless, uint64_t* total) {
+    *total = 0;
+    if (n < 0 || n > (int)kCodecScanFields || (n > 0 && !fields)) return false;
+    for (int i = 0; i < n; ++i) {
+        uint64_t worst = 0;
+        if (!field_worst(fields[i], headerless, &worst)) return false;
+        if (!field_emitted(fields[i])) continue;
+        *total += worst;
+        if (!headerless) *total += varint_len((uint64_t)fields[i].number << 3) + varint_len(worst);
+    }
+    return true;
+}
+
+bool job_ok(const DeviceMessageJob& j, bool headerless) {
+    uint64_t total = 0;
+    if (!j.dst || !message_worst(j.fields, j.nfields, headerless, &total)) return false;
+    for (int i = 0; i < j.nfields; ++i) {
+        const DeviceMessageField& f = j.fields[i];
+        if (f.count > 0 && (!f.src || ((uintptr_t)f.src & (elem_bytes(f.kind) - 1)))) return false;
+    }
+    return true;
+}
+
+// Every job that passes the host checks becomes one message of one codec
+// request; a job without an emitted field is an empty message and needs no
+// device work.
+int build_messages(DeviceMessageJob* jobs, int n, bool headerless, int device) {
+    if (n <= 0) return 0;
+    PooledRequest pooled;
+    CodecRequest& req = *pooled.r;
+    std::vector<int> row(n, -1);  // job -> its message in the request
+    for (int k = 0; k < n; ++k) {
+        DeviceMessageJob& j = jobs[k];
+        j.len = 0;
+        j.err = 0;
+        if (!job_ok(j, headerless)) {
+            j.err = 2;
+            const int nf = j.fields ? std::min(j.nfields, (int)kCodecScanFields) : 0;
+            for (int i = 0; i < nf; ++i) j.fields[i].off = j.fields[i].len = 0;
+            g_build_err.fetch_add(1, std::memory_order_relaxed);
+            continue;
+        }
+        PbMsgJob m;
+        m.dst = static_cast<uint8_t*>(j.dst);
+        m.cap = j.cap;
+        m.first_field = (uint32_t)req.msg_fields.size();
+        m.nfields = 0;
+        for (int i = 0; i < j.nfields; ++i) {
+            DeviceMessageField& f = j.fields[i];
+            f.off = f.len = 0;
+            if (!field_emitted(f)) continue;
+            PbMsgField mf;
+            mf.msg = (uint32_t)req.msgs.size();
+            mf.tag = (f.number << 3) | 2;
+            mf.first_chunk = (uint32_t)req.msg_chunks.size();
+            mf.headerless = headerless ? 1 : 0;
+            mf.pad = 0;
+            const uint32_t eb = elem_bytes(f.kind);
+            const uint64_t per = f.kind == kDeviceFieldBytes ? kPbMsgBytesChunk : kPbRunChunkElems;
+            for (uint64_t o = 0; o < f.count; o += per) {
+                PbMsgChunk c;
+                c.src = static_cast<const uint8_t*>(f.src) + o * eb;
+                c.count = (uint32_t)std::min<uint64_t>(per, f.count - o);
+                c.kind = f.kind;
+                c.field = (uint32_t)req.msg_fields.size();
+                c.first = mf.first_chunk;
+                req.msg_chunks.push_back(c);
+            }
+            mf.nchunks = (uint32_t)req.msg_chunks.size() - mf.first_chunk;
+            req.msg_fields.push_back(mf);
+            ++m.nfields;
+        }
+        if (m.nfields == 0) continue;
+        row[k] = (int)req.msgs.size();
+        req.msgs.push_back(m);
+    }
+    if (!req.msgs.empty() && RunCodecRequest(&req, device) != 0) return -1;
+    for (int k = 0; k < n; ++k) {
+        DeviceMessageJob& j = jobs[k];
+        if (j.err) continue;
+        int64_t nf = 0;
+        if (row[k] >= 0) {
+            const PbMsgResult& r = req.msg_res[row[k]];
+            j.len = r.len;
+            j.err = r.err;
+            if (j.err) {
+                g_build_err.fetch_add(1, std::memory_order_relaxed);
+                continue;
+            }
+            size_t at = req.msgs[row[k]].first_field;
+            for (int i = 0; i < j.nfields; ++i) {
+                DeviceMessageField& f = j.fields[i];
+                if (!field_emitted(f)) continue;
+                f.off = req.msg_field_res[at].off;
+                f.len = req.msg_field_res[at].len;
+                ++at;
+                ++nf;
+            }
+        }
+        g_built.fetch_add(1, std::memory_order_relaxed);
+        g_built_fields.fetch_add(nf, std::memory_order_relaxed);
+        g_built_bytes.fetch_add((int64_t)j.len, std::memory_order_relaxed);
+    }
+    return 0;
+}
+
+struct ArenaBlock {
+    size_t n;
+    int device;
+};
+void free_arena_block(void* p, void* arg) {
+    ArenaBlock* a = static_cast<ArenaBlock*>(arg);
+    HbmFree(p, a->n, a->device);
+    delete a;
+}
+
+}  // namespace
+
+uint64_t DeviceMessageWorstCaseBytes(const DeviceMessageField* fields, int n) {
+    uint64_t total = 0;
+    return message_worst(fields, n, false, &total) ? total : 0;
+}
+
+int DeviceBuildMessages(DeviceMessageJob* jobs, int n, int device) { return build_messages(jobs, n, false, device); }
+
+int BuildDeviceMessage(DeviceMessageField* fields, int n, Buf* out, int device) {
+    uint64_t worst = 0;
+    if (!out || !message_worst(fields, n, false, &worst)) {
+        g_build_err.fetch_add(1, std::memory_order_relaxed);
+        return 2;
+    }
+    // an arena block even for an empty message: the job needs a destination
+    const size_t cap = (size_t)std::max<uint64_t>(worst, 16);
+    void* dst = HbmAlloc(cap, device);
+    if (!dst) return -1;
+    DeviceMessageJob job;
+    job.fields = fields;
+    job.nfields = n;
+    job.dst = dst;
+    job.cap = cap;
+    const int rc = DeviceBuildMessages(&job, 1, device);
+    if (rc != 0 || job.err != 0 || job.len == 0) {
+        HbmFree(dst, cap, device);
+        return rc != 0 ? -1 : job.err;
+    }
+    ArenaBlock* a = new ArenaBlock{cap, device};
+    if (AppendDevice(out, dst, (size_t)job.len, device, free_arena_block, a) != 0) {
+        free_arena_block(dst, a);
+        return -1;
+    }
+    return 0;
+}
+
+int DeviceEncodePackedRuns(DevicePackedEncodeRun* runs, int n, int device) {
+    if (n <= 0) return 0;
+    std::vector<DeviceMessageField> fields(n);
+    std::vector<DeviceMessageJob> jobs(n);
+    for (int i = 0; i < n; ++i) {
+        fields[i].kind = runs[i].kind;
+        fields[i].src = runs[i].src;
+        fields[i].count = runs[i].count;
+        jobs[i].fields = &fields[i];
+        // a bare run has no bytes kind: refused through the field count
+        jobs[i].nfields = runs[i].kind <= PB_RUN_BOOL ? 1 : -1;
+        jobs[i].dst = runs[i].dst;
+        jobs[i].cap = runs[i].cap;
+    }
+    const int rc = build_messages(jobs.data(), n, true, device);
+    for (int i = 0; i < n; ++i) {
+        runs[i].bytes = rc == 0 && jobs[i].err == 0 ? jobs[i].len : 0;
+        runs[i].err = rc == 0 ? jobs[i].err : 0;
+    }
+    return rc;
+}
+
 DeviceCodecStats GetDeviceCodecStats() {
     DeviceCodecStats s;
+    s.built_messages = g_built.load();
+    s.built_fields = g_built_fields.load();
+    s.built_bytes = g_built_bytes.load();
+    s.build_errors = g_build_err.load();
     s.encodes = g_encodes.load();
     s.encoded_bytes = g_enc_bytes.load();
     s.encoded_out_bytes = g_enc_out.load();

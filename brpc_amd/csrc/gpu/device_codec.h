@@ -21,6 +21,7 @@
 
 namespace mrpc {
 struct DevicePayloadIndex;
+class Buf;
 namespace gpu {
 
 struct DeviceSnappyLayout {
@@ -84,11 +85,68 @@ struct DevicePackedRun {
 // -1 only on a device error; per-run codes in runs[i].err.
 int DeviceDecodePackedRuns(DevicePackedRun* runs, int n, int device);
 
+// ---- the encode side: arrays in device memory -> one serialized message in
+// device memory, ready to lend as a device attachment. The host never sees a
+// value and learns only lengths (the reference serializes every message on
+// the host: SerializeToString / SerializeAsCompressedData,
+// src/brpc/compress.cpp:92).
+// Field kind of raw bytes, next to the gpu::PbRunKind values 0..6: a
+// length-delimited field copied verbatim (string / bytes / embedded message,
+// and packed float / double / fixed32 / fixed64, whose wire form is their
+// memory image). The packed-run decoder keeps refusing it.
+constexpr uint32_t kDeviceFieldBytes = 7;
+struct DeviceMessageField {
+    uint32_t number = 0;        // 1 .. 2^29-1
+    uint32_t kind = 0;          // gpu::PbRunKind (a packed field) or kDeviceFieldBytes
+    const void* src = nullptr;  // device; vector layout of the kind, naturally aligned
+    uint64_t count = 0;         // elements (bytes for kDeviceFieldBytes)
+    uint64_t off = 0, len = 0;  // out: the payload's position in the message
+};
+// Most bytes the message can take (10 per element for int32 and the 64-bit
+// kinds, 5 for uint32 / sint32, 1 for bool and bytes; a header is its tag plus
+// the varint of the worst payload). Host only. 0 when the fields would be
+// refused (or when they make an empty message).
+uint64_t DeviceMessageWorstCaseBytes(const DeviceMessageField* fields, int n);
+struct DeviceMessageJob {
+    DeviceMessageField* fields = nullptr;
+    int nfields = 0;
+    void* dst = nullptr;  // device, cap bytes
+    uint64_t cap = 0;
+    uint64_t len = 0;  // out: serialized size (with err 3: the size it needs)
+    // out: 0 built; 2 refused before any launch (null src with count > 0, null
+    // dst, bad kind, field number 0 or above 2^29-1, more than
+    // kCodecScanFields fields, misaligned src, a field whose worst case
+    // exceeds 2^32-1 bytes); 3 longer than cap (dst untouched); 4 a source
+    // array changed while the message was built
+    int err = 0;
+};
+// Fields are emitted in the order given; a packed field of count 0 is
+// omitted (as the host serializer does), a bytes field of length 0 is tag +
+// 0x00. All jobs form one codec request. Returns -1 only on a device error.
+int DeviceBuildMessages(DeviceMessageJob* jobs, int n, int device);
+// Builds into a fresh arena block of the worst-case size and appends exactly
+// the message's bytes to *out as one DEVICE block (its deleter frees the whole
+// allocation). 0, a DeviceMessageJob::err code, or -1 on a device error.
+int BuildDeviceMessage(DeviceMessageField* fields, int n, Buf* out, int device);
+// The mirror of DeviceDecodePackedRuns: a bare packed run (no tag, no
+// length) per array, through the same kernels.
+struct DevicePackedEncodeRun {
+    const void* src = nullptr;
+    uint64_t count = 0;
+    uint32_t kind = 0;  // gpu::PbRunKind
+    void* dst = nullptr;
+    uint64_t cap = 0;
+    uint64_t bytes = 0;  // out
+    int err = 0;         // out: as DeviceMessageJob::err
+};
+int DeviceEncodePackedRuns(DevicePackedEncodeRun* runs, int n, int device);
+
 struct DeviceCodecStats {
     int64_t encodes = 0, encoded_bytes = 0, encoded_out_bytes = 0;
     int64_t decodes = 0, decoded_bytes = 0, bad_tables = 0, decode_errors = 0;
     int64_t scans = 0;
     int64_t packed_runs = 0, packed_bytes = 0, packed_elems = 0, packed_errors = 0;
+    int64_t built_messages = 0, built_fields = 0, built_bytes = 0, build_errors = 0;
 };
 DeviceCodecStats GetDeviceCodecStats();
 

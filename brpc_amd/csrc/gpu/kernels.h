@@ -261,6 +261,70 @@ struct PbRunDecodeChunk {
 int LaunchPbRunDecode(const PbRunDecodeChunk* chunks, int n, uint32_t* counts, uint32_t* prefix, int32_t* err,
                       hipStream_t s);
 
+// Message builder (the encode mirror of the packed-run decoder): arrays in
+// device memory become whole serialized protobuf messages in device memory,
+// the host knowing no value and learning only lengths. A message is a list
+// of length-delimited fields; a field's payload is the concatenation of its
+// chunks, each <= kPbRunChunkElems numeric elements encoded as varints (a
+// packed field) or <= kPbMsgBytesChunk raw bytes copied verbatim (a bytes
+// field, and so a packed float/double/fixed field: its wire form is its
+// memory image). Four launches on one stream, ordered by the launches alone
+// (no workgroup waits on another):
+//   size   a wave per chunk writes its encoded size into prefix[chunk]
+//          (prefix: device memory, nchunks + 1 entries; the last gets 0)
+//   prefix pb_run_prefix_kernel scans them (exclusive, mod 2^32)
+//   layout a wave per message scans header + payload lengths of its fields in
+//          64 bits; a message longer than its cap is marked (err 3) and gets
+//          nothing written, else every header is written and base[field]
+//          (device memory, nfields entries) gets the payload's address
+//   place  a workgroup per chunk encodes it into LDS and copies it to
+//          base[field] + (prefix[chunk] - prefix[field's first chunk])
+// The three tables are device-readable (pinned host) arrays; res / fres are
+// device-writable (pinned host) results.
+constexpr uint32_t PB_MSG_BYTES = 7;  // chunk kind next to the PbRunKind values: raw bytes
+constexpr uint32_t kPbMsgBytesChunk = 16384;
+struct PbMsgJob {
+    uint8_t* dst;  // the message's first byte (device-writable), never null
+    uint64_t cap;  // bytes available at dst
+    uint32_t first_field, nfields;  // its fields, in wire order
+};
+struct PbMsgField {
+    uint32_t msg;          // owning message
+    uint32_t tag;          // (number << 3) | 2
+    uint32_t first_chunk;  // its chunks, in order (a valid index even when nchunks == 0)
+    uint32_t nchunks;
+    uint32_t headerless;   // 1: a bare run, neither tag nor length is written
+    uint32_t pad;
+};
+struct PbMsgChunk {
+    const void* src;  // this chunk's first element / byte (device-readable, naturally aligned)
+    uint32_t count;   // elements, 1..kPbRunChunkElems (bytes, 1..kPbMsgBytesChunk, for PB_MSG_BYTES)
+    uint32_t kind;    // PbRunKind or PB_MSG_BYTES
+    uint32_t field;   // owning field
+    uint32_t first;   // the owning field's first chunk
+};
+struct PbMsgResult {
+    uint64_t len;  // serialized size (also when it did not fit)
+    int32_t err;   // 0, 3 (longer than cap; nothing written), 4 (a source changed between size and place)
+    int32_t pad;
+};
+struct PbMsgFieldResult {
+    uint64_t off, len;  // the payload's position in the message (0, 0 when the message failed)
+};
+struct PbMsgTables {
+    const PbMsgJob* msgs = nullptr;
+    int nmsgs = 0;
+    const PbMsgField* fields = nullptr;
+    int nfields = 0;
+    const PbMsgChunk* chunks = nullptr;
+    int nchunks = 0;
+    uint32_t* prefix = nullptr;  // device memory, nchunks + 1 entries
+    uint64_t* base = nullptr;    // device memory, nfields entries
+    PbMsgResult* res = nullptr;          // nmsgs
+    PbMsgFieldResult* fres = nullptr;    // nfields
+};
+int LaunchPbMsgEncode(const PbMsgTables& t, hipStream_t s);
+
 // JSON structural index (gpu/json_kernels.hip): out_pos receives, in order,
 // the byte offsets of every unescaped '"' and of every { } [ ] : , outside
 // strings; count_dev the number found (positions past max_out are dropped

@@ -502,7 +502,294 @@ __global__ void __launch_bounds__(kRunThreads) pb_run_decode_kernel(const PbRunD
     }
 }
 
+// --------------------------------------------------------- message builder
+// Arrays in HBM -> serialized messages in HBM (kernels.h: size, prefix,
+// layout, place). The host knows no value, so nothing here takes a size from
+// it: the size pass measures every chunk, the prefix kernel above turns the
+// sizes into offsets within each field, and the layout pass adds the headers.
+constexpr int kMsgImage16 = (kPbRunChunkElems * 10 + 16 + 15) / 16;  // a numeric chunk at any 16-byte phase
+static_assert(kMsgImage16 * 16 >= (int)kPbMsgBytesChunk + 32, "a bytes chunk is staged in the same image");
+
+__device__ __forceinline__ uint32_t msg_chunk_count(const PbMsgChunk& c) {
+    const uint32_t most = c.kind == PB_MSG_BYTES ? kPbMsgBytesChunk : kPbRunChunkElems;
+    return c.count < most ? c.count : most;
+}
+
+// A lane's share of the encoded size of a numeric chunk whose source is
+// 16-byte aligned, read as 16-byte units (2 or 4 elements each; unit u goes
+// to lane u % 64). The last unit may reach past the chunk's last element:
+// inside its aligned 16 bytes, so inside its page.
+template <int kElemBytes>
+__device__ __forceinline__ uint32_t msg_size_units(const void* src_, uint32_t count, uint32_t kind, int lane) {
+    constexpr int kIn = 16 / kElemBytes;
+    constexpr int kUnits = kPbRunChunkElems / kIn / 64;
+    const u32x4* src = static_cast<const u32x4*>(src_);
+    const uint32_t nunits = (count + kIn - 1) / kIn;
+    u32x4 v[kUnits];
+#pragma unroll
+    for (int k = 0; k < kUnits; ++k) {
+        const uint32_t u = (uint32_t)lane + 64u * k;
+        if (u < nunits) v[k] = src[u];
+    }
+    uint32_t n = 0;
+#pragma unroll
+    for (int k = 0; k < kUnits; ++k) {
+        const uint32_t u = (uint32_t)lane + 64u * k;
+        if (u >= nunits) continue;
+        const uint32_t w[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+        for (int j = 0; j < kIn; ++j) {
+            if (u * kIn + j >= count) continue;
+            uint64_t raw;  // as run_load makes it
+            if (kElemBytes == 8) {
+                raw = ((uint64_t)w[2 * j + 1] << 32) | w[2 * j];
+            } else {
+                raw = kind == PB_RUN_UINT32 ? (uint64_t)w[j] : (uint64_t)(int64_t)(int32_t)w[j];
+            }
+            n += run_varint_len(run_value(raw, kind));
+        }
+    }
+    return n;
+}
+
+__global__ void __launch_bounds__(kRunThreads) pb_msg_size_kernel(const PbMsgChunk* __restrict__ chunks, int nchunks,
+                                                                  uint32_t* __restrict__ sizes) {
+    // one wave per chunk, no LDS, no barriers. A lane's share of the chunk
+    // is all loaded before any of it is used, so a wave keeps its whole chunk
+    // (16 KiB of 64-bit elements) in flight: the pass only reads, it is bound
+    // by HBM. 16-byte loads when the source allows them, else one element each
+    constexpr int kPer = kPbRunChunkElems / 64;
+    const int lane = threadIdx.x & 63;
+    const int nwaves = (int)gridDim.x * (kRunThreads / 64);
+    if (blockIdx.x == 0 && threadIdx.x == 0) sizes[nchunks] = 0;  // becomes the total under the scan
+    for (int ci = (int)blockIdx.x * (kRunThreads / 64) + (int)(threadIdx.x >> 6); ci < nchunks; ci += nwaves) {
+        const PbMsgChunk c = chunks[ci];
+        const uint32_t count = msg_chunk_count(c);
+        uint32_t n = count;  // bools and raw bytes: one byte each
+        if (c.kind < PB_RUN_BOOL) {
+            if (((uintptr_t)c.src & 15) == 0) {
+                n = c.kind <= PB_RUN_SINT32 ? msg_size_units<4>(c.src, count, c.kind, lane)
+                                            : msg_size_units<8>(c.src, count, c.kind, lane);
+            } else {
+                uint64_t raws[kPer];
+#pragma unroll
+                for (int k = 0; k < kPer; ++k) {
+                    const uint32_t i = (uint32_t)lane + 64u * k;
+                    raws[k] = i < count ? run_load(c.src, i, c.kind) : 0;
+                }
+                n = 0;
+#pragma unroll
+                for (int k = 0; k < kPer; ++k) {
+                    const uint32_t i = (uint32_t)lane + 64u * k;
+                    if (i < count) n += run_varint_len(run_value(raws[k], c.kind));
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+        }
+        if (lane == 0) sizes[ci] = n;
+    }
+}
+
+__device__ __forceinline__ uint32_t put_varint(uint8_t* o, uint64_t v) {
+    uint32_t n = 0;
+    while (v >= 0x80) {
+        o[n++] = (uint8_t)(v | 0x80);
+        v >>= 7;
+    }
+    o[n++] = (uint8_t)v;
+    return n;
+}
+
+// Payload and header length of field f (payloads stay below 2^32: the host
+// refuses a field whose worst case does not).
+__device__ __forceinline__ void msg_field_lens(const PbMsgField& f, const uint32_t* prefix, uint32_t* plen,
+                                               uint32_t* hlen) {
+    *plen = prefix[f.first_chunk + f.nchunks] - prefix[f.first_chunk];
+    *hlen = f.headerless ? 0 : run_varint_len(f.tag) + run_varint_len(*plen);
+}
+
+// One wave per message: field k's header starts where fields 0..k-1 end.
+// The length is summed first, so a message that does not fit gets no byte.
+__global__ void __launch_bounds__(64) pb_msg_layout_kernel(const PbMsgJob* __restrict__ msgs,
+                                                           const PbMsgField* __restrict__ fields,
+                                                           const uint32_t* __restrict__ prefix,
+                                                           uint64_t* __restrict__ base, PbMsgResult* __restrict__ res,
+                                                           PbMsgFieldResult* __restrict__ fres) {
+    const PbMsgJob m = msgs[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    uint64_t total = 0;
+    for (uint32_t f0 = 0; f0 < m.nfields; f0 += 64) {
+        uint64_t mine = 0;
+        if (f0 + lane < m.nfields) {
+            uint32_t plen, hlen;
+            msg_field_lens(fields[m.first_field + f0 + lane], prefix, &plen, &hlen);
+            mine = (uint64_t)plen + hlen;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+        total += mine;
+    }
+    const bool fits = total <= m.cap;
+    uint64_t carry = 0;
+    for (uint32_t f0 = 0; f0 < m.nfields; f0 += 64) {
+        const bool live = f0 + lane < m.nfields;
+        const uint32_t gf = m.first_field + f0 + lane;
+        PbMsgField f;
+        uint32_t plen = 0, hlen = 0;
+        if (live) {
+            f = fields[gf];
+            msg_field_lens(f, prefix, &plen, &hlen);
+        }
+        const uint64_t mine = (uint64_t)plen + hlen;
+        uint64_t incl = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint64_t y = __shfl_up(incl, off, 64);
+            if (lane >= (uint32_t)off) incl += y;
+        }
+        const uint64_t off = carry + incl - mine;
+        if (live) {
+            if (fits) {
+                uint8_t* o = m.dst + off;
+                if (!f.headerless) {
+                    o += put_varint(o, f.tag);
+                    put_varint(o, plen);
+                }
+                base[gf] = (uint64_t)(uintptr_t)(m.dst + off + hlen);
+                fres[gf] = PbMsgFieldResult{off + hlen, plen};
+            } else {
+                base[gf] = 0;  // the place pass skips the field's chunks
+                fres[gf] = PbMsgFieldResult{0, 0};
+            }
+        }
+        carry += __shfl(incl, 63, 64);
+    }
+    if (lane == 0) res[blockIdx.x] = PbMsgResult{total, fits ? 0 : 3, 0};
+}
+
+// One workgroup per chunk. A numeric chunk is encoded like
+// pb_run_encode_kernel's varint path, into an LDS image that sits at the
+// destination's 16-byte phase, so it leaves as 16-byte LDS reads and 16-byte
+// stores around an unaligned head and tail. What the chunk encodes to is
+// compared with what the size pass measured: the two differ only when the
+// source changed in between, and then nothing is written (the offsets of
+// every later chunk were derived from the measured size).
+__global__ void __launch_bounds__(kRunThreads) pb_msg_place_kernel(const PbMsgChunk* __restrict__ chunks,
+                                                                   const PbMsgField* __restrict__ fields,
+                                                                   const uint32_t* __restrict__ prefix,
+                                                                   const uint64_t* __restrict__ base,
+                                                                   PbMsgResult* __restrict__ res) {
+    __shared__ u32x4 image16[kMsgImage16];
+    __shared__ uint32_t wave_tot[kPbRunChunkElems / kRunThreads][kRunThreads / 64];
+    uint8_t* image = reinterpret_cast<uint8_t*>(image16);
+    const uint32_t ci = blockIdx.x;
+    const PbMsgChunk c = chunks[ci];
+    const uint64_t b = base[c.field];
+    if (!b) return;  // the message did not fit (the whole workgroup leaves)
+    const uint32_t want = prefix[ci + 1] - prefix[ci];
+    uint8_t* dst = reinterpret_cast<uint8_t*>((uintptr_t)(b + (uint32_t)(prefix[ci] - prefix[c.first])));
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint32_t count = msg_chunk_count(c);
+    if (c.kind == PB_MSG_BYTES) {
+        // a straight copy through LDS: 16-byte loads of the aligned span
+        // around the source, all issued before the first is stored
+        const uint8_t* p = static_cast<const uint8_t*>(c.src);
+        const uint32_t a = (uint32_t)((uintptr_t)p & 15);
+        const u32x4* src = reinterpret_cast<const u32x4*>(p - a);
+        const uint32_t n16 = (a + count + 15) >> 4;
+        constexpr int kUnits = (kPbMsgBytesChunk / 16 + 2 + kRunThreads - 1) / kRunThreads;
+        u32x4 v[kUnits];
+#pragma unroll
+        for (int k = 0; k < kUnits; ++k) {
+            const uint32_t i = (uint32_t)t + (uint32_t)k * kRunThreads;
+            if (i < n16) v[k] = src[i];
+        }
+#pragma unroll
+        for (int k = 0; k < kUnits; ++k) {
+            const uint32_t i = (uint32_t)t + (uint32_t)k * kRunThreads;
+            if (i < n16) image16[i] = v[k];
+        }
+        __syncthreads();
+        if (((uintptr_t)dst & 15) == a) {
+            copy_out_aligned(dst, image, a, count);
+        } else {
+            copy_out(dst, image + a, count);
+        }
+        return;
+    }
+    const uint32_t sh = (uint32_t)((uintptr_t)dst & 15);
+    constexpr int kRounds = kPbRunChunkElems / kRunThreads;
+    uint64_t raws[kRounds];
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const uint32_t i = (uint32_t)r * kRunThreads + t;
+        raws[r] = i < count ? run_load(c.src, i, c.kind) : 0;
+    }
+    // lane t of round r takes element 256r + t. Every round's lengths are
+    // scanned inside the waves first, so the whole chunk needs two barriers
+    // (the wave totals of all rounds, then the image), not three per round
+    uint32_t lens[kRounds], incls[kRounds];
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const uint32_t i = (uint32_t)r * kRunThreads + t;
+        raws[r] = run_value(raws[r], c.kind);
+        lens[r] = i < count ? run_varint_len(raws[r]) : 0;
+        uint32_t incl = lens[r];
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t y = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += y;
+        }
+        incls[r] = incl;
+        if (lane == 63) wave_tot[r][wave] = incl;
+    }
+    __syncthreads();
+    uint32_t total = 0;
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        uint32_t pos = total + incls[r] - lens[r];
+#pragma unroll
+        for (int w = 0; w < kRunThreads / 64; ++w) {
+            const uint32_t x = wave_tot[r][w];
+            if (w < wave) pos += x;
+            total += x;
+        }
+        uint8_t* o = image + sh + pos;
+        uint64_t v = raws[r];
+        for (uint32_t j = 0; j < lens[r]; ++j) {
+            o[j] = (uint8_t)((v & 0x7f) | (j + 1 < lens[r] ? 0x80 : 0));
+            v >>= 7;
+        }
+    }
+    __syncthreads();
+    if (total != want) {
+        if (t == 0) res[fields[c.field].msg].err = 4;
+        return;
+    }
+    copy_out_aligned(dst, image, sh, total);
+}
+
 }  // namespace
+
+int LaunchPbMsgEncode(const PbMsgTables& t, hipStream_t s) {
+    if (t.nmsgs <= 0) return 0;
+    if (!t.prefix || !t.base || t.nfields < 0 || t.nchunks < 0) return -1;
+    const int size_wgs = (t.nchunks + kRunThreads / 64 - 1) / (kRunThreads / 64);
+    const int size_grid = size_wgs < 1 ? 1 : (size_wgs < 2048 ? size_wgs : 2048);
+    hipLaunchKernelGGL(pb_msg_size_kernel, dim3((unsigned)size_grid), dim3(kRunThreads), 0, s, t.chunks, t.nchunks,
+                       t.prefix);
+    if (hipGetLastError() != hipSuccess) return -1;
+    hipLaunchKernelGGL(pb_run_prefix_kernel, dim3(1), dim3(kPrefixThreads), 0, s, t.prefix, t.nchunks + 1);
+    if (hipGetLastError() != hipSuccess) return -1;
+    hipLaunchKernelGGL(pb_msg_layout_kernel, dim3((unsigned)t.nmsgs), dim3(64), 0, s, t.msgs, t.fields, t.prefix,
+                       t.base, t.res, t.fres);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (t.nchunks == 0) return 0;
+    hipLaunchKernelGGL(pb_msg_place_kernel, dim3((unsigned)t.nchunks), dim3(kRunThreads), 0, s, t.chunks, t.fields,
+                       t.prefix, t.base, t.res);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 int LaunchPbRunDecode(const PbRunDecodeChunk* chunks, int n, uint32_t* counts, uint32_t* prefix, int32_t* err,
                       hipStream_t s) {

@@ -14,8 +14,11 @@
 #include "mrpc/proto/echo.pb.h"
 #include "pb/dynamic.h"
 #include "pb/parser.h"
+#include "gpu/device_codec.h"
 #include "gpu/gpu.h"
 #include "gpu/hbm_pool.h"
+#include "gpu/kernels.h"
+#include "policy/device_payload.h"
 #include "rpc/channel.h"
 #include "rpc/combo_channels.h"
 #include "rpc/controller.h"
@@ -140,6 +143,8 @@ PressSession::PressSession() {}
 PressSession::~PressSession() {
     _channels.clear();
     if (_device_attachment) gpu::HbmFree(_device_attachment, _attachment.size(), _opt.gpu_device);
+    if (_build_body_dev) gpu::HbmFree(_build_body_dev, _build_body_len, _opt.gpu_device);
+    if (_build_ids_dev) gpu::HbmFree(_build_ids_dev, _build_ids.size() * sizeof(int64_t), _opt.gpu_device);
 }
 
 static bool read_file(const std::string& path, std::string* out) {
@@ -308,6 +313,10 @@ int PressSession::Init(const PressOptions& opt, std::string* error) {
             id = (int64_t)(q >> (q % 57));
             if ((q & 0xff) == 0) id = -id;
         }
+        if (_opt.device_build_ids > 0 && _opt.attachment_size <= 0) {
+            *error = "device_build_ids needs an attachment_size (the body the message is built around)";
+            return -1;
+        }
         if (_opt.attachment_size > 0) {
             if (!_opt.attachment_body.empty()) {
                 _attachment = EchoBody(_opt.attachment_body, (size_t)_opt.attachment_size);
@@ -325,7 +334,39 @@ int PressSession::Init(const PressOptions& opt, std::string* error) {
                     _attachment[i] = (char)r;
                 }
             }
-            if (_opt.attachment_pb) {
+            if (_opt.device_build_ids > 0) {
+                if (!_opt.device_attachment) {
+                    *error = "device_build_ids needs device_attachment";
+                    return -1;
+                }
+                if (gpu::Init(_opt.gpu_device, error) != 0) return -1;
+                // the parts stay in HBM; _attachment becomes what the host
+                // serializer makes of them (what every echo is compared with)
+                uint64_t b = 0xA0761D6478BD642Full;
+                _build_ids.resize((size_t)_opt.device_build_ids);
+                for (int64_t& id : _build_ids) {
+                    b ^= b << 13;
+                    b ^= b >> 7;
+                    b ^= b << 17;
+                    id = (int64_t)(b >> (b % 57));
+                    if ((b & 0xff) == 0) id = -id;
+                }
+                _build_body_len = _attachment.size();
+                _build_body_dev = gpu::HbmAlloc(_build_body_len, _opt.gpu_device);
+                _build_ids_dev = gpu::HbmAlloc(_build_ids.size() * sizeof(int64_t), _opt.gpu_device);
+                if (!_build_body_dev || !_build_ids_dev ||
+                    gpu::CopyHostToDevice(_build_body_dev, _attachment.data(), _build_body_len, _opt.gpu_device) != 0 ||
+                    gpu::CopyHostToDevice(_build_ids_dev, _build_ids.data(), _build_ids.size() * sizeof(int64_t),
+                                          _opt.gpu_device) != 0) {
+                    *error = "fail to upload the parts of the device-built attachment to HBM";
+                    return -1;
+                }
+                example::EchoRequest m;
+                m.set_message(_attachment);
+                *m.mutable_ids() = _build_ids;
+                _attachment.clear();
+                m.SerializeToString(&_attachment);
+            } else if (_opt.attachment_pb) {
                 example::EchoRequest m;
                 m.set_message(_attachment);
                 _attachment.clear();
@@ -334,7 +375,7 @@ int PressSession::Init(const PressOptions& opt, std::string* error) {
             char* blk = _attachment_buf.append_contiguous(_attachment.size());
             if (blk) memcpy(blk, _attachment.data(), _attachment.size());
             else _attachment_buf.append(_attachment);
-            if (_opt.device_attachment) {
+            if (_opt.device_attachment && !_build_body_dev) {
                 if (gpu::Init(_opt.gpu_device, error) != 0) return -1;
                 // arena memory: the xGMI transport lends it to the server
                 // without a copy (gpu/xgmi.h)
@@ -366,6 +407,7 @@ struct PressCall : public Closure {
     int64_t t0 = 0;
     int64_t nbytes = 0;
     bool check = false;
+    int build_rc = 0;  // device_build_ids: what BuildDeviceMessage returned
     void Run() override;
 };
 
@@ -391,8 +433,23 @@ void PressSession::issue(Worker* w, int64_t seq, PressCall* call, bool async) {
     if (_opt.gpu_process) call->echo_req.set_gpu_process(true);
     if (_opt.cpu_process) call->echo_req.set_cpu_process(true);
     if (call->echo_req.ids_size() != (int)_ids.size()) *call->echo_req.mutable_ids() = _ids;
-    if (_device_attachment) {
+    if (_build_body_dev) {
+        // the attachment of THIS call, serialized on the device from the
+        // arrays in HBM (the issuing fiber parks on the codec batch)
+        gpu::DeviceMessageField f[2];
+        f[0].number = 1;
+        f[0].kind = gpu::kDeviceFieldBytes;
+        f[0].src = _build_body_dev;
+        f[0].count = _build_body_len;
+        f[1].number = 8;
+        f[1].kind = gpu::PB_RUN_INT64;
+        f[1].src = _build_ids_dev;
+        f[1].count = _build_ids.size();
+        call->build_rc = gpu::BuildDeviceMessage(f, 2, &cntl.request_attachment(), _opt.gpu_device);
+    } else if (_device_attachment) {
         gpu::AppendDevice(&cntl.request_attachment(), _device_attachment, _attachment.size(), _opt.gpu_device);
+    }
+    if (_device_attachment || _build_body_dev) {
         if (_opt.device_compress) cntl.set_device_payload_compress_type((CompressType)_opt.device_compress);
         if (_opt.device_scan) cntl.set_device_payload_scan(true);
         if (_opt.verify_device_payload) cntl.set_verify_device_payload(true);
@@ -414,6 +471,10 @@ void PressSession::finish(PressCall* call) {
     if (FLAGS_press_slow_trace_us > 0 && lat >= FLAGS_press_slow_trace_us) RecordSlowCall(call->t0, lat);
     Controller& cntl = call->cntl;
     bool ok = !cntl.Failed();
+    if (ok && call->build_rc != 0) {
+        ok = false;
+        cntl.SetFailed(ERESPONSE, "building the attachment on the device failed (code %d)", call->build_rc);
+    }
     if (ok && call->check && !_method) {
         if (call->echo_res.message() != _echo_message) {
             ok = false;
@@ -432,6 +493,13 @@ void PressSession::finish(PressCall* call) {
             if (gpu::CopyBufToHost(cntl.response_attachment(), &got) != 0 || got != want) {
                 ok = false;
                 cntl.SetFailed(ERESPONSE, "echoed attachment mismatch (%zu bytes)", got.size());
+            } else if (_build_body_dev && _opt.device_scan && _fanout == 1 &&
+                       !cntl.response_attachment().all_host_accessible()) {
+                const std::string wrong = check_built_reply(cntl);
+                if (!wrong.empty()) {
+                    ok = false;
+                    cntl.SetFailed(ERESPONSE, "%s", wrong.c_str());
+                }
             } else if (_device_attachment && _opt.device_scan && _fanout == 1 &&
                        !cntl.response_attachment().all_host_accessible() &&
                        (ix.nfields != 1 || ix.fields.size() < 2 || ix.fields[0] != ((1u << 3) | 2) ||
@@ -448,6 +516,42 @@ void PressSession::finish(PressCall* call) {
         }
     }
     call->w->add(lat, ok, cntl.ErrorCode(), ok ? std::string() : cntl.ErrorText(), call->nbytes);
+}
+
+// A device reply to a device-built attachment: the field table the receiver
+// made on the device must locate the packed ids (field 8), and decoding them
+// there must give the ids the message was built from.
+std::string PressSession::check_built_reply(const Controller& cntl) const {
+    const DevicePayloadIndex& ix = cntl.device_payload_index();
+    uint64_t off = 0, len = 0, boff = 0, blen = 0;
+    if (ix.nfields != 2 || !gpu::DevicePayloadField(ix, 8, &off, &len) ||
+        !gpu::DevicePayloadField(ix, 1, &boff, &blen) || blen != _build_body_len || off + len != _attachment.size()) {
+        return "wrong table: device pb index of the echoed built message (nfields " + std::to_string(ix.nfields) + ")";
+    }
+    Buf flat;
+    if (gpu::GatherToDevice(cntl.response_attachment(), &flat, _opt.gpu_device) != 0 || flat.backing_block_num() != 1) {
+        return "wrong ids: the echoed built message could not be gathered in HBM";
+    }
+    const BlockRef& r = flat.ref_at(0);
+    const size_t room = std::max<size_t>(len, _build_ids.size()) * sizeof(int64_t);
+    void* arr = gpu::HbmAlloc(room, _opt.gpu_device);
+    if (!arr) return "wrong ids: no HBM for the decoded ids";
+    gpu::DevicePackedRun run;
+    run.src = r.block->data + r.offset + off;
+    run.len = len;
+    run.kind = gpu::PB_RUN_INT64;
+    run.dst = arr;
+    std::vector<int64_t> got(_build_ids.size());
+    std::string wrong;
+    if (gpu::DeviceDecodePackedRuns(&run, 1, _opt.gpu_device) != 0 || run.err != 0 || run.count != _build_ids.size()) {
+        wrong = "wrong ids: field 8 of the echoed built message decodes to " + std::to_string(run.count) +
+                " ids (code " + std::to_string(run.err) + ")";
+    } else if (gpu::CopyDeviceToHost(got.data(), arr, got.size() * sizeof(int64_t), _opt.gpu_device) != 0 ||
+               got != _build_ids) {
+        wrong = "wrong ids: field 8 of the echoed built message does not decode to the ids it was built from";
+    }
+    gpu::HbmFree(arr, room, _opt.gpu_device);
+    return wrong;
 }
 
 void PressCall::Run() {

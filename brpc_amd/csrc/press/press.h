@@ -27,6 +27,7 @@
 namespace mrpc {
 
 class ChannelBase;
+class Controller;
 namespace pb {
 class Message;
 class MethodDescriptor;
@@ -69,6 +70,14 @@ struct PressOptions {
     // device attachments: the receiver pb_scan-indexes the payload (the
     // server mirrors it; check_echo verifies the reply's field table)
     bool device_scan = false;
+    // device attachments (needs device_attachment): the press keeps this many
+    // int64 ids and the attachment body in HBM and BUILDS the attachment on
+    // the device for every call (gpu::BuildDeviceMessage): one EchoRequest
+    // whose message (field 1) is the body and whose ids (field 8) are the
+    // packed ids. check_echo compares the echo with the host serializer's
+    // bytes of the same message and, for a device reply with device_scan,
+    // decodes field 8 on the device and compares the ids
+    int device_build_ids = 0;
     // device attachments: CRC32C-verified on the device by the receiver
     bool verify_device_payload = false;
     int gpu_device = -1;
@@ -159,6 +168,14 @@ private:
     std::vector<int64_t> _ids;  // EchoRequest.ids of every call
     Buf _attachment_buf;                 // _attachment as one shared block
     void* _device_attachment = nullptr;  // HBM copy of _attachment when device_attachment
+    // device_build_ids: the parts every call's attachment is built from (HBM),
+    // _attachment being the host serialization of the same message
+    std::vector<int64_t> _build_ids;
+    void* _build_body_dev = nullptr;
+    void* _build_ids_dev = nullptr;
+    size_t _build_body_len = 0;
+    // "" when field 8 of a device reply decodes to _build_ids, else what is wrong
+    std::string check_built_reply(const Controller& cntl) const;
 
     mutable std::mutex _mu;
     var::LatencyHistogram _hist;

@@ -72,6 +72,19 @@ struct DevBuf {
     T* as() const { return static_cast<T*>(p); }
 };
 
+// (number, kind, device pointer, count) rows of device_build_message
+typedef std::tuple<uint32_t, uint32_t, uintptr_t, uint64_t> MessageFieldRow;
+std::vector<gpu::DeviceMessageField> message_fields(const std::vector<MessageFieldRow>& rows) {
+    std::vector<gpu::DeviceMessageField> fs(rows.size());
+    for (size_t i = 0; i < rows.size(); ++i) {
+        fs[i].number = std::get<0>(rows[i]);
+        fs[i].kind = std::get<1>(rows[i]);
+        fs[i].src = (const void*)std::get<2>(rows[i]);
+        fs[i].count = std::get<3>(rows[i]);
+    }
+    return fs;
+}
+
 }  // namespace
 
 void bind_gpu_ops(py::module_& g) {
@@ -221,6 +234,70 @@ void bind_gpu_ops(py::module_& g) {
         for (const gpu::DevicePackedRun& r : runs) out.append(py::make_tuple(r.count, r.err));
         return out;
     }, py::arg("srcs"), py::arg("lens"), py::arg("kinds"), py::arg("dsts"), py::arg("device") = 0);
+    // The encode side: device arrays -> one serialized message at dst (cap
+    // bytes of device memory). fields = [(number, kind, ptr, count)], kind a
+    // PbRunKind or 7 (raw bytes). -> (len, err, [(off, len) per field]); err 0
+    // built, 2 refused before any launch, 3 longer than cap (dst untouched).
+    g.def("device_build_message", [](const std::vector<MessageFieldRow>& fields, uintptr_t dst, uint64_t cap,
+                                     int device) {
+        std::vector<gpu::DeviceMessageField> fs = message_fields(fields);
+        gpu::DeviceMessageJob job;
+        job.fields = fs.data();
+        job.nfields = (int)fs.size();
+        job.dst = (void*)dst;
+        job.cap = cap;
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceBuildMessages(&job, 1, device);
+        }
+        check(rc, "device_build_message");
+        py::list pos;
+        for (const gpu::DeviceMessageField& f : fs) pos.append(py::make_tuple(f.off, f.len));
+        return py::make_tuple(job.len, job.err, pos);
+    }, py::arg("fields"), py::arg("dst"), py::arg("cap"), py::arg("device") = 0);
+    g.def("device_message_worst_case", [](const std::vector<MessageFieldRow>& fields) {
+        std::vector<gpu::DeviceMessageField> fs = message_fields(fields);
+        return gpu::DeviceMessageWorstCaseBytes(fs.data(), (int)fs.size());
+    });
+    // Bare packed runs (no tag, no length), the mirror of device_decode_packed:
+    // [(bytes, err)] per array.
+    g.def("device_encode_packed", [](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& counts,
+                                     const std::vector<uint32_t>& kinds, const std::vector<uintptr_t>& dsts,
+                                     const std::vector<uint64_t>& caps, int device) {
+        if (srcs.size() != counts.size() || kinds.size() != counts.size() || dsts.size() != counts.size() ||
+            caps.size() != counts.size())
+            throw std::invalid_argument("size mismatch");
+        std::vector<gpu::DevicePackedEncodeRun> runs(counts.size());
+        for (size_t i = 0; i < counts.size(); ++i) {
+            runs[i].src = (const void*)srcs[i];
+            runs[i].count = counts[i];
+            runs[i].kind = kinds[i];
+            runs[i].dst = (void*)dsts[i];
+            runs[i].cap = caps[i];
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceEncodePackedRuns(runs.data(), (int)runs.size(), device);
+        }
+        check(rc, "device_encode_packed");
+        py::list out;
+        for (const gpu::DevicePackedEncodeRun& r : runs) out.append(py::make_tuple(r.bytes, r.err));
+        return out;
+    }, py::arg("srcs"), py::arg("counts"), py::arg("kinds"), py::arg("dsts"), py::arg("caps"), py::arg("device") = 0);
+    // Field table of a message already in device memory -> (nfields, fields)
+    g.def("device_pb_scan", [](uintptr_t buf, uint64_t len, int device) {
+        const void* p = (const void*)buf;
+        DevicePayloadIndex idx;
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DevicePbScan(&p, &len, 1, &idx, device);
+        }
+        check(rc, "device_pb_scan");
+        return py::make_tuple(idx.nfields, idx.fields);
+    }, py::arg("buf"), py::arg("len"), py::arg("device") = 0);
     g.def("device_payload_field", [](int nfields, const std::vector<uint64_t>& fields, uint32_t number) -> py::object {
         DevicePayloadIndex idx;
         idx.nfields = nfields;

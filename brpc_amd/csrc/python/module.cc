@@ -159,6 +159,7 @@ press::PressOptions press_options(const py::dict& d) {
         else if (k == "attachment_pb") o.attachment_pb = v.cast<bool>();
         else if (k == "device_compress") o.device_compress = v.cast<int>();
         else if (k == "device_scan") o.device_scan = v.cast<bool>();
+        else if (k == "device_build_ids") o.device_build_ids = v.cast<int>();
         else if (k == "verify_device_payload") o.verify_device_payload = v.cast<bool>();
         else if (k == "gpu_device") o.gpu_device = v.cast<int>();
         else if (k == "check_echo") o.check_echo = v.cast<bool>();
@@ -725,6 +726,10 @@ PYBIND11_MODULE(_native, m) {
         d["packed_bytes"] = s.packed_bytes;
         d["packed_elems"] = s.packed_elems;
         d["packed_errors"] = s.packed_errors;
+        d["built_messages"] = s.built_messages;
+        d["built_fields"] = s.built_fields;
+        d["built_bytes"] = s.built_bytes;
+        d["build_errors"] = s.build_errors;
         return d;
     });
     g.def("codec_batch_stats", [] {
@@ -735,6 +740,7 @@ PYBIND11_MODULE(_native, m) {
         d["run_chunks"] = s.run_chunks;
         d["decode_chunks"] = s.decode_chunks;
         d["fused_launches"] = s.fused_launches;
+        d["msg_chunks"] = s.msg_chunks;
         d["timed"] = s.timed;
         d["queue_us"] = s.queue_us;
         d["api_us"] = s.api_us;

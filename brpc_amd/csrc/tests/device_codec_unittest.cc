@@ -228,8 +228,9 @@ TEST(DeviceCodec, pooled_request_reset_matches_a_fresh_one) {
     EXPECT_EQ(r.stream_piece_limit, fresh.stream_piece_limit);
     EXPECT_EQ(r.pieces_max_ulen, fresh.pieces_max_ulen);
     EXPECT_EQ(r.pieces.capacity(), cap);  // capacity kept: no allocation on the next use
-    // 22 lists and 4 limits (x86-64 layout, with the padding after the two
-    // lone limits): a member added later changes the size, and this test
-    // (and Reset()) must learn about it
-    EXPECT_EQ(sizeof(gpu::CodecRequest), 22 * sizeof(std::vector<int>) + 4 * sizeof(uint32_t) + 8);
+    // 27 lists (the 5 of the message builder are checked in
+    // device_message_unittest.cc) and 4 limits (x86-64 layout, with the
+    // padding after the two lone limits): a member added later changes the
+    // size, and this test (and Reset()) must learn about it
+    EXPECT_EQ(sizeof(gpu::CodecRequest), 27 * sizeof(std::vector<int>) + 4 * sizeof(uint32_t) + 8);
 }

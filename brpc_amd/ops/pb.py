@@ -38,6 +38,70 @@ def pb_scan(buf, offsets, max_fields=16):
     return fields[:n], nfields[:n]
 
 
+# kind_name -> (PbRunKind / kDeviceFieldBytes, tensor dtypes whose memory is the kind's vector layout)
+_KINDS = {
+    "int32": (0, (torch.int32,)),
+    "uint32": (1, (torch.int32, getattr(torch, "uint32", torch.int32))),
+    "sint32": (2, (torch.int32,)),
+    "int64": (3, (torch.int64,)),
+    "uint64": (4, (torch.int64, getattr(torch, "uint64", torch.int64))),
+    "sint64": (5, (torch.int64,)),
+    "bool": (6, (torch.bool, torch.uint8)),
+    "bytes": (7, None),
+}
+BUILD_ERRORS = {2: "refused (field number, kind, alignment or size)", 3: "longer than the destination",
+                4: "a source tensor changed while the message was built"}
+
+
+def pb_build_message(fields):
+    """Serialize device tensors into one protobuf message in device memory
+    (``gpu::DeviceBuildMessages``): the values never leave HBM, the host
+    learns only lengths.
+
+    fields: [(number, tensor, kind_name)] in wire order, kind_name one of
+    int32, uint32, sint32, int64, uint64, sint64, bool (a packed repeated
+    field of the tensor's elements; the unsigned kinds take the signed tensor
+    of the same width, its bits read as unsigned) or bytes (a length-delimited
+    field holding the tensor's memory image: bytes / string, and packed
+    float / double / fixed32 / fixed64). An empty packed field is omitted, as
+    the host serializer does; an empty bytes field is emitted.
+
+    Returns (message, positions): a uint8 device tensor trimmed to the
+    message's length, and [(offset, length)] of every field's payload in it.
+
+    The codec batch runs on its own stream, not on torch's: the caller's
+    current stream is synchronized before the call, so tensors produced by
+    kernels queued just before are complete when the builder reads them, and
+    the message is complete when this returns."""
+    if not fields:
+        raise ValueError("no fields")
+    dev = fields[0][1].device
+    rows, keep = [], []
+    for number, t, kind_name in fields:
+        if kind_name not in _KINDS:
+            raise ValueError("unknown kind %r (one of %s)" % (kind_name, ", ".join(_KINDS)))
+        kind, dtypes = _KINDS[kind_name]
+        require_gpu_tensor(t, "field %d" % number)
+        if t.device != dev:
+            raise ValueError("all fields must live on one device (%s vs %s)" % (t.device, dev))
+        if dtypes is not None and t.dtype not in dtypes:
+            raise TypeError("field %d: kind %s takes a tensor of %s, not %s" % (number, kind_name, dtypes[0], t.dtype))
+        t = t.contiguous()
+        keep.append(t)
+        count = t.numel() * t.element_size() if kind == 7 else t.numel()
+        rows.append((int(number), kind, t.data_ptr() if count else 0, count))
+    cap = native.gpu.device_message_worst_case(rows)
+    if cap == 0 and any(r[3] or r[1] == 7 for r in rows):
+        raise ValueError("fields refused: " + BUILD_ERRORS[2])
+    out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        n, err, pos = native.gpu.device_build_message(rows, out.data_ptr(), cap, dev.index or 0)
+    if err:
+        raise ValueError("pb_build_message: " + BUILD_ERRORS.get(err, "code %d" % err))
+    return out[:n], [tuple(p) for p in pos]
+
+
 def pb_scan_host(msg, max_fields=16):
     """Pure-python reference of one message's scan (tests)."""
     out, p = [], 0
