@@ -31,6 +31,7 @@
 
 #include <cstdint>
 
+#include "base/shortest_double.h"
 #include "gpu/kernels.h"
 
 namespace mrpc {
@@ -459,7 +460,140 @@ __global__ void __launch_bounds__(256) json_int_array_kernel(const char* __restr
     out[i] = neg ? (int64_t)((uint64_t)0 - v) : (int64_t)v;
 }
 
+// pb2json float / double arrays (kernels.h: size, prefix, place). The
+// reference prints them element by element on the host through rapidjson's
+// Writer (src/json2pb/pb_to_json.cpp); here one lane formats one element
+// with base/shortest_double.h, the same code the host printer runs.
+namespace sd = ::mrpc::shortest_double;
+typedef uint32_t jf_u32x4 __attribute__((ext_vector_type(4)));
+constexpr int kJfThreads = (int)kJsonFloatChunkElems;  // a lane per element
+constexpr int kJfWaves = kJfThreads / 64;
+constexpr uint32_t kJfElemMax = (uint32_t)sd::kMaxJsonDoubleChars + 1;                // with its comma
+constexpr int kJfImage16 = (int)(kJsonFloatChunkElems * kJfElemMax + 16 + 15) / 16;  // at any 16-byte phase
+
+__device__ __forceinline__ uint32_t jf_count(const JsonFloatChunk& c) {
+    return c.count < kJsonFloatChunkElems ? c.count : kJsonFloatChunkElems;
+}
+
+__device__ __forceinline__ uint64_t jf_load_bits(const JsonFloatChunk& c, uint32_t i) {
+    if (c.kind == JSON_FLOAT32) return sd::WidenFloatBits(static_cast<const uint32_t*>(c.src)[i]);
+    return static_cast<const uint64_t*>(c.src)[i];
+}
+
+// the element's text size, its comma included (none after an array's last)
+__device__ __forceinline__ uint32_t jf_elem_len(const sd::Decimal& d, const JsonFloatChunk& c, uint32_t i,
+                                                uint32_t count) {
+    return (uint32_t)sd::JsonDecimalLength(d) + (c.last && i + 1 == count ? 0u : 1u);
+}
+
+__global__ void __launch_bounds__(kJfThreads) json_float_size_kernel(const JsonFloatChunk* __restrict__ chunks,
+                                                                     int nchunks, uint32_t* __restrict__ sizes,
+                                                                     sd::Decimal* __restrict__ digits) {
+    __shared__ uint32_t wave_tot[kJfWaves];
+    const uint32_t ci = blockIdx.x, t = threadIdx.x;
+    const JsonFloatChunk c = chunks[ci];
+    const uint32_t count = jf_count(c);
+    if (ci == 0 && t == 0) sizes[nchunks] = 0;  // becomes the total under the scan
+    uint32_t n = 0;
+    if (t < count) {
+        const sd::Decimal d = sd::ShortestDigits(jf_load_bits(c, t));
+        n = jf_elem_len(d, c, t, count);
+        digits[(uint64_t)ci * kJsonFloatChunkElems + t] = d;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+    if ((t & 63) == 0) wave_tot[t >> 6] = n;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t total = 0;
+#pragma unroll
+        for (int w = 0; w < kJfWaves; ++w) total += wave_tot[w];
+        sizes[ci] = total;
+    }
+}
+
+__global__ void __launch_bounds__(kJfThreads) json_float_place_kernel(const JsonFloatJob* __restrict__ jobs,
+                                                                      const JsonFloatChunk* __restrict__ chunks,
+                                                                      const uint32_t* __restrict__ prefix,
+                                                                      const sd::Decimal* __restrict__ digits,
+                                                                      JsonFloatResult* __restrict__ res) {
+    __shared__ jf_u32x4 image16[kJfImage16];
+    __shared__ uint32_t wave_tot[kJfWaves];
+    uint8_t* image = reinterpret_cast<uint8_t*>(image16);
+    const uint32_t ci = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const JsonFloatChunk c = chunks[ci];
+    const JsonFloatJob job = jobs[c.job];
+    // the host refuses arrays whose worst case passes 2^32 - 1, so the
+    // differences of the scan (mod 2^32) are the sizes themselves
+    const uint32_t first = prefix[job.first_chunk];
+    const uint32_t job_len = prefix[job.first_chunk + job.nchunks] - first;
+    const bool fits = (uint64_t)job_len <= job.cap;
+    if (ci == job.first_chunk && t == 0) {
+        res[c.job].len = job_len;
+        if (!fits) res[c.job].err = 3;
+    }
+    if (!fits) return;  // the whole workgroup leaves: nothing of this array is written
+    const uint32_t want = prefix[ci + 1] - prefix[ci];
+    uint8_t* dst = job.dst + (uint32_t)(prefix[ci] - first);
+    const uint32_t sh = (uint32_t)((uintptr_t)dst & 15);
+    const uint32_t count = jf_count(c);
+    sd::Decimal d;
+    uint32_t len = 0;
+    if (t < count) {
+        d = digits[(uint64_t)ci * kJsonFloatChunkElems + t];
+        len = jf_elem_len(d, c, t, count);
+        if (len > kJfElemMax) len = 0;  // whatever the slot holds, never past the image
+    }
+    uint32_t incl = len;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(incl, off, 64);
+        if (lane >= (uint32_t)off) incl += y;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    uint32_t pos = incl - len, total = 0;
+#pragma unroll
+    for (int w = 0; w < kJfWaves; ++w) {
+        const uint32_t x = wave_tot[w];
+        if ((uint32_t)w < wave) pos += x;
+        total += x;
+    }
+    if (len) {
+        char* o = reinterpret_cast<char*>(image + sh + pos);
+        const uint32_t body = (uint32_t)sd::FormatJsonDecimal(d, o);
+        if (body < len) o[body] = ',';
+    }
+    __syncthreads();
+    if (total != want) {  // not what the size pass measured, and every later offset assumed `want`
+        if (t == 0) res[c.job].err = 4;
+        return;
+    }
+    // image[sh, sh + total) -> dst, dst = sh (mod 16): 16-byte LDS reads and
+    // 16-byte stores around an unaligned head and tail
+    uint32_t head = (16 - sh) & 15;
+    if (head > total) head = total;
+    if (t < head) dst[t] = image[sh + t];
+    const uint32_t nv = (total - head) / 16;
+    const jf_u32x4* from = reinterpret_cast<const jf_u32x4*>(image + sh + head);
+    jf_u32x4* body16 = reinterpret_cast<jf_u32x4*>(dst + head);
+    for (uint32_t w = t; w < nv; w += kJfThreads) body16[w] = from[w];
+    for (uint32_t j = head + 16 * nv + t; j < total; j += kJfThreads) dst[j] = image[sh + j];
+}
+
 }  // namespace
+
+int LaunchJsonFloatPrint(const JsonFloatTables& t, hipStream_t s) {
+    if (t.njobs <= 0 || t.nchunks <= 0) return 0;
+    if (!t.jobs || !t.chunks || !t.prefix || !t.digits || !t.res) return -1;
+    hipLaunchKernelGGL(json_float_size_kernel, dim3((unsigned)t.nchunks), dim3(kJfThreads), 0, s, t.chunks, t.nchunks,
+                       t.prefix, static_cast<sd::Decimal*>(t.digits));
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (LaunchPbRunPrefix(t.prefix, t.nchunks + 1, s) != 0) return -1;
+    hipLaunchKernelGGL(json_float_place_kernel, dim3((unsigned)t.nchunks), dim3(kJfThreads), 0, s, t.jobs, t.chunks,
+                       t.prefix, static_cast<const sd::Decimal*>(t.digits), t.res);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 int LaunchJsonIntArray(const char* text, const uint32_t* seps, uint32_t n, int64_t* out, int32_t* bad,
                        hipStream_t s) {

@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "base/flags.h"
+#include "base/shortest_double.h"
 #include "base/time.h"
 #include "gpu/gpu.h"
 #include "gpu/hbm_pool.h"
@@ -28,6 +29,12 @@ DEFINE_int32(gpu_pb2json_min_elems, 4096,
              "repeated integer/bool fields with at least this many elements are printed by the device in pb2json "
              "(pb_run_encode_kernel, decimal format) and integer arrays of at least as many elements are parsed by "
              "json_int_array_kernel in json2pb, while the GPU JSON path is enabled");
+DEFINE_int32(gpu_pb2json_float_min_elems, 4096,
+             "repeated float / double fields with at least this many elements are printed by the device in pb2json "
+             "(json_float_size_kernel / json_float_place_kernel) while the GPU JSON path is enabled; shorter ones by "
+             "the host printer (4096: the smallest size measured, where the device already wins, "
+             "profiles/json_float_print.txt). 0: never. Reloadable");
+MRPC_VALIDATE_FLAG(gpu_pb2json_float_min_elems, ::mrpc::PassValidator);
 DEFINE_int32(json_index_min_density, 8,
              "structural characters per KiB (sampled in three windows) a JSON body needs before the GPU index is "
              "used; sparser bodies (long strings) parse faster on the host; 0: always offload");
@@ -171,9 +178,116 @@ int JsonIndex(const char* data, size_t n, std::vector<uint32_t>* out, int device
     return rc == 0 ? 0 : -1;
 }
 
+uint64_t FloatPrintWorstCaseBytes(uint64_t count) {
+    return count ? count * (uint64_t)(shortest_double::kMaxJsonDoubleChars + 1) - 1 : 0;
+}
+
+int DevicePrintFloatArrays(DeviceFloatPrintJob* jobs, int n, int device) {
+    if (n <= 0) return 0;
+    if (!jobs || device < 0) return -1;
+    // refuse what must not reach a kernel; count the chunks of the rest
+    uint64_t nchunks = 0;
+    int live = 0;
+    for (int i = 0; i < n; ++i) {
+        DeviceFloatPrintJob& j = jobs[i];
+        j.len = 0;
+        j.err = 0;
+        if (j.count == 0) continue;
+        const size_t eb = j.kind == kJsonFloat32 ? 4 : 8;
+        if ((j.kind != kJsonFloat32 && j.kind != kJsonFloat64) || !j.src || !j.dst ||
+            ((uintptr_t)j.src & (eb - 1)) != 0 || j.count > 0xFFFFFFFFull / (shortest_double::kMaxJsonDoubleChars + 1)) {
+            j.err = 2;
+            continue;
+        }
+        nchunks += (j.count + kJsonFloatChunkElems - 1) / kJsonFloatChunkElems;
+        ++live;
+    }
+    if (live == 0) return 0;
+    if (nchunks > 0x3FFFFFFFull) return -1;  // the tables are indexed with int
+    const size_t jobs_bytes = (size_t)live * sizeof(JsonFloatJob);
+    const size_t chunks_bytes = (size_t)nchunks * sizeof(JsonFloatChunk);
+    const size_t res_bytes = (size_t)live * sizeof(JsonFloatResult);
+    Pinned tables(jobs_bytes + chunks_bytes + res_bytes);
+    Hbm prefix((size_t)(nchunks + 1) * sizeof(uint32_t), device);
+    Hbm digits((size_t)nchunks * kJsonFloatChunkElems * sizeof(shortest_double::Decimal), device);
+    if (!tables.p || !prefix.p || !digits.p) return -1;
+    JsonFloatJob* tj = static_cast<JsonFloatJob*>(tables.p);
+    JsonFloatChunk* tc = reinterpret_cast<JsonFloatChunk*>(static_cast<char*>(tables.p) + jobs_bytes);
+    JsonFloatResult* tr = reinterpret_cast<JsonFloatResult*>(static_cast<char*>(tables.p) + jobs_bytes + chunks_bytes);
+    uint32_t ci = 0;
+    int k = 0;
+    for (int i = 0; i < n; ++i) {
+        const DeviceFloatPrintJob& j = jobs[i];
+        if (j.count == 0 || j.err != 0) continue;
+        const size_t eb = j.kind == kJsonFloat32 ? 4 : 8;
+        const uint32_t nc = (uint32_t)((j.count + kJsonFloatChunkElems - 1) / kJsonFloatChunkElems);
+        tj[k] = JsonFloatJob{static_cast<uint8_t*>(j.dst), j.cap, ci, nc};
+        tr[k] = JsonFloatResult{0, 0, 0};
+        for (uint32_t c = 0; c < nc; ++c) {
+            const uint64_t at = (uint64_t)c * kJsonFloatChunkElems;
+            const uint64_t left = j.count - at;
+            tc[ci + c] = JsonFloatChunk{static_cast<const char*>(j.src) + at * eb,
+                                        (uint32_t)std::min<uint64_t>(left, kJsonFloatChunkElems), j.kind, (uint32_t)k,
+                                        c + 1 == nc ? 1u : 0u};
+        }
+        ci += nc;
+        ++k;
+    }
+    JsonFloatTables t;
+    t.jobs = tj;
+    t.njobs = live;
+    t.chunks = tc;
+    t.nchunks = (int)nchunks;
+    t.prefix = static_cast<uint32_t*>(prefix.p);
+    t.digits = digits.p;
+    t.res = tr;
+    int prev = 0;
+    hipGetDevice(&prev);
+    if (prev != device) hipSetDevice(device);
+    hipStream_t s = PoolStream(device);
+    const int rc = s ? LaunchJsonFloatPrint(t, s) : -1;
+    const int wrc = s ? SyncStream(s) : -1;  // never free buffers a launched kernel may still use
+    if (prev != device) hipSetDevice(prev);
+    if (rc != 0 || wrc != 0) return -1;
+    k = 0;
+    for (int i = 0; i < n; ++i) {
+        DeviceFloatPrintJob& j = jobs[i];
+        if (j.count == 0 || j.err != 0) continue;
+        j.len = tr[k].len;
+        j.err = tr[k].err;
+        ++k;
+    }
+    return 0;
+}
+
+int PrintFloatsOnDevice(const void* values, size_t n, uint32_t kind, std::string* out, int device) {
+    if (!out || device < 0 || (kind != kJsonFloat32 && kind != kJsonFloat64)) return -1;
+    if (n == 0) {
+        out->clear();
+        return 0;
+    }
+    if (!values) return -1;
+    const size_t eb = kind == kJsonFloat32 ? 4 : 8;
+    const uint64_t cap = FloatPrintWorstCaseBytes(n);
+    if (cap > 0xFFFFFFFFull) return -1;
+    Pinned stage(n * eb), text((size_t)cap);
+    if (!stage.p || !text.p) return -1;
+    memcpy(stage.p, values, n * eb);
+    DeviceFloatPrintJob job;
+    job.src = stage.p;
+    job.count = n;
+    job.kind = kind;
+    job.dst = text.p;
+    job.cap = cap;
+    if (DevicePrintFloatArrays(&job, 1, device) != 0 || job.err != 0 || job.len > cap) return -1;
+    out->assign(static_cast<const char*>(text.p), (size_t)job.len);
+    return 0;
+}
+
 namespace {
 
 std::atomic<int64_t> g_arrays{0}, g_array_elems{0}, g_array_failures{0};
+std::atomic<int64_t> g_float_arrays{0}, g_float_elems{0};
 
 // pb2json number arrays: pb_run_encode_kernel prints the
 // field's values in the codec batch (gpu/snappy_offload.h
@@ -181,6 +295,17 @@ std::atomic<int64_t> g_arrays{0}, g_array_elems{0}, g_array_failures{0};
 bool array_offload(const void* values, size_t n, uint32_t kind, std::string* text) {
     const int dev = g_device;
     if (dev < 0) return false;
+    if (kind == kJsonFloat32 || kind == kJsonFloat64) {
+        const int min_elems = FLAGS_gpu_pb2json_float_min_elems;
+        if (min_elems <= 0 || n < (size_t)min_elems) return false;  // the host printer takes it
+        if (PrintFloatsOnDevice(values, n, kind, text, dev) != 0) {
+            g_array_failures.fetch_add(1, std::memory_order_relaxed);
+            return false;
+        }
+        g_float_arrays.fetch_add(1, std::memory_order_relaxed);
+        g_float_elems.fetch_add((int64_t)n, std::memory_order_relaxed);
+        return true;
+    }
     if (EncodeRunOnDevice(values, n, kind, PB_RUN_DECIMAL, text, dev) != 0) {
         g_array_failures.fetch_add(1, std::memory_order_relaxed);
         return false;
@@ -245,6 +370,8 @@ int EnableGpuJsonIndex(int device, size_t min_bytes, std::string* error) {
     json::SetIntArrayOffload(int_array_offload, (size_t)std::max(1, FLAGS_gpu_pb2json_min_elems));
     static var::PassiveStatus<int64_t> v5("gpu_json_int_arrays", [] { return g_int_arrays.load(); });
     static var::PassiveStatus<int64_t> v4("gpu_pb2json_arrays", [] { return g_arrays.load(); });
+    static var::PassiveStatus<int64_t> v6("gpu_pb2json_float_arrays", [] { return g_float_arrays.load(); });
+    static var::PassiveStatus<int64_t> v7("gpu_pb2json_float_elems", [] { return g_float_elems.load(); });
     static var::PassiveStatus<int64_t> v1("gpu_json_indexed_bodies", [] { return g_bodies.load(); });
     static var::PassiveStatus<int64_t> v2("gpu_json_indexed_bytes", [] { return g_bytes.load(); });
     static var::PassiveStatus<int64_t> v3("gpu_json_index_failures", [] { return g_failures.load(); });
@@ -265,6 +392,8 @@ GpuJsonStats GetGpuJsonStats() {
     s.pb2json_arrays = g_arrays.load();
     s.pb2json_elems = g_array_elems.load();
     s.pb2json_failures = g_array_failures.load();
+    s.pb2json_float_arrays = g_float_arrays.load();
+    s.pb2json_float_elems = g_float_elems.load();
     s.int_arrays = g_int_arrays.load();
     s.int_array_fallbacks = g_int_array_fallbacks.load();
     s.sparse_skips = g_sparse.load();

@@ -324,6 +324,59 @@ struct PbMsgTables {
     PbMsgFieldResult* fres = nullptr;    // nfields
 };
 int LaunchPbMsgEncode(const PbMsgTables& t, hipStream_t s);
+// The one-workgroup exclusive prefix sum (mod 2^32) those passes use, over
+// prefix[0, n) in place (device memory), for other kernels' size tables.
+int LaunchPbRunPrefix(uint32_t* prefix, int n, hipStream_t s);
+
+// JSON float / double arrays (gpu/json_kernels.hip): arrays in device (or
+// pinned host) memory become "v,v,...,v" in device memory, every element
+// exactly as json::Value prints a double (base/shortest_double.h; a float is
+// widened first; "NaN" / "Infinity" / "-Infinity" quoted). An element's size
+// is known only once it is formatted, so the host sizes nothing. An array is
+// cut into chunks of <= kJsonFloatChunkElems elements, one lane per element;
+// three launches on one stream, ordered by the launches alone:
+//   size   a workgroup per chunk finds each element's digits, keeps them as a
+//          16-byte Decimal in digits[chunk * 256 + lane] and writes the
+//          chunk's text size into prefix[chunk] (prefix: device memory,
+//          nchunks + 1 entries; the last gets 0)
+//   prefix LaunchPbRunPrefix scans the sizes
+//   place  a workgroup per chunk: an array longer than its cap is marked
+//          (err 3) and gets nothing written; else the chunk's text is laid
+//          out in LDS from `digits` and leaves with 16-byte stores at
+//          dst + (prefix[chunk] - prefix[first]). A chunk whose text is not
+//          the size the size pass measured writes nothing and marks err 4.
+// Keeping the digits beat formatting the source a second time in the place
+// pass at every size measured (profiles/json_float_print.txt), and a pinned
+// host source is read once.
+constexpr uint32_t kJsonFloatChunkElems = 256;
+constexpr uint32_t JSON_FLOAT32 = 8, JSON_FLOAT64 = 9;  // json2pb::kArrayKindFloat / kArrayKindDouble
+struct JsonFloatJob {
+    uint8_t* dst;  // device-writable, never null
+    uint64_t cap;
+    uint32_t first_chunk, nchunks;  // nchunks >= 1
+};
+struct JsonFloatChunk {
+    const void* src;  // this chunk's first element (device-readable, naturally aligned)
+    uint32_t count;   // 1..kJsonFloatChunkElems
+    uint32_t kind;    // JSON_FLOAT32 or JSON_FLOAT64
+    uint32_t job;
+    uint32_t last;    // 1: the array's last chunk (no comma after its last element)
+};
+struct JsonFloatResult {
+    uint64_t len;  // text size (also when it did not fit)
+    int32_t err;   // zero before the launch; 3 or 4 afterwards when the array failed
+    int32_t pad;
+};
+struct JsonFloatTables {
+    const JsonFloatJob* jobs = nullptr;      // device-readable (pinned host)
+    int njobs = 0;
+    const JsonFloatChunk* chunks = nullptr;  // device-readable (pinned host)
+    int nchunks = 0;
+    uint32_t* prefix = nullptr;  // device memory, nchunks + 1 entries
+    void* digits = nullptr;      // device memory, nchunks * kJsonFloatChunkElems * 16 bytes
+    JsonFloatResult* res = nullptr;  // device-writable (pinned host), njobs
+};
+int LaunchJsonFloatPrint(const JsonFloatTables& t, hipStream_t s);
 
 // JSON structural index (gpu/json_kernels.hip): out_pos receives, in order,
 // the byte offsets of every unescaped '"' and of every { } [ ] : , outside

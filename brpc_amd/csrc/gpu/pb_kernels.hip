@@ -791,6 +791,13 @@ int LaunchPbMsgEncode(const PbMsgTables& t, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int LaunchPbRunPrefix(uint32_t* prefix, int n, hipStream_t s) {
+    if (n <= 0) return 0;
+    if (!prefix) return -1;
+    hipLaunchKernelGGL(pb_run_prefix_kernel, dim3(1), dim3(kPrefixThreads), 0, s, prefix, n);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int LaunchPbRunDecode(const PbRunDecodeChunk* chunks, int n, uint32_t* counts, uint32_t* prefix, int32_t* err,
                       hipStream_t s) {
     if (n <= 0) return 0;

@@ -12,7 +12,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
+#include "base/shortest_double.h"
 #include "base/util.h"
 
 namespace mrpc {
@@ -113,6 +115,8 @@ bool array_kind(const FieldDescriptor* f, const Pb2JsonOptions& opt, uint32_t* k
     case CppType::UINT64: *kind = 4; return true;
     case CppType::BOOL: *kind = 6; return true;
     case CppType::ENUM: *kind = 0; return !(opt.enum_option_as_string && f->enum_type);
+    case CppType::FLOAT: *kind = kArrayKindFloat; return true;
+    case CppType::DOUBLE: *kind = kArrayKindDouble; return true;
     default: return false;
     }
 }
@@ -123,20 +127,25 @@ bool array_offload(const Message& m, const FieldDescriptor* f, const Pb2JsonOpti
     if (!fn || opt.pretty_json || !array_kind(f, opt, &kind)) return false;
     size_t n = 0, eb = 0;
     const void* data = Reflection::RepeatedScalarData(m, f, &n, &eb);
-    if (!data || n < g_array_offload_min.load(std::memory_order_relaxed)) return false;
+    // float kinds: the offload has a threshold of its own
+    const bool floats = kind == kArrayKindFloat || kind == kArrayKindDouble;
+    if (!data || (!floats && n < g_array_offload_min.load(std::memory_order_relaxed))) return false;
     return fn(data, n, kind, text);
 }
 
 // The host twin of the device printer: the array's elements as decimal
 // text straight from the field's storage (std::to_chars), one string for
 // the whole array instead of a json::Value per element. Same text as
-// Value-by-Value printing.
+// Value-by-Value printing; floats and doubles through FormatJsonDouble
+// (base/shortest_double.h) instead of AppendShortestDouble's snprintf /
+// strtod rounds.
 bool array_print_host(const Message& m, const FieldDescriptor* f, const Pb2JsonOptions& opt, std::string* text) {
     uint32_t kind;
     if (opt.pretty_json || !array_kind(f, opt, &kind)) return false;
     size_t n = 0, eb = 0;
     const void* data = Reflection::RepeatedScalarData(m, f, &n, &eb);
     if (!data || n == 0) return false;
+    if (kind == kArrayKindFloat || kind == kArrayKindDouble) return FormatFloatArray(data, n, kind, text);
     text->reserve(n * (kind == 3 || kind == 4 ? 12 : 6) + 2);
     char buf[24];
     for (size_t i = 0; i < n; ++i) {
@@ -534,6 +543,34 @@ namespace {
 std::atomic<JsonIndexOffload> g_index_offload{nullptr};
 size_t g_index_min = (size_t)-1;
 }  // namespace
+
+bool FormatFloatArray(const void* values, size_t n, uint32_t kind, std::string* text) {
+    if (kind != kArrayKindFloat && kind != kArrayKindDouble) return false;
+    if (n == 0) return true;
+    if (!values) return false;
+    // written in place: an element is at most kMaxJsonDoubleChars and a comma
+    const size_t start = text->size();
+    size_t used = start;
+    for (size_t i = 0; i < n; ++i) {
+        if (text->size() - used < (size_t)shortest_double::kMaxJsonDoubleChars + 1) {
+            text->resize(used + std::max<size_t>((n - i) * 20, 4096));
+        }
+        char* o = &(*text)[used];
+        if (i) *o++ = ',';
+        uint64_t bits;
+        if (kind == kArrayKindFloat) {
+            uint32_t fb;
+            memcpy(&fb, static_cast<const float*>(values) + i, sizeof(fb));
+            bits = shortest_double::WidenFloatBits(fb);
+        } else {
+            memcpy(&bits, static_cast<const double*>(values) + i, sizeof(bits));
+        }
+        o += shortest_double::FormatJsonDoubleBits(bits, o);
+        used = (size_t)(o - text->data());
+    }
+    text->resize(used);
+    return true;
+}
 
 void SetPb2JsonArrayOffload(Pb2JsonArrayOffload fn, size_t min_elems) {
     g_array_offload_min.store(fn ? std::max<size_t>(1, min_elems) : (size_t)-1, std::memory_order_relaxed);

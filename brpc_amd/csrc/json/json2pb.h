@@ -44,8 +44,19 @@ bool JsonValueToProtoMessage(const json::Value& v, pb::Message* msg, const Json2
 // kind a gpu PbRunKind — as "v,v,...,v" into *text (false: the host prints
 // them). Only for compact output (not pretty_json) and fields of at least
 // min_elems elements; enums printed as names stay on the host.
+// Float and double fields use the kinds below (7 is the device codec's raw
+// bytes); for them min_elems does not apply, the offload has a threshold of
+// its own (-gpu_pb2json_float_min_elems) and declines shorter arrays, which
+// the host then prints with FormatFloatArray.
+constexpr uint32_t kArrayKindFloat = 8;
+constexpr uint32_t kArrayKindDouble = 9;
 typedef bool (*Pb2JsonArrayOffload)(const void* values, size_t n, uint32_t kind, std::string* text);
 void SetPb2JsonArrayOffload(Pb2JsonArrayOffload fn, size_t min_elems);
+// The host twin of the device float printer: n floats (kArrayKindFloat) or
+// doubles (kArrayKindDouble) appended to *text as "v,v,...,v", each exactly
+// as json::Value prints a double ("NaN" / "Infinity" / "-Infinity" quoted).
+// False for another kind.
+bool FormatFloatArray(const void* values, size_t n, uint32_t kind, std::string* text);
 typedef bool (*JsonIndexOffload)(const char* data, size_t n, std::vector<uint32_t>* index);
 void SetJsonIndexOffload(JsonIndexOffload fn, size_t min_bytes);
 

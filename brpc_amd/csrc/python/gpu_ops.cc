@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <cstring>
 #include <vector>
 
 #include "base/time.h"
@@ -15,6 +16,7 @@
 #include "gpu/device_codec.h"
 #include "policy/device_payload.h"
 #include "gpu/gpu.h"
+#include "gpu/json_offload.h"
 #include "gpu/kernels.h"
 
 namespace py = pybind11;
@@ -286,6 +288,54 @@ void bind_gpu_ops(py::module_& g) {
         for (const gpu::DevicePackedEncodeRun& r : runs) out.append(py::make_tuple(r.bytes, r.err));
         return out;
     }, py::arg("srcs"), py::arg("counts"), py::arg("kinds"), py::arg("dsts"), py::arg("caps"), py::arg("device") = 0);
+    // Float (kind 8) / double (kind 9) arrays in device memory -> JSON text
+    // "v,v,...,v" at dst (cap bytes of device memory), all arrays in one
+    // launch sequence: [(len, err)] per array; err 0 printed, 2 refused before
+    // any launch, 3 longer than cap (dst untouched, len = the size needed).
+    g.def("device_json_print_floats", [](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& counts,
+                                         const std::vector<uint32_t>& kinds, const std::vector<uintptr_t>& dsts,
+                                         const std::vector<uint64_t>& caps, int device) {
+        if (srcs.size() != counts.size() || kinds.size() != counts.size() || dsts.size() != counts.size() ||
+            caps.size() != counts.size())
+            throw std::invalid_argument("size mismatch");
+        std::vector<gpu::DeviceFloatPrintJob> jobs(counts.size());
+        for (size_t i = 0; i < counts.size(); ++i) {
+            jobs[i].src = (const void*)srcs[i];
+            jobs[i].count = counts[i];
+            jobs[i].kind = kinds[i];
+            jobs[i].dst = (void*)dsts[i];
+            jobs[i].cap = caps[i];
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DevicePrintFloatArrays(jobs.data(), (int)jobs.size(), device);
+        }
+        check(rc, "device_json_print_floats");
+        py::list out;
+        for (const gpu::DeviceFloatPrintJob& j : jobs) out.append(py::make_tuple(j.len, j.err));
+        return out;
+    }, py::arg("srcs"), py::arg("counts"), py::arg("kinds"), py::arg("dsts"), py::arg("caps"), py::arg("device") = 0);
+    g.def("json_float_worst_case", &gpu::FloatPrintWorstCaseBytes);
+    // Host floats / doubles (their memory image) -> the same text through the
+    // device (gpu::PrintFloatsOnDevice: pinned stage, one wait).
+    g.def("json_print_floats", [](py::bytes values, uint64_t n, uint32_t kind, int device) {
+        const std::string data = values;
+        const size_t eb = kind == gpu::kJsonFloat32 ? 4 : 8;
+        if (kind != gpu::kJsonFloat32 && kind != gpu::kJsonFloat64) throw std::invalid_argument("kind must be 8 or 9");
+        if (data.size() != n * eb) throw std::invalid_argument("values must hold n elements");
+        // a std::string's buffer need not be aligned for doubles
+        std::vector<uint64_t> aligned((data.size() + 7) / 8);
+        memcpy(aligned.data(), data.data(), data.size());
+        std::string text;
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::PrintFloatsOnDevice(aligned.data(), (size_t)n, kind, &text, device);
+        }
+        check(rc, "json_print_floats");
+        return py::bytes(text);
+    }, py::arg("values"), py::arg("n"), py::arg("kind"), py::arg("device") = 0);
     // Field table of a message already in device memory -> (nfields, fields)
     g.def("device_pb_scan", [](uintptr_t buf, uint64_t len, int device) {
         const void* p = (const void*)buf;

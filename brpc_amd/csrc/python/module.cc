@@ -450,7 +450,8 @@ PYBIND11_MODULE(_native, m) {
     // wire bytes -> message -> JSON: ProtoMessageToJson's verdict and error
     // (a missing required field is one) plus the JSON
     m.def("json_proto_from_wire", [](const std::string& proto_dir, const std::string& proto_file,
-                                     const std::string& type_name, py::bytes wire, bool bytes_to_base64) {
+                                     const std::string& type_name, py::bytes wire, bool bytes_to_base64,
+                                     bool pretty) {
         pb::Importer imp({proto_dir});
         std::string err;
         if (!imp.Import(proto_file, &err)) throw std::runtime_error("import " + proto_file + ": " + err);
@@ -462,10 +463,28 @@ PYBIND11_MODULE(_native, m) {
         std::string out;
         json2pb::Pb2JsonOptions po;
         po.bytes_to_base64 = bytes_to_base64;
+        po.pretty_json = pretty;
         const bool ok = json2pb::ProtoMessageToJson(*msg, &out, po, &err);
         return py::make_tuple(ok, err, out);
     }, py::arg("proto_dir"), py::arg("proto_file"), py::arg("type_name"), py::arg("wire"),
-       py::arg("bytes_to_base64") = false);
+       py::arg("bytes_to_base64") = false, py::arg("pretty") = false);
+    // the text json::Value prints for a double (json::AppendShortestDouble;
+    // non-finite values as quoted strings): the oracle of the array printers
+    m.def("json_shortest_double", [](double x) { return py::bytes(json::Value(x).ToString()); });
+    // pb2json's host printer of float (kind 8) / double (kind 9) arrays over
+    // their memory image: b"v,v,...,v" (json2pb::FormatFloatArray)
+    m.def("json_format_floats", [](py::bytes values, uint32_t kind) {
+        const std::string data = values;
+        if (kind != json2pb::kArrayKindFloat && kind != json2pb::kArrayKindDouble)
+            throw std::invalid_argument("kind must be 8 (float) or 9 (double)");
+        const size_t eb = kind == json2pb::kArrayKindFloat ? 4 : 8;
+        if (data.size() % eb) throw std::invalid_argument("values must hold whole elements");
+        std::vector<uint64_t> aligned((data.size() + 7) / 8);
+        memcpy(aligned.data(), data.data(), data.size());
+        std::string text;
+        json2pb::FormatFloatArray(aligned.data(), data.size() / eb, kind, &text);
+        return py::bytes(text);
+    }, py::arg("values"), py::arg("kind"));
     m.def("json_to_pb_to_json", [](const std::string& type_name, py::bytes text) {
         const pb::Descriptor* d = pb::DescriptorPool::generated_pool()->FindMessageTypeByName(type_name);
         if (!d || !d->prototype) throw std::invalid_argument("unknown message type " + type_name);
@@ -785,6 +804,8 @@ PYBIND11_MODULE(_native, m) {
         d["pb2json_arrays"] = s.pb2json_arrays;
         d["pb2json_elems"] = s.pb2json_elems;
         d["pb2json_failures"] = s.pb2json_failures;
+        d["pb2json_float_arrays"] = s.pb2json_float_arrays;
+        d["pb2json_float_elems"] = s.pb2json_float_elems;
         d["int_arrays"] = s.int_arrays;
         d["int_array_fallbacks"] = s.int_array_fallbacks;
         d["sparse_skips"] = s.sparse_skips;

@@ -51,3 +51,40 @@ def json_index_host(data):
         elif not in_str and c in _STRUCTURAL:
             out.append(i)
     return out, in_str
+
+
+_FLOAT_KINDS = {torch.float32: 8, torch.float64: 9}
+PRINT_ERRORS = {2: "refused (bad arguments)", 3: "longer than the output buffer", 4: "the source changed while printing"}
+
+
+def json_print_floats(values):
+    """float32 / float64 device tensor -> uint8 device tensor of JSON text
+    ``v,v,...,v`` (no brackets), every element exactly as the host's pb2json
+    prints a double: the shortest digits that convert back, ``2.0`` /
+    ``123.45`` / ``0.000123`` / ``1.5e-7`` layouts, ``"NaN"`` / ``"Infinity"``
+    / ``"-Infinity"`` quoted; a float32 is widened first (0.1f prints as
+    0.10000000149011612). The values never leave HBM
+    (``gpu::DevicePrintFloatArrays``).
+
+    The printer runs on a pool stream, not on torch's: the caller's current
+    stream is synchronized before the call, and the text is complete when
+    this returns."""
+    require_gpu_tensor(values, "values")
+    if values.dtype not in _FLOAT_KINDS:
+        raise TypeError("values must be float32 or float64, not %s" % values.dtype)
+    dev = values.device
+    t = values.contiguous().view(-1)
+    n = t.numel()
+    if n == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev)
+    cap = native.gpu.json_float_worst_case(n)
+    if cap >= 1 << 32:
+        raise ValueError("json_print_floats handles outputs below 4 GiB")
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (length, err), = native.gpu.device_json_print_floats([t.data_ptr()], [n], [_FLOAT_KINDS[t.dtype]],
+                                                            [out.data_ptr()], [cap], dev.index or 0)
+    if err:
+        raise ValueError("json_print_floats: " + PRINT_ERRORS.get(err, "code %d" % err))
+    return out[:length]
