@@ -31,6 +31,7 @@
 
 #include <cstdint>
 
+#include "base/decimal_to_double.h"
 #include "base/shortest_double.h"
 #include "gpu/kernels.h"
 
@@ -460,6 +461,100 @@ __global__ void __launch_bounds__(256) json_int_array_kernel(const char* __restr
     out[i] = neg ? (int64_t)((uint64_t)0 - v) : (int64_t)v;
 }
 
+// json2pb number arrays, floats among them (kernels.h JsonNumberJob; the
+// reference converts every element with rapidjson's number parser on the
+// host). The shape is json_int_array_kernel's; the conversion is
+// base/decimal_to_double.h, the code json::Reader runs. A separator of
+// 0xFFFFFFFF stands for one before the text's first byte (seps[i] + 1 is
+// taken mod 2^32), so bare "v,v,...,v" text needs no bracket.
+namespace dd = ::mrpc::decimal_to_double;
+
+__global__ void __launch_bounds__(256) json_number_init_kernel(JsonNumberResult* __restrict__ res, int njobs) {
+    const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (j < njobs) res[j] = JsonNumberResult{0xFFFFFFFFu, 0u};
+}
+
+__global__ void __launch_bounds__(256) json_number_publish_kernel(const JsonNumberResult* __restrict__ res,
+                                                                  JsonNumberResult* __restrict__ out, int njobs) {
+    const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (j < njobs) out[j] = res[j];
+}
+
+__global__ void __launch_bounds__(256) json_number_array_kernel(const JsonNumberJob* __restrict__ jobs, int njobs,
+                                                                JsonNumberResult* __restrict__ res) {
+    __shared__ char span[kIntSpan];
+    __shared__ uint32_t lo_s, hi_s;
+    // the job that owns this block: the last whose first_block is not past it
+    int ja = 0, jb = njobs - 1;
+    while (ja < jb) {
+        const int mid = (ja + jb + 1) / 2;
+        if (jobs[mid].first_block <= blockIdx.x) ja = mid;
+        else jb = mid - 1;
+    }
+    const JsonNumberJob job = jobs[ja];
+    const char* __restrict__ text = job.text;
+    const uint32_t* __restrict__ seps = job.seps;
+    const uint32_t n = job.count;
+    const uint64_t first64 = (uint64_t)(blockIdx.x - job.first_block) * 256;
+    if (first64 >= n) return;  // uniform: a block the host did not mean for this job
+    const uint32_t first = (uint32_t)first64;
+    const uint64_t i64 = first64 + threadIdx.x;
+    const uint32_t i = (uint32_t)i64;
+    const uint32_t last = (uint32_t)(first64 + 256 < n ? first64 + 256 : n);  // elements [first, last)
+    uint32_t b = 0, e = 0;
+    if (i64 < n) {
+        b = seps[i] + 1;
+        e = seps[i + 1];
+    }
+    if (threadIdx.x == 0) lo_s = seps[first] + 1;
+    if (i64 + 1 == last) hi_s = e;
+    __syncthreads();
+    const uint32_t lo = lo_s, hi = hi_s;
+    const bool staged = hi >= lo && hi - lo <= kIntSpan;
+    if (staged) {
+        constexpr int kPer = kIntSpan / 256;
+        char v[kPer];
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) {
+            const uint32_t j = threadIdx.x + (uint32_t)k * 256;
+            v[k] = j < hi - lo ? text[lo + j] : 0;
+        }
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) {
+            const uint32_t j = threadIdx.x + (uint32_t)k * 256;
+            if (j < hi - lo) span[j] = v[k];
+        }
+    }
+    __syncthreads();
+    if (i64 >= n) return;
+    // separators that do not ascend: never index LDS outside the staged span
+    if (b > e || (staged && (b < lo || e > hi))) b = e = lo;
+    // positions stay absolute; an LDS pointer must never be offset below the
+    // array (a flat address below the LDS aperture is a global address)
+    auto at = [&](uint32_t k) -> char { return staged ? span[k - lo] : text[k]; };
+    while (b < e && json_ws(at(b))) ++b;
+    while (e > b && json_ws(at(e - 1))) --e;
+    dd::NumberResult r;
+    dd::ParseJsonNumberAt(at, b, e, &r);
+    if (r.cls == dd::kMalformed) {
+        atomicMin(&res[ja].bad, i);
+        return;
+    }
+    if (r.cls == dd::kNeedsExact) {
+        const uint32_t slot = atomicAdd(&res[ja].n_redo, 1u);
+        if (slot < job.redo_cap) job.redo[slot] = i;
+        return;
+    }
+    if (job.mode == JSON_PARSE_NUMBERS) {
+        static_cast<uint64_t*>(job.out)[i] = r.bits;
+        job.classes[i] = r.cls;
+    } else if (job.mode == JSON_PARSE_FLOAT64) {
+        static_cast<uint64_t*>(job.out)[i] = dd::NumberToDoubleBits(r);
+    } else {
+        static_cast<uint32_t*>(job.out)[i] = dd::NarrowDoubleBits(dd::NumberToDoubleBits(r));
+    }
+}
+
 // pb2json float / double arrays (kernels.h: size, prefix, place). The
 // reference prints them element by element on the host through rapidjson's
 // Writer (src/json2pb/pb_to_json.cpp); here one lane formats one element
@@ -599,6 +694,20 @@ int LaunchJsonIntArray(const char* text, const uint32_t* seps, uint32_t n, int64
                        hipStream_t s) {
     if (n == 0) return 0;
     hipLaunchKernelGGL(json_int_array_kernel, dim3((n + 255) / 256), dim3(256), 0, s, text, seps, n, out, bad);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int LaunchJsonNumberArrays(const JsonNumberJob* jobs, int njobs, uint32_t nblocks, JsonNumberResult* res_dev,
+                           JsonNumberResult* res_out, hipStream_t s) {
+    if (njobs <= 0 || nblocks == 0) return 0;
+    if (!jobs || !res_dev || !res_out) return -1;
+    const dim3 small((unsigned)(njobs + 255) / 256);
+    hipLaunchKernelGGL(json_number_init_kernel, small, dim3(256), 0, s, res_dev, njobs);
+    if (hipGetLastError() != hipSuccess) return -1;
+    hipLaunchKernelGGL(json_number_array_kernel, dim3(nblocks), dim3(256), 0, s, jobs, njobs, res_dev);
+    if (hipGetLastError() != hipSuccess) return -1;
+    hipLaunchKernelGGL(json_number_publish_kernel, small, dim3(256), 0, s, (const JsonNumberResult*)res_dev, res_out,
+                       njobs);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -14,6 +14,7 @@
 #include <atomic>
 #include <cstring>
 
+#include "base/decimal_to_double.h"
 #include "base/flags.h"
 #include "base/shortest_double.h"
 #include "base/time.h"
@@ -21,6 +22,7 @@
 #include "gpu/hbm_pool.h"
 #include "gpu/kernels.h"
 #include "gpu/snappy_offload.h"
+#include "json/json.h"
 #include "json/json2pb.h"
 #include "rpc/span.h"
 #include "var/var.h"
@@ -35,6 +37,12 @@ DEFINE_int32(gpu_pb2json_float_min_elems, 4096,
              "the host printer (4096: the smallest size measured, where the device already wins, "
              "profiles/json_float_print.txt). 0: never. Reloadable");
 MRPC_VALIDATE_FLAG(gpu_pb2json_float_min_elems, ::mrpc::PassValidator);
+DEFINE_int32(gpu_json2pb_float_min_elems, 4096,
+             "JSON arrays of numbers that are not all int64 (floats) with at least this many elements are parsed by "
+             "the device in json2pb (json_number_array_kernel) while the GPU JSON path is enabled; shorter ones by "
+             "the host's packed pass (4096: the smallest size measured, where the device already wins, "
+             "profiles/json_float_parse.txt). 0: never. Reloadable");
+MRPC_VALIDATE_FLAG(gpu_json2pb_float_min_elems, ::mrpc::PassValidator);
 DEFINE_int32(json_index_min_density, 8,
              "structural characters per KiB (sampled in three windows) a JSON body needs before the GPU index is "
              "used; sparser bodies (long strings) parse faster on the host; 0: always offload");
@@ -284,6 +292,115 @@ int PrintFloatsOnDevice(const void* values, size_t n, uint32_t kind, std::string
     return 0;
 }
 
+int DeviceParseNumberArrays(DeviceNumberParseJob* jobs, int n, int device) {
+    if (n <= 0) return 0;
+    if (!jobs || device < 0) return -1;
+    // refuse what must not reach a kernel; count the blocks of the rest
+    uint64_t nblocks = 0;
+    int live = 0;
+    for (int i = 0; i < n; ++i) {
+        DeviceNumberParseJob& j = jobs[i];
+        j.n_redo = 0;
+        j.first_bad = 0xFFFFFFFFu;
+        j.err = 0;
+        if (j.count == 0) continue;
+        const size_t align = j.mode == kJsonParseFloat32 ? 4 : 8;
+        if (j.mode > kJsonParseFloat32 || !j.text || !j.seps || !j.out ||
+            (j.mode == kJsonParseNumbers && !j.classes) || (j.redo_cap > 0 && !j.redo) ||
+            ((uintptr_t)j.out & (align - 1)) != 0 || ((uintptr_t)j.seps & 3) != 0 ||
+            ((uintptr_t)j.redo & 3) != 0 || j.count > 0xFFFFFFFEull) {
+            j.err = 2;
+            continue;
+        }
+        nblocks += (j.count + 255) / 256;
+        ++live;
+    }
+    if (live == 0) return 0;
+    if (nblocks > 0x7FFFFFFFull) return -1;  // one grid
+    Pinned tables((size_t)live * (sizeof(JsonNumberJob) + sizeof(JsonNumberResult)));
+    Hbm counters((size_t)live * sizeof(JsonNumberResult), device);
+    if (!tables.p || !counters.p) return -1;
+    JsonNumberJob* tj = static_cast<JsonNumberJob*>(tables.p);
+    JsonNumberResult* tr = reinterpret_cast<JsonNumberResult*>(tj + live);
+    uint32_t block = 0;
+    int k = 0;
+    for (int i = 0; i < n; ++i) {
+        const DeviceNumberParseJob& j = jobs[i];
+        if (j.count == 0 || j.err != 0) continue;
+        tj[k] = JsonNumberJob{j.text, j.seps, j.out, j.classes, j.redo, (uint32_t)j.count, j.mode, j.redo_cap, block};
+        tr[k] = JsonNumberResult{0xFFFFFFFFu, 0};
+        block += (uint32_t)((j.count + 255) / 256);
+        ++k;
+    }
+    int prev = 0;
+    hipGetDevice(&prev);
+    if (prev != device) hipSetDevice(device);
+    hipStream_t s = PoolStream(device);
+    const int rc = s ? LaunchJsonNumberArrays(tj, live, block, static_cast<JsonNumberResult*>(counters.p), tr, s) : -1;
+    const int wrc = s ? SyncStream(s) : -1;  // never free buffers a launched kernel may still use
+    if (prev != device) hipSetDevice(prev);
+    if (rc != 0 || wrc != 0) return -1;
+    k = 0;
+    for (int i = 0; i < n; ++i) {
+        DeviceNumberParseJob& j = jobs[i];
+        if (j.count == 0 || j.err != 0) continue;
+        j.first_bad = tr[k].bad;
+        j.n_redo = tr[k].n_redo;
+        if (j.first_bad != 0xFFFFFFFFu) j.err = 1;
+        else if (j.n_redo > j.redo_cap) j.err = 3;
+        ++k;
+    }
+    return 0;
+}
+
+namespace {
+// elements of one array the device may hand back for exact arithmetic before
+// the whole array goes to the host (they are rare: a 20-digit number whose
+// 19-digit truncation straddles a rounding boundary)
+constexpr uint32_t kRedoCap = 64;
+}  // namespace
+
+bool ParseNumbersOnDevice(const char* base, const uint32_t* seps, size_t nseps, uint64_t* payload, uint8_t* classes,
+                          int device, uint32_t* n_redo) {
+    if (n_redo) *n_redo = 0;
+    if (device < 0 || nseps < 2 || !base || !seps || !payload || !classes) return false;
+    const size_t n = nseps - 1;
+    if (n > 0xFFFFFFFEull) return false;
+    // the text from the byte after the first separator up to the last one
+    const uint32_t lo = seps[0] + 1, hi = seps[nseps - 1];
+    if (hi < lo) return false;
+    const size_t vals_bytes = n * sizeof(uint64_t);
+    Pinned text((size_t)(hi - lo) + 1), sep(nseps * sizeof(uint32_t)),
+        vals(vals_bytes + kRedoCap * sizeof(uint32_t) + n);
+    if (!text.p || !sep.p || !vals.p) return false;
+    memcpy(text.p, base + lo, hi - lo);
+    uint32_t* sp = static_cast<uint32_t*>(sep.p);
+    for (size_t i = 0; i < nseps; ++i) sp[i] = seps[i] - lo;  // the first becomes 0xFFFFFFFF
+    DeviceNumberParseJob job;
+    job.text = static_cast<const char*>(text.p);
+    job.seps = sp;
+    job.count = n;
+    job.mode = kJsonParseNumbers;
+    job.out = vals.p;
+    job.redo = reinterpret_cast<uint32_t*>(static_cast<char*>(vals.p) + vals_bytes);
+    job.redo_cap = kRedoCap;
+    job.classes = reinterpret_cast<uint8_t*>(job.redo + kRedoCap);
+    if (DeviceParseNumberArrays(&job, 1, device) != 0 || job.err != 0) return false;
+    memcpy(payload, vals.p, vals_bytes);
+    memcpy(classes, job.classes, n);
+    for (uint32_t r = 0; r < job.n_redo; ++r) {
+        const uint32_t i = job.redo[r];
+        if (i >= n) return false;
+        const char* b = base + (uint32_t)(seps[i] + 1);
+        const char* e = base + seps[i + 1];
+        while (b < e && (*b == ' ' || *b == '\t' || *b == '\n' || *b == '\r')) ++b;
+        while (e > b && (e[-1] == ' ' || e[-1] == '\t' || e[-1] == '\n' || e[-1] == '\r')) --e;
+        if (!json::ParseNumberExact(b, e, &payload[i], &classes[i])) return false;
+    }
+    if (n_redo) *n_redo = job.n_redo;
+    return true;
+}
+
 namespace {
 
 std::atomic<int64_t> g_arrays{0}, g_array_elems{0}, g_array_failures{0};
@@ -360,6 +477,26 @@ bool int_array_offload(const char* base, const uint32_t* seps, size_t nseps, std
     return true;
 }
 
+std::atomic<int64_t> g_number_arrays{0}, g_number_elems{0}, g_number_array_fallbacks{0}, g_number_redo_elems{0};
+
+// json2pb number arrays that are not all int64 (json::SetNumberArrayOffload).
+// The reader's own threshold is 1: the reloadable flag decides here.
+bool number_array_offload(const char* base, const uint32_t* seps, size_t nseps, uint64_t* payload,
+                          uint8_t* classes) {
+    const int dev = g_device;
+    const int min_elems = FLAGS_gpu_json2pb_float_min_elems;
+    if (dev < 0 || nseps < 2 || min_elems <= 0 || nseps - 1 < (size_t)min_elems) return false;
+    uint32_t redone = 0;
+    if (!ParseNumbersOnDevice(base, seps, nseps, payload, classes, dev, &redone)) {
+        g_number_array_fallbacks.fetch_add(1, std::memory_order_relaxed);
+        return false;
+    }
+    g_number_arrays.fetch_add(1, std::memory_order_relaxed);
+    g_number_elems.fetch_add((int64_t)(nseps - 1), std::memory_order_relaxed);
+    g_number_redo_elems.fetch_add((int64_t)redone, std::memory_order_relaxed);
+    return true;
+}
+
 }  // namespace
 
 int EnableGpuJsonIndex(int device, size_t min_bytes, std::string* error) {
@@ -368,6 +505,12 @@ int EnableGpuJsonIndex(int device, size_t min_bytes, std::string* error) {
     json2pb::SetJsonIndexOffload(offload, min_bytes);
     json2pb::SetPb2JsonArrayOffload(array_offload, (size_t)std::max(1, FLAGS_gpu_pb2json_min_elems));
     json::SetIntArrayOffload(int_array_offload, (size_t)std::max(1, FLAGS_gpu_pb2json_min_elems));
+    json::SetNumberArrayOffload(number_array_offload, 1);
+    static var::PassiveStatus<int64_t> v8("gpu_json_number_arrays", [] { return g_number_arrays.load(); });
+    static var::PassiveStatus<int64_t> v9("gpu_json_number_elems", [] { return g_number_elems.load(); });
+    static var::PassiveStatus<int64_t> v10("gpu_json_number_array_fallbacks",
+                                           [] { return g_number_array_fallbacks.load(); });
+    static var::PassiveStatus<int64_t> v11("gpu_json_number_redo_elems", [] { return g_number_redo_elems.load(); });
     static var::PassiveStatus<int64_t> v5("gpu_json_int_arrays", [] { return g_int_arrays.load(); });
     static var::PassiveStatus<int64_t> v4("gpu_pb2json_arrays", [] { return g_arrays.load(); });
     static var::PassiveStatus<int64_t> v6("gpu_pb2json_float_arrays", [] { return g_float_arrays.load(); });
@@ -382,6 +525,7 @@ void DisableGpuJsonIndex() {
     json2pb::SetJsonIndexOffload(nullptr, (size_t)-1);
     json2pb::SetPb2JsonArrayOffload(nullptr, (size_t)-1);
     json::SetIntArrayOffload(nullptr, (size_t)-1);
+    json::SetNumberArrayOffload(nullptr, (size_t)-1);
 }
 
 GpuJsonStats GetGpuJsonStats() {
@@ -397,6 +541,10 @@ GpuJsonStats GetGpuJsonStats() {
     s.int_arrays = g_int_arrays.load();
     s.int_array_fallbacks = g_int_array_fallbacks.load();
     s.sparse_skips = g_sparse.load();
+    s.number_arrays = g_number_arrays.load();
+    s.number_elems = g_number_elems.load();
+    s.number_array_fallbacks = g_number_array_fallbacks.load();
+    s.number_redo_elems = g_number_redo_elems.load();
     return s;
 }
 

@@ -390,6 +390,47 @@ int LaunchJsonFloatPrint(const JsonFloatTables& t, hipStream_t s);
 // parses the array itself. *bad must be 0 before the launch.
 int LaunchJsonIntArray(const char* text, const uint32_t* seps, uint32_t n, int64_t* out, int32_t* bad,
                        hipStream_t s);
+// JSON number arrays (floats among them): json_number_array_kernel, in the
+// shape of the integer kernel above (a lane per element, 256 per workgroup,
+// the workgroup's text span staged in LDS, memory read directly when the
+// span exceeds the window), converts each trimmed element with
+// base/decimal_to_double.h, the code the host reader runs. All jobs share
+// one launch: job j owns the blocks [first_block, first_block +
+// ceil(count / 256)). Output by mode:
+//   JSON_PARSE_NUMBERS  out: 8 bytes of payload per element, classes: a byte
+//                       per element (0 int64, 1 uint64, 2 double bits)
+//   JSON_PARSE_FLOAT64  out: the double per element (an integer class is
+//                       converted to the double of its value, so "-0" is +0.0)
+//   JSON_PARSE_FLOAT32  out: (float) of that double, rounded in integers
+// res[j].bad: the lowest index of an element outside the RFC 8259 number
+// grammar (atomicMin), 0xFFFFFFFF when there is none; when it is set nothing
+// of the job's output may be trusted. An element that needs exact arithmetic
+// (more than 19 significant digits that do not decide the rounding, or more
+// than kMaxDeviceNumberChars characters) gets nothing written to out; its
+// index goes to redo[slot] with slot taken from the atomic counter
+// res[j].n_redo, which keeps counting past redo_cap (slots >= redo_cap are
+// dropped). The counters live in device memory (res_dev, njobs entries,
+// initialised by the launch) and are copied to res_out (device-writable,
+// pinned host or device) by a last small kernel, so the host needs no atomics
+// across the bus.
+constexpr uint32_t JSON_PARSE_NUMBERS = 0, JSON_PARSE_FLOAT64 = 1, JSON_PARSE_FLOAT32 = 2;
+struct JsonNumberJob {
+    const char* text;      // device-readable (pinned host or device)
+    const uint32_t* seps;  // count + 1 separator offsets into text; element i is (seps[i], seps[i+1])
+    void* out;             // device-writable, naturally aligned for the mode
+    uint8_t* classes;      // JSON_PARSE_NUMBERS only
+    uint32_t* redo;        // redo_cap entries, may be null when redo_cap is 0
+    uint32_t count;        // 1 .. 2^32 - 2
+    uint32_t mode;
+    uint32_t redo_cap;
+    uint32_t first_block;
+};
+struct JsonNumberResult {
+    uint32_t bad;
+    uint32_t n_redo;
+};
+int LaunchJsonNumberArrays(const JsonNumberJob* jobs, int njobs, uint32_t nblocks, JsonNumberResult* res_dev,
+                           JsonNumberResult* res_out, hipStream_t s);
 // scratch must hold JsonIndexScratchBytes(n).
 size_t JsonIndexScratchBytes(uint64_t n);
 int LaunchJsonIndex(const uint8_t* in, uint64_t n, uint32_t* out_pos, uint64_t max_out, uint64_t* count_dev,

@@ -9,6 +9,8 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "base/decimal_to_double.h"
+
 namespace mrpc {
 namespace json {
 
@@ -16,8 +18,14 @@ const std::vector<Value>& Value::packed_view() const {
     std::shared_ptr<const std::vector<Value>> v = std::atomic_load(&_view);
     if (v) return *v;
     auto built = std::make_shared<std::vector<Value>>();
-    built->reserve(_ints.size());
-    for (int64_t x : _ints) built->emplace_back(x);
+    if (_nums) {
+        built->reserve(_nums->payload.size());
+        for (size_t i = 0; i < _nums->payload.size(); ++i)
+            built->push_back(NumberElement(_nums->payload[i], _nums->classes[i]));
+    } else {
+        built->reserve(_ints.size());
+        for (int64_t x : _ints) built->emplace_back(x);
+    }
     std::shared_ptr<const std::vector<Value>> want = built;
     // first publisher wins; a loser's copy is dropped, every reader gets the
     // published one
@@ -26,6 +34,13 @@ const std::vector<Value>& Value::packed_view() const {
     return *expected;
 }
 
+Value Value::NumberElement(uint64_t payload, uint8_t cls) {
+    if (cls == decimal_to_double::kInt64) return Value((int64_t)payload);
+    if (cls == decimal_to_double::kUInt64) return Value(payload);
+    double d;
+    memcpy(&d, &payload, sizeof(d));
+    return Value(d);
+}
 
 int64_t Value::as_int() const {
     switch (_type) {
@@ -219,6 +234,27 @@ void Value::write(std::string* out, bool pretty, int indent) const {
     case STRING: EscapeString(_s, out); break;
     case RAW: *out += _s; break;
     case ARRAY:
+        if (_nums) {  // each element as its INT / UINT / DOUBLE Value prints
+            out->push_back('[');
+            for (size_t i = 0; i < _nums->payload.size(); ++i) {
+                if (i) out->push_back(',');
+                nl(indent + 1);
+                const uint64_t x = _nums->payload[i];
+                const uint8_t cls = _nums->classes[i];
+                if (cls == decimal_to_double::kInt64) {
+                    snprintf(buf, sizeof(buf), "%lld", (long long)x);
+                    *out += buf;
+                } else if (cls == decimal_to_double::kUInt64) {
+                    snprintf(buf, sizeof(buf), "%llu", (unsigned long long)x);
+                    *out += buf;
+                } else {
+                    NumberElement(x, cls).write(out, pretty, indent + 1);
+                }
+            }
+            nl(indent);
+            out->push_back(']');
+            break;
+        }
         if (!_ints.empty()) {
             out->push_back('[');
             for (size_t i = 0; i < _ints.size(); ++i) {
@@ -270,6 +306,145 @@ std::atomic<size_t> g_int_array_min{(size_t)-1};
 void SetIntArrayOffload(IntArrayOffload fn, size_t min_elems) {
     g_int_array_min.store(fn ? (min_elems ? min_elems : 1) : (size_t)-1, std::memory_order_relaxed);
     g_int_array_offload.store(fn, std::memory_order_release);
+}
+
+namespace {
+std::atomic<NumberArrayOffload> g_number_array_offload{nullptr};
+std::atomic<size_t> g_number_array_min{(size_t)-1};
+std::atomic<bool> g_packed_numbers{true};
+
+namespace dd = decimal_to_double;
+
+inline bool json_space(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; }
+
+// A decimal int64 literal at [p, end): the end of its digits, or nullptr
+// (no digits, more than 19 digits, or out of int64 range: the caller
+// takes the general path). Up to 19 digits cannot overflow a uint64, so
+// the loop has no per-digit overflow check.
+const char* parse_int64(const char* p, const char* end, int64_t* out) {
+    const bool neg = p < end && *p == '-';
+    if (neg) ++p;
+    const char* b = p;
+    const char* lim = end - p > 19 ? p + 19 : end;
+    uint64_t v = 0;
+    while (p < lim && (unsigned)(*p - '0') < 10u) v = v * 10 + (unsigned)(*p++ - '0');
+    if (p == b || (p < end && (unsigned)(*p - '0') < 10u)) return nullptr;
+    if (neg) {
+        if (v > (uint64_t)INT64_MAX + 1) return nullptr;
+        *out = (int64_t)(0 - v);
+    } else {
+        if (v > (uint64_t)INT64_MAX) return nullptr;
+        *out = (int64_t)v;
+    }
+    return p;
+}
+
+// The general number route (std::from_chars: no std::string per number, no
+// errno/strtoll round trip) over text [b, e) made of digits, '.', 'e', 'E'
+// and exponent signs after a leading -?digit: laxer than RFC 8259 ("01",
+// "1."). is_float: the text holds '.', 'e' or 'E'. False: "bad number".
+bool convert_number_general(const char* b, const char* e, bool is_float, uint64_t* payload, uint8_t* cls) {
+    if (!is_float) {
+        int64_t x;
+        if (parse_int64(b, e, &x) == e) {
+            *payload = (uint64_t)x;
+            *cls = dd::kInt64;
+            return true;
+        }
+        if (*b != '-') {
+            uint64_t x;
+            auto r = std::from_chars(b, e, x);
+            if (r.ec == std::errc() && r.ptr == e) {
+                *payload = x;
+                *cls = x <= (uint64_t)INT64_MAX ? dd::kInt64 : dd::kUInt64;
+                return true;
+            }
+        }
+    }
+    double d = 0;
+    auto r = std::from_chars(b, e, d);
+    if (r.ec == std::errc::result_out_of_range) {
+        d = strtod(std::string(b, e - b).c_str(), nullptr);  // +-inf / denormal edge, as before
+    } else if (r.ec != std::errc() || r.ptr != e) {
+        return false;
+    }
+    memcpy(payload, &d, sizeof(d));
+    *cls = dd::kDouble;
+    return true;
+}
+
+// -? (0 | [1-9][0-9]*) (\.[0-9]+)? ([eE][+-]?[0-9]+)? over all of [p, e)
+bool rfc8259_number(const char* p, const char* e, bool* is_float) {
+    auto digit = [&](const char* q) { return q < e && (unsigned)(*q - '0') < 10u; };
+    *is_float = false;
+    if (p < e && *p == '-') ++p;
+    if (!digit(p)) return false;
+    if (*p == '0') {
+        ++p;
+    } else {
+        while (digit(p)) ++p;
+    }
+    if (p < e && *p == '.') {
+        *is_float = true;
+        ++p;
+        if (!digit(p)) return false;
+        while (digit(p)) ++p;
+    }
+    if (p < e && (*p == 'e' || *p == 'E')) {
+        *is_float = true;
+        ++p;
+        if (p < e && (*p == '+' || *p == '-')) ++p;
+        if (!digit(p)) return false;
+        while (digit(p)) ++p;
+    }
+    return p == e;
+}
+}  // namespace
+
+void SetNumberArrayOffload(NumberArrayOffload fn, size_t min_elems) {
+    g_number_array_min.store(fn ? (min_elems ? min_elems : 1) : (size_t)-1, std::memory_order_relaxed);
+    g_number_array_offload.store(fn, std::memory_order_release);
+}
+
+void SetPackedNumberArrays(bool on) { g_packed_numbers.store(on, std::memory_order_relaxed); }
+
+bool ParseNumberExact(const char* b, const char* e, uint64_t* payload, uint8_t* cls) {
+    bool is_float;
+    return rfc8259_number(b, e, &is_float) && convert_number_general(b, e, is_float, payload, cls);
+}
+
+void NumberArraySeparators(const char* text, size_t n, std::vector<uint32_t>* seps) {
+    seps->clear();
+    size_t b = 0, e = n;
+    while (b < e && json_space(text[b])) ++b;
+    while (e > b && json_space(text[e - 1])) --e;
+    const bool bracketed = e - b >= 2 && text[b] == '[' && text[e - 1] == ']';
+    seps->push_back(bracketed ? (uint32_t)b : 0xFFFFFFFFu);
+    const size_t from = bracketed ? b + 1 : 0, to = bracketed ? e - 1 : n;
+    for (size_t i = from; i < to; ++i) {
+        if (text[i] == ',') seps->push_back((uint32_t)i);
+    }
+    seps->push_back((uint32_t)to);
+}
+
+bool ParseNumberArray(const char* base, const uint32_t* seps, size_t nseps, uint64_t* payload, uint8_t* classes,
+                      bool exact, size_t* bad_index) {
+    for (size_t i = 0; i + 1 < nseps; ++i) {
+        const char* b = base + (uint32_t)(seps[i] + 1);  // 0xFFFFFFFF: before the first byte
+        const char* e = base + seps[i + 1];
+        while (b < e && json_space(*b)) ++b;
+        while (e > b && json_space(e[-1])) --e;
+        dd::NumberResult r;
+        dd::ParseJsonNumber(b, e, &r);
+        if (r.cls == dd::kNeedsExact && exact && !ParseNumberExact(b, e, &r.bits, &r.cls)) r.cls = dd::kMalformed;
+        if (r.cls == dd::kMalformed) {
+            if (bad_index) *bad_index = i;
+            return false;
+        }
+        payload[i] = r.bits;
+        classes[i] = r.cls;
+    }
+    return true;
 }
 
 namespace {
@@ -343,9 +518,26 @@ private:
         default: return number(v);
         }
     }
-    // Numbers are converted in place from the text (std::from_chars): no
-    // std::string per number, no errno/strtoll round trip.
+    // Numbers are converted in place from the text: base/decimal_to_double.h
+    // when the text is of the RFC 8259 grammar and it decides the rounding,
+    // the general route (std::from_chars) for everything else, so laxness
+    // and error text are what they always were.
     bool number(Value* v) {
+        uint64_t payload;
+        uint8_t cls;
+        if (!number_raw(&payload, &cls)) return false;
+        if (cls == dd::kInt64) {
+            *v = Value((int64_t)payload);
+        } else if (cls == dd::kUInt64) {
+            *v = Value(payload);
+        } else {
+            double d;
+            memcpy(&d, &payload, sizeof(d));
+            *v = Value(d);
+        }
+        return true;
+    }
+    bool number_raw(uint64_t* payload, uint8_t* cls) {
         const char* b = _p;
         if (_p < _end && *_p == '-') ++_p;
         if (_p >= _end || !isdigit((unsigned char)*_p)) return fail("bad number");
@@ -355,52 +547,17 @@ private:
             if (*_p == '.' || *_p == 'e' || *_p == 'E') is_float = true;
             ++_p;
         }
-        if (!is_float) {
-            int64_t x;
-            if (parse_int64(b, _p, &x) == _p) {
-                *v = Value(x);
+        if (g_packed_numbers.load(std::memory_order_relaxed)) {
+            dd::NumberResult r;
+            dd::ParseJsonNumber(b, _p, &r);
+            if (r.cls <= dd::kDouble) {
+                *payload = r.bits;
+                *cls = r.cls;
                 return true;
             }
-            if (*b != '-') {
-                uint64_t x;
-                auto r = std::from_chars(b, _p, x);
-                if (r.ec == std::errc() && r.ptr == _p) {
-                    if (x <= (uint64_t)INT64_MAX) *v = Value((int64_t)x);
-                    else *v = Value(x);
-                    return true;
-                }
-            }
         }
-        double d = 0;
-        auto r = std::from_chars(b, _p, d);
-        if (r.ec == std::errc::result_out_of_range) {
-            d = strtod(std::string(b, _p - b).c_str(), nullptr);  // +-inf / denormal edge, as before
-        } else if (r.ec != std::errc() || r.ptr != _p) {
-            return fail("bad number");
-        }
-        *v = Value(d);
+        if (!convert_number_general(b, _p, is_float, payload, cls)) return fail("bad number");
         return true;
-    }
-    // A decimal int64 literal at [p, end): the end of its digits, or nullptr
-    // (no digits, more than 19 digits, or out of int64 range: the caller
-    // takes the general path). Up to 19 digits cannot overflow a uint64, so
-    // the loop has no per-digit overflow check.
-    static const char* parse_int64(const char* p, const char* end, int64_t* out) {
-        const bool neg = p < end && *p == '-';
-        if (neg) ++p;
-        const char* b = p;
-        const char* lim = end - p > 19 ? p + 19 : end;
-        uint64_t v = 0;
-        while (p < lim && (unsigned)(*p - '0') < 10u) v = v * 10 + (unsigned)(*p++ - '0');
-        if (p == b || (p < end && (unsigned)(*p - '0') < 10u)) return nullptr;
-        if (neg) {
-            if (v > (uint64_t)INT64_MAX + 1) return nullptr;
-            *out = (int64_t)(0 - v);
-        } else {
-            if (v > (uint64_t)INT64_MAX) return nullptr;
-            *out = (int64_t)v;
-        }
-        return p;
     }
     // An integer element of an int array, converted in place: true with *x
     // when the next value is a plain int64 literal followed by ',' or ']'
@@ -515,12 +672,16 @@ private:
         }
         return true;
     }
-    // The index shows an array of >= the offload's minimum plain elements
-    // (only ',' between the brackets): one bulk parse instead of a Value
-    // per element; false leaves the array to the element-wise path.
-    bool bulk_int_array(Value* v) {
+    // The index shows an array of plain elements (only ',' between the
+    // brackets): one bulk parse instead of a Value per element. The integer
+    // offload is tried first when the run meets its minimum, then the number
+    // offload when the run meets its own; false leaves the array to the
+    // element-wise path.
+    bool bulk_array(Value* v) {
+        if (!_idx) return false;
         IntArrayOffload fn = g_int_array_offload.load(std::memory_order_acquire);
-        if (!fn || !_idx) return false;
+        NumberArrayOffload nfn = g_number_array_offload.load(std::memory_order_acquire);
+        if (!fn && !nfn) return false;
         const size_t at = (size_t)(_p - _begin);
         while (_k < _nidx && _idx[_k] < at) ++_k;
         if (_k >= _nidx || _idx[_k] != at) return false;
@@ -528,16 +689,41 @@ private:
         const size_t len = (size_t)(_end - _begin);
         while (j < _nidx && _idx[j] < len && _begin[_idx[j]] == ',') ++j;
         if (j >= _nidx || _idx[j] >= len || _begin[_idx[j]] != ']') return false;
-        if (j - _k < g_int_array_min.load(std::memory_order_relaxed)) return false;
-        std::vector<int64_t> ints;
-        if (!fn(_begin, _idx + _k, j - _k + 1, &ints) || ints.size() != j - _k) return false;
-        *v = Value::PackedInts(std::move(ints));
+        const size_t n = j - _k;
+        bool done = false;
+        if (fn && n >= g_int_array_min.load(std::memory_order_relaxed)) {
+            std::vector<int64_t> ints;
+            if (fn(_begin, _idx + _k, n + 1, &ints) && ints.size() == n) {
+                *v = Value::PackedInts(std::move(ints));
+                done = true;
+            }
+        }
+        if (!done && nfn && n >= g_number_array_min.load(std::memory_order_relaxed) &&
+            g_packed_numbers.load(std::memory_order_relaxed)) {
+            Value::NumberArray nums;
+            nums.payload.resize(n);
+            nums.classes.resize(n);
+            if (nfn(_begin, _idx + _k, n + 1, nums.payload.data(), nums.classes.data())) {
+                *v = packed(std::move(nums));
+                done = true;
+            }
+        }
+        if (!done) return false;
         _p = _begin + _idx[j] + 1;
         _k = j + 1;
         return true;
     }
+    // Packed numbers; packed ints when every element turned out an int64
+    static Value packed(Value::NumberArray nums) {
+        for (uint8_t c : nums.classes) {
+            if (c != dd::kInt64) return Value::PackedNumbers(std::move(nums));
+        }
+        std::vector<int64_t> ints(nums.payload.size());
+        if (!ints.empty()) memcpy(ints.data(), nums.payload.data(), ints.size() * sizeof(int64_t));
+        return Value::PackedInts(std::move(ints));
+    }
     bool array(Value* v, int depth) {
-        if (bulk_int_array(v)) return true;
+        if (bulk_array(v)) return true;
         ++_p;
         *v = Value::Array();
         skip();
@@ -548,7 +734,9 @@ private:
         // Integer arrays stay packed (one int64 per element, no Value per
         // element; json2pb takes them in bulk, the way rapidjson's in-situ
         // numbers feed the reference's json_to_pb.cpp). The first element
-        // that is not a plain int64 turns the array into Values.
+        // that is not a plain int64 but is a number carries the array on in
+        // packed-number form (8 bytes and a class byte per element); the
+        // first element that is no number turns it into Values.
         std::vector<int64_t> ints;
         for (;;) {
             int64_t x;
@@ -567,7 +755,36 @@ private:
             }
             return fail("expected , or ]");
         }
-        for (int64_t x : ints) v->push_back(Value(x));
+        auto starts_number = [&] { return _p < _end && (*_p == '-' || isdigit((unsigned char)*_p)); };
+        if (g_packed_numbers.load(std::memory_order_relaxed) && starts_number()) {
+            Value::NumberArray nums;
+            nums.payload.assign(ints.begin(), ints.end());
+            nums.classes.assign(ints.size(), (uint8_t)dd::kInt64);
+            while (starts_number()) {
+                uint64_t payload;
+                uint8_t cls;
+                if (!number_raw(&payload, &cls)) return false;
+                nums.payload.push_back(payload);
+                nums.classes.push_back(cls);
+                skip();
+                if (_p < _end && *_p == ',') {
+                    ++_p;
+                    skip();
+                    continue;
+                }
+                if (_p < _end && *_p == ']') {
+                    ++_p;
+                    *v = packed(std::move(nums));
+                    return true;
+                }
+                return fail("expected , or ]");
+            }
+            // no number: the element-wise loop takes over where this one stands
+            for (size_t i = 0; i < nums.payload.size(); ++i)
+                v->push_back(Value::NumberElement(nums.payload[i], nums.classes[i]));
+        } else {
+            for (int64_t x : ints) v->push_back(Value(x));
+        }
         for (;;) {
             Value e;
             skip();

@@ -23,7 +23,7 @@ public:
     // copy never reads _view non-atomically while a reader publishes it
     Value(const Value& o)
         : _type(o._type), _b(o._b), _i(o._i), _u(o._u), _d(o._d), _s(o._s), _arr(o._arr), _ints(o._ints),
-          _obj(o._obj) {}
+          _nums(o._nums), _obj(o._obj) {}
     Value(Value&&) = default;
     Value& operator=(const Value& o) {
         if (this != &o) *this = Value(o);
@@ -71,8 +71,29 @@ public:
         return a;
     }
     const std::vector<int64_t>* packed_ints() const { return _ints.empty() ? nullptr : &_ints; }
+    // An array of numbers of which at least one is not an int64 (floats, or
+    // integers above INT64_MAX) stays packed too: 8 bytes of payload and a
+    // class byte per element, so int64 and uint64 elements stay exact. The
+    // classes are those of base/decimal_to_double.h: 0 the payload is the
+    // int64 (an INT Value), 1 a uint64 above INT64_MAX (UINT), 2 the bits of
+    // the double (DOUBLE). packed_ints() is nullptr for such an array; the
+    // accessors behave as for packed ints. The packed form never changes, so
+    // copies share it.
+    struct NumberArray {
+        std::vector<uint64_t> payload;
+        std::vector<uint8_t> classes;
+    };
+    static Value PackedNumbers(NumberArray nums) {
+        Value a;
+        a._type = ARRAY;
+        if (!nums.payload.empty()) a._nums = std::make_shared<const NumberArray>(std::move(nums));
+        return a;
+    }
+    const NumberArray* packed_numbers() const { return _nums.get(); }
+    // the Value of element i of a packed-number array
+    static Value NumberElement(uint64_t payload, uint8_t cls);
     const std::vector<Value>& array() const {
-        if (_ints.empty()) return _arr;
+        if (_ints.empty() && !_nums) return _arr;
         return packed_view();
     }
     std::vector<Value>& mutable_array() {
@@ -86,7 +107,11 @@ public:
         _arr.push_back(std::move(v));
         return _arr.back();
     }
-    size_t size() const { return _type == ARRAY ? (_ints.empty() ? _arr.size() : _ints.size()) : _obj.size(); }
+    size_t size() const {
+        if (_type != ARRAY) return _obj.size();
+        if (_nums) return _nums->payload.size();
+        return _ints.empty() ? _arr.size() : _ints.size();
+    }
 
     // objects (insertion ordered)
     const std::vector<std::pair<std::string, Value>>& members() const { return _obj; }
@@ -100,6 +125,14 @@ public:
 private:
     void write(std::string* out, bool pretty, int indent) const;
     void materialize() {
+        if (_nums) {
+            _arr.reserve(_nums->payload.size());
+            for (size_t i = 0; i < _nums->payload.size(); ++i)
+                _arr.push_back(NumberElement(_nums->payload[i], _nums->classes[i]));
+            _nums.reset();
+            _view.reset();
+            return;
+        }
         if (_ints.empty()) return;
         _arr.reserve(_ints.size());
         for (int64_t x : _ints) _arr.emplace_back(x);
@@ -115,6 +148,7 @@ private:
     std::string _s;
     std::vector<Value> _arr;
     std::vector<int64_t> _ints;
+    std::shared_ptr<const NumberArray> _nums;
     // Values of a packed array for const readers (std::atomic_load/store)
     mutable std::shared_ptr<const std::vector<Value>> _view;
     std::vector<std::pair<std::string, Value>> _obj;
@@ -128,6 +162,41 @@ private:
 // and the reader then parses the array itself.
 typedef bool (*IntArrayOffload)(const char* base, const uint32_t* seps, size_t nseps, std::vector<int64_t>* out);
 void SetIntArrayOffload(IntArrayOffload fn, size_t min_elems);
+
+// The same for arrays of numbers that are not all int64 (floats): tried on
+// the same separator run when the integer offload declined or its threshold
+// is not met, if the run has at least this offload's min_elems elements. fn
+// fills payload[n] and classes[n] (n = nseps - 1; the classes of
+// Value::NumberArray) and returns false unless every element is a number of
+// the RFC 8259 grammar; the reader then parses the array itself.
+typedef bool (*NumberArrayOffload)(const char* base, const uint32_t* seps, size_t nseps, uint64_t* payload,
+                                   uint8_t* classes);
+void SetNumberArrayOffload(NumberArrayOffload fn, size_t min_elems);
+
+// The host twin of the device number parser (gpu/json_kernels.hip
+// json_number_array_kernel): element i is the text between separators
+// seps[i] and seps[i+1] (exclusive), trimmed of JSON whitespace and
+// converted with base/decimal_to_double.h. An element that needs exact
+// arithmetic (more than 19 significant digits whose truncation does not
+// decide the rounding, or a text too long for a device lane) is converted
+// as Reader::number always did (std::from_chars / strtod) when `exact` is
+// set, and left as class 3 with payload 0 otherwise. Returns false, with
+// *bad_index (if given) the first offending element, when an element is not
+// a number of the RFC 8259 grammar.
+bool ParseNumberArray(const char* base, const uint32_t* seps, size_t nseps, uint64_t* payload, uint8_t* classes,
+                      bool exact = true, size_t* bad_index = nullptr);
+// One trimmed number of the RFC 8259 grammar, of any length, by the exact
+// route alone; false when the text is not in the grammar.
+bool ParseNumberExact(const char* b, const char* e, uint64_t* payload, uint8_t* cls);
+// Separator offsets of a flat number array for ParseNumberArray and the
+// device parser: of "[v,v,...]" (spaces around the brackets allowed) the
+// '[', every ',' and the ']'; of bare "v,v,...,v" every ',' between
+// 0xFFFFFFFF (a separator before the first byte) and n. Text below 4 GiB.
+void NumberArraySeparators(const char* text, size_t n, std::vector<uint32_t>* seps);
+// Test and benchmark hook: false makes the reader parse number arrays element
+// by element with std::from_chars, as it did before packed numbers (the DOM
+// is the same either way; only storage and speed differ). Default true.
+void SetPackedNumberArrays(bool on);
 
 // Returns false and sets *error on malformed input.
 bool Parse(const std::string& text, Value* out, std::string* error = nullptr);

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "base/decimal_to_double.h"
 #include "base/shortest_double.h"
 #include "base/util.h"
 
@@ -463,6 +464,26 @@ private:
         }
     }
 
+    // Packed numbers (json::Value::PackedNumbers) into a repeated float or
+    // double field without a Value per element, converted as scalar() does:
+    // an integer class through as_double()'s cast, a float field narrowed
+    // with (float). Every other field type takes the element loop, which
+    // reports what it always reported.
+    static bool bulk_numbers(const json::Value::NumberArray& nums, const FieldDescriptor* f, Message* m) {
+        const bool is_float = f->cpp_type() == CppType::FLOAT;
+        if (!is_float && f->cpp_type() != CppType::DOUBLE) return false;
+        for (size_t i = 0; i < nums.payload.size(); ++i) {
+            const uint64_t p = nums.payload[i];
+            double x;
+            if (nums.classes[i] == decimal_to_double::kInt64) x = (double)(int64_t)p;
+            else if (nums.classes[i] == decimal_to_double::kUInt64) x = (double)p;
+            else memcpy(&x, &p, sizeof(x));
+            if (is_float) Reflection::AddFloat(m, f, (float)x);
+            else Reflection::AddDouble(m, f, x);
+        }
+        return true;
+    }
+
     bool field(const json::Value& v, const FieldDescriptor* f, Message* m) {
         if (v.is_null()) {
             if (f->is_required()) {
@@ -478,6 +499,9 @@ private:
             }
             if (const std::vector<int64_t>* ints = v.packed_ints()) {
                 if (bulk_ints(*ints, f, m)) return true;
+            }
+            if (const json::Value::NumberArray* nums = v.packed_numbers()) {
+                if (bulk_numbers(*nums, f, m)) return true;
             }
             for (const json::Value& e : v.array()) {
                 if (f->cpp_type() == CppType::MESSAGE) {

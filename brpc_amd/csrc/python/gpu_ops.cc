@@ -18,6 +18,7 @@
 #include "gpu/gpu.h"
 #include "gpu/json_offload.h"
 #include "gpu/kernels.h"
+#include "json/json.h"
 
 namespace py = pybind11;
 using namespace mrpc;
@@ -336,6 +337,65 @@ void bind_gpu_ops(py::module_& g) {
         check(rc, "json_print_floats");
         return py::bytes(text);
     }, py::arg("values"), py::arg("n"), py::arg("kind"), py::arg("device") = 0);
+    // Number arrays as text in device (or pinned) memory -> values, all jobs
+    // in one launch (gpu::DeviceParseNumberArrays). Per job: text, seps
+    // (count + 1 uint32 offsets), count, mode (0 numbers: 8-byte payload at
+    // out and a class byte at classes; 1 float64; 2 float32), out, classes,
+    // redo (redo_cap uint32 slots). Returns [(err, first_bad, n_redo)].
+    g.def("device_json_parse_numbers", [](const std::vector<uintptr_t>& texts, const std::vector<uintptr_t>& seps,
+                                          const std::vector<uint64_t>& counts, const std::vector<uint32_t>& modes,
+                                          const std::vector<uintptr_t>& outs, const std::vector<uintptr_t>& classes,
+                                          const std::vector<uintptr_t>& redos, const std::vector<uint32_t>& redo_caps,
+                                          int device) {
+        const size_t n = counts.size();
+        if (texts.size() != n || seps.size() != n || modes.size() != n || outs.size() != n || classes.size() != n ||
+            redos.size() != n || redo_caps.size() != n)
+            throw std::invalid_argument("size mismatch");
+        std::vector<gpu::DeviceNumberParseJob> jobs(n);
+        for (size_t i = 0; i < n; ++i) {
+            jobs[i].text = (const char*)texts[i];
+            jobs[i].seps = (const uint32_t*)seps[i];
+            jobs[i].count = counts[i];
+            jobs[i].mode = modes[i];
+            jobs[i].out = (void*)outs[i];
+            jobs[i].classes = (uint8_t*)classes[i];
+            jobs[i].redo = (uint32_t*)redos[i];
+            jobs[i].redo_cap = redo_caps[i];
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceParseNumberArrays(jobs.data(), (int)jobs.size(), device);
+        }
+        check(rc, "device_json_parse_numbers");
+        py::list out;
+        for (const gpu::DeviceNumberParseJob& j : jobs) out.append(py::make_tuple(j.err, j.first_bad, j.n_redo));
+        return out;
+    }, py::arg("texts"), py::arg("seps"), py::arg("counts"), py::arg("modes"), py::arg("outs"), py::arg("classes"),
+       py::arg("redos"), py::arg("redo_caps"), py::arg("device") = 0);
+    // Host text "[v,v,...]" or "v,v,...,v" -> (payload, classes, n_redo)
+    // through the device (gpu::ParseNumbersOnDevice: pinned stage, one wait,
+    // redo elements repaired on the host); ValueError when the device
+    // declines (a malformed element or too many redo elements).
+    g.def("json_parse_numbers", [](py::bytes text, int device) {
+        const std::string t = text;
+        if (t.size() >= 0xFFFFFFFFull) throw std::invalid_argument("text must be below 4 GiB");
+        std::vector<uint32_t> seps;
+        json::NumberArraySeparators(t.data(), t.size(), &seps);
+        const size_t n = seps.size() - 1;
+        std::vector<uint64_t> payload(n);
+        std::string classes(n, '\0');
+        uint32_t n_redo = 0;
+        bool ok;
+        {
+            py::gil_scoped_release nogil;
+            ok = gpu::ParseNumbersOnDevice(t.data(), seps.data(), seps.size(), payload.data(),
+                                           reinterpret_cast<uint8_t*>(&classes[0]), device, &n_redo);
+        }
+        if (!ok) throw py::value_error("the device declined the array (malformed element or redo overflow)");
+        return py::make_tuple(py::bytes(reinterpret_cast<const char*>(payload.data()), n * 8), py::bytes(classes),
+                              n_redo);
+    }, py::arg("text"), py::arg("device") = 0);
     // Field table of a message already in device memory -> (nfields, fields)
     g.def("device_pb_scan", [](uintptr_t buf, uint64_t len, int device) {
         const void* p = (const void*)buf;

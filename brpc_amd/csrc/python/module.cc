@@ -7,6 +7,7 @@
 #include <unistd.h>
 
 #include "base/crc32c.h"
+#include "base/decimal_to_double.h"
 #include "builtin/cpu_profiler.h"
 #include "base/snappy.h"
 #include "base/flags.h"
@@ -20,6 +21,7 @@
 #include "gpu/json_offload.h"
 #include "gpu/codec_batch.h"
 #include "gpu/device_codec.h"
+#include "json/json.h"
 #include "json/json2pb.h"
 #include "pb/descriptor.h"
 #include "pb/parser.h"
@@ -485,6 +487,60 @@ PYBIND11_MODULE(_native, m) {
         json2pb::FormatFloatArray(aligned.data(), data.size() / eb, kind, &text);
         return py::bytes(text);
     }, py::arg("values"), py::arg("kind"));
+    // One JSON number (RFC 8259 grammar) to the double json::Reader makes of
+    // it, an integer literal converted as Value::as_double() does
+    // (base/decimal_to_double.h; the exact route where that does not decide)
+    m.def("json_parse_double", [](py::bytes text) {
+        const std::string t = text;
+        decimal_to_double::NumberResult r;
+        decimal_to_double::ParseJsonNumber(t.data(), t.data() + t.size(), &r);
+        if (r.cls == decimal_to_double::kNeedsExact &&
+            !json::ParseNumberExact(t.data(), t.data() + t.size(), &r.bits, &r.cls))
+            r.cls = decimal_to_double::kMalformed;
+        if (r.cls == decimal_to_double::kMalformed) throw std::invalid_argument("not a JSON number: " + t);
+        const uint64_t bits = decimal_to_double::NumberToDoubleBits(r);
+        double d;
+        memcpy(&d, &bits, sizeof(d));
+        return d;
+    });
+    // The host twin of the device number parser over a whole "[v,v,...]" or
+    // bare "v,v,...,v" text (json::ParseNumberArray): (payload, classes), 8
+    // bytes and a class byte per element (0 int64, 1 uint64, 2 double bits).
+    // exact=False leaves the elements a device lane would hand back as class
+    // 3 with payload 0. Raises ValueError naming the first malformed element.
+    m.def("json_parse_numbers", [](py::bytes text, bool exact) {
+        const std::string t = text;
+        if (t.size() >= 0xFFFFFFFFull) throw std::invalid_argument("text must be below 4 GiB");
+        std::vector<uint32_t> seps;
+        json::NumberArraySeparators(t.data(), t.size(), &seps);
+        const size_t n = seps.size() - 1;
+        std::vector<uint64_t> payload(n);
+        std::string classes(n, '\0');
+        size_t bad = 0;
+        if (!json::ParseNumberArray(t.data(), seps.data(), seps.size(), payload.data(),
+                                    reinterpret_cast<uint8_t*>(&classes[0]), exact, &bad))
+            throw py::value_error("element " + std::to_string(bad) + " is not a JSON number");
+        return py::make_tuple(py::bytes(reinterpret_cast<const char*>(payload.data()), n * 8), py::bytes(classes));
+    }, py::arg("text"), py::arg("exact") = true);
+    m.def("narrow_double_bits", [](uint64_t bits) { return decimal_to_double::NarrowDoubleBits(bits); });
+    m.def("json_max_device_number_chars", [] { return decimal_to_double::kMaxDeviceNumberChars; });
+    // json::Parse alone (the DOM is dropped): (ok, error). packed=False parses
+    // number arrays element by element, as before packed numbers.
+    m.def("json_parse_check", [](py::bytes text, bool packed) {
+        char* t = nullptr;  // read in place
+        Py_ssize_t tn = 0;
+        if (PyBytes_AsStringAndSize(text.ptr(), &t, &tn) != 0) throw py::error_already_set();
+        std::string err;
+        bool ok;
+        {
+            py::gil_scoped_release nogil;
+            json::Value v;
+            json::SetPackedNumberArrays(packed);
+            ok = json::Parse(t, (size_t)tn, &v, &err);
+            json::SetPackedNumberArrays(true);
+        }
+        return py::make_tuple(ok, err);
+    }, py::arg("text"), py::arg("packed") = true);
     m.def("json_to_pb_to_json", [](const std::string& type_name, py::bytes text) {
         const pb::Descriptor* d = pb::DescriptorPool::generated_pool()->FindMessageTypeByName(type_name);
         if (!d || !d->prototype) throw std::invalid_argument("unknown message type " + type_name);
@@ -809,7 +865,30 @@ PYBIND11_MODULE(_native, m) {
         d["int_arrays"] = s.int_arrays;
         d["int_array_fallbacks"] = s.int_array_fallbacks;
         d["sparse_skips"] = s.sparse_skips;
+        d["number_arrays"] = s.number_arrays;
+        d["number_elems"] = s.number_elems;
+        d["number_array_fallbacks"] = s.number_array_fallbacks;
+        d["number_redo_elems"] = s.number_redo_elems;
         return d;
+    });
+    // json::ParseWithIndex over a structural index (the uint32 positions of
+    // json_index_bytes as bytes) with whatever array offloads are installed;
+    // the DOM is dropped: (ok, error)
+    g.def("json_parse_with_index", [](py::bytes text, py::bytes index_u32) {
+        // read in place: a copy of a 20 MB body would show in what this is used to time
+        char *t = nullptr, *raw = nullptr;
+        Py_ssize_t tn = 0, rawn = 0;
+        if (PyBytes_AsStringAndSize(text.ptr(), &t, &tn) != 0 || PyBytes_AsStringAndSize(index_u32.ptr(), &raw, &rawn) != 0)
+            throw py::error_already_set();
+        if (((uintptr_t)raw & 3) != 0) throw std::invalid_argument("index must be 4-byte aligned");
+        std::string err;
+        bool ok;
+        {
+            py::gil_scoped_release nogil;
+            json::Value v;
+            ok = json::ParseWithIndex(t, (size_t)tn, reinterpret_cast<const uint32_t*>(raw), (size_t)rawn / 4, &v, &err);
+        }
+        return py::make_tuple(ok, err);
     });
     // host bytes -> structural positions through the device (tests)
     g.def("json_index_bytes", [](py::bytes b, int dev) {

@@ -88,3 +88,74 @@ def json_print_floats(values):
     if err:
         raise ValueError("json_print_floats: " + PRINT_ERRORS.get(err, "code %d" % err))
     return out[:length]
+
+
+_PARSE_MODES = {torch.float64: 1, torch.float32: 2}
+_REDO_CAP = 64
+
+
+def json_parse_floats(text, dtype=torch.float64):
+    """uint8 device tensor of JSON text ``v,v,...,v`` (or ``[v,v,...]``) ->
+    float64 / float32 device tensor, the inverse of ``json_print_floats``.
+    Every element is converted exactly as the host's json2pb converts it:
+    the correctly rounded double (``base/decimal_to_double.h``, the code the
+    host reader runs; an integer literal becomes the double of its value),
+    and for float32 ``(float)`` of that double. The text never leaves HBM
+    (``gpu::DeviceParseNumberArrays``); the separators are found with torch
+    ops on the device.
+
+    The rare elements a device lane does not decide (more than 19
+    significant digits whose truncation leaves the rounding open) are
+    fetched as text, converted with ``native.json_parse_double`` and written
+    back. Raises ValueError naming the first element that is not a number of
+    the RFC 8259 grammar (quoted ``"NaN"`` / ``"Infinity"`` among them).
+
+    The parser runs on a pool stream, not on torch's: the caller's current
+    stream is synchronized before the call, and the values are complete when
+    this returns."""
+    require_gpu_tensor(text, "text")
+    if text.dtype != torch.uint8:
+        raise TypeError("text must be uint8")
+    if dtype not in _PARSE_MODES:
+        raise TypeError("dtype must be float32 or float64, not %s" % dtype)
+    dev = text.device
+    t = text.contiguous().view(-1)
+    n = t.numel()
+    if n >= (1 << 32) - 1:
+        raise ValueError("json_parse_floats handles inputs below 4 GiB")
+    if n == 0:
+        return torch.empty(0, dtype=dtype, device=dev)
+    bracketed = n >= 2 and int(t[0]) == 0x5B and int(t[-1]) == 0x5D
+    commas = torch.nonzero(t == 0x2C).view(-1)
+    if bracketed and n == 2:
+        return torch.empty(0, dtype=dtype, device=dev)
+    first, last = (0, n - 1) if bracketed else (-1, n)  # -1: a separator before the first byte
+    seps64 = torch.cat([torch.tensor([first], dtype=torch.int64, device=dev), commas,
+                        torch.tensor([last], dtype=torch.int64, device=dev)])
+    # uint32 offsets in an int32 tensor (two's complement: -1 is 0xFFFFFFFF)
+    seps = torch.where(seps64 >= 1 << 31, seps64 - (1 << 32), seps64).to(torch.int32)
+    count = seps.numel() - 1
+    out = torch.zeros(count, dtype=dtype, device=dev)
+    redo = torch.zeros(_REDO_CAP, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        cap = _REDO_CAP
+        while True:
+            (err, first_bad, n_redo), = native.gpu.device_json_parse_numbers(
+                [t.data_ptr()], [seps.data_ptr()], [count], [_PARSE_MODES[dtype]], [out.data_ptr()], [0],
+                [redo.data_ptr()], [cap], dev.index or 0)
+            if err != 3:
+                break
+            cap = n_redo  # every listed element is repaired below: list them all
+            redo = torch.zeros(cap, dtype=torch.int32, device=dev)
+    if err == 1:
+        raise ValueError("json_parse_floats: element %d is not a JSON number" % first_bad)
+    if err:
+        raise ValueError("json_parse_floats: refused (bad arguments, code %d)" % err)
+    if n_redo:
+        idx = redo[:n_redo].to(torch.int64)
+        begins = (seps64[idx] + 1).tolist()
+        ends = seps64[idx + 1].tolist()
+        vals = [native.json_parse_double(bytes(t[b:e].cpu().numpy()).strip(b" \t\n\r")) for b, e in zip(begins, ends)]
+        out[idx] = torch.tensor(vals, dtype=torch.float64).to(dtype).to(dev)  # narrowed on the host
+    return out
