@@ -14,6 +14,7 @@
 #include "fiber/butex.h"
 #include "gpu/gpu.h"
 #include "gpu/hbm_pool.h"
+#include "gpu/scoped.h"
 
 DEFINE_bool(codec_fused, true,
             "run codec batches of compress blocks and decode pieces (<= 8 KiB) as one launch (then the pb scans, "
@@ -37,22 +38,6 @@ namespace {
 
 const int kMaxDev = 16;
 
-// A pinned host array the kernels read (job tables) or write (results);
-// grows, never shrinks, owned by one batch.
-template <typename T>
-struct PinnedArray {
-    T* p = nullptr;
-    size_t cap = 0;
-    bool reserve(size_t n) {
-        if (n <= cap) return true;
-        if (p) PinnedFree(p, cap * sizeof(T));
-        cap = std::max<size_t>(n, 64);
-        p = static_cast<T*>(PinnedAlloc(cap * sizeof(T)));
-        if (!p) cap = 0;
-        return p != nullptr;
-    }
-};
-
 struct CBatch {
     std::vector<CodecRequest*> reqs;
     std::vector<size_t> comp_first, decomp_first, stream_first, piece_first, scan_row, run_first;
@@ -64,10 +49,8 @@ struct CBatch {
     PinnedArray<PbMsgChunk> msg_chunks;
     PinnedArray<PbMsgResult> msg_res;
     PinnedArray<PbMsgFieldResult> msg_fres;
-    uint32_t* msg_prefix = nullptr;  // HBM: per-chunk encoded sizes, scanned, of the message builder
-    size_t msg_prefix_cap = 0;
-    uint64_t* msg_base = nullptr;  // HBM: per-field payload address
-    size_t msg_base_cap = 0;
+    HbmArray<uint32_t> msg_prefix;  // per-chunk encoded sizes, scanned, of the message builder
+    HbmArray<uint64_t> msg_base;    // per-field payload address
     std::vector<size_t> dec_first;
     PinnedArray<PbRunDecodeChunk> dec_jobs;
     PinnedArray<uint32_t> dec_counts;
@@ -77,20 +60,16 @@ struct CBatch {
     PinnedArray<SnappyJob> comp_jobs, decomp_jobs;
     PinnedArray<SnappyStream> stream_jobs;
     PinnedArray<int> stream_err, piece_err;
-    SnappyPiece* pieces = nullptr;  // HBM: written by the split kernel, read by the piece decoder
-    size_t pieces_cap = 0;
-    uint32_t* dec_prefix = nullptr;  // HBM: per-chunk counts, scanned, of the packed-run decoder
-    size_t dec_prefix_cap = 0;
+    HbmArray<SnappyPiece> pieces;   // written by the split kernel, read by the piece decoder
+    HbmArray<uint32_t> dec_prefix;  // per-chunk counts, scanned, of the packed-run decoder
     PinnedArray<uint32_t> comp_len, decomp_len;
     PinnedArray<int> comp_err, decomp_err;
     PinnedArray<PbScanJob> scan_jobs;
     PinnedArray<uint32_t> piece_group, group_pieces;  // fused launches: piece -> scan group, pieces per group
-    uint32_t* group_done = nullptr;                   // HBM counters, zero between launches
-    size_t group_done_cap = 0;
+    HbmArray<uint32_t> group_done;                    // zero between launches
     PinnedArray<uint64_t> scan_fields;
     PinnedArray<int32_t> scan_n;
-    void* scratch = nullptr;  // compress slots of blocks above 16 KiB
-    size_t scratch_bytes = 0;
+    HbmArray<char> scratch;  // compress slots of blocks above 16 KiB
     std::atomic<int>* butex = nullptr;
     hipEvent_t ev = nullptr;
     std::atomic<int> refs{0};
@@ -209,13 +188,7 @@ bool launch(CBatch* b, int device) {
         !b->msg_chunks.reserve(nmchunks)) {
         return false;
     }
-    if (npieces > b->pieces_cap) {
-        if (b->pieces) HbmFree(b->pieces, b->pieces_cap * sizeof(SnappyPiece), device);
-        const size_t cap = std::max<size_t>(npieces, 256);
-        b->pieces = static_cast<SnappyPiece*>(HbmAlloc(cap * sizeof(SnappyPiece), device));
-        b->pieces_cap = b->pieces ? cap : 0;
-        if (!b->pieces) return false;
-    }
+    if (!b->pieces.reserve(npieces, 256, device)) return false;
     for (size_t i = 0; i < b->reqs.size(); ++i) {
         const CodecRequest* r = b->reqs[i];
         std::copy(r->comp.begin(), r->comp.end(), b->comp_jobs.p + b->comp_first[i]);
@@ -254,35 +227,14 @@ bool launch(CBatch* b, int device) {
             first += st.max_pieces;
         }
     }
-    if (ndec > b->dec_prefix_cap) {
-        if (b->dec_prefix) HbmFree(b->dec_prefix, b->dec_prefix_cap * sizeof(uint32_t), device);
-        const size_t cap = std::max<size_t>(ndec, 1024);
-        b->dec_prefix = static_cast<uint32_t*>(HbmAlloc(cap * sizeof(uint32_t), device));
-        b->dec_prefix_cap = b->dec_prefix ? cap : 0;
-        if (!b->dec_prefix) return false;
+    if (!b->dec_prefix.reserve(ndec, 1024, device)) return false;
+    if (nmsgs && (!b->msg_prefix.reserve(nmchunks + 1, 1024, device) ||
+                  !b->msg_base.reserve(std::max<size_t>(nmfields, 1), 256, device))) {
+        return false;
     }
-    if (nmsgs && nmchunks + 1 > b->msg_prefix_cap) {
-        if (b->msg_prefix) HbmFree(b->msg_prefix, b->msg_prefix_cap * sizeof(uint32_t), device);
-        const size_t cap = std::max<size_t>(nmchunks + 1, 1024);
-        b->msg_prefix = static_cast<uint32_t*>(HbmAlloc(cap * sizeof(uint32_t), device));
-        b->msg_prefix_cap = b->msg_prefix ? cap : 0;
-        if (!b->msg_prefix) return false;
-    }
-    if (nmsgs && std::max<size_t>(nmfields, 1) > b->msg_base_cap) {
-        if (b->msg_base) HbmFree(b->msg_base, b->msg_base_cap * sizeof(uint64_t), device);
-        const size_t cap = std::max<size_t>(nmfields, 256);
-        b->msg_base = static_cast<uint64_t*>(HbmAlloc(cap * sizeof(uint64_t), device));
-        b->msg_base_cap = b->msg_base ? cap : 0;
-        if (!b->msg_base) return false;
-    }
-    if (ncomp && SnappyCompressUsesScratch(comp_max)) {
-        const size_t need = ncomp * SnappyCompressScratchPerBlock();
-        if (need > b->scratch_bytes) {
-            if (b->scratch) HbmFree(b->scratch, b->scratch_bytes, device);
-            b->scratch = HbmAlloc(need, device);
-            b->scratch_bytes = b->scratch ? need : 0;
-        }
-        if (!b->scratch) return false;
+    if (ncomp && SnappyCompressUsesScratch(comp_max) &&
+        !b->scratch.reserve(ncomp * SnappyCompressScratchPerBlock(), 1, device)) {
+        return false;
     }
     // one fused launch when the batch is codec work only: compress blocks
     // and headerless pieces that fit the one-launch kernels (the pb scans
@@ -305,104 +257,104 @@ bool launch(CBatch* b, int device) {
         }
     }
     if (scan_in_kernel && (!b->piece_group.reserve(nhpieces) || !b->group_pieces.reserve(nscan))) return false;
-    int prev = 0;
-    hipGetDevice(&prev);
-    if (prev != device) hipSetDevice(device);
-    hipStream_t s = PoolStream(device);
-    b->ev = AcquireEvent();
-    int rc = (s && b->ev) ? 0 : -1;
-    if (rc == 0 && fused) {
-        if (scan_in_kernel) {
-            if (nscan > b->group_done_cap) {
-                if (b->group_done) HbmFree(b->group_done, b->group_done_cap * sizeof(uint32_t), device);
-                const size_t cap = std::max<size_t>(nscan, 256);
-                b->group_done = static_cast<uint32_t*>(HbmAlloc(cap * sizeof(uint32_t), device));
-                b->group_done_cap = b->group_done ? cap : 0;
-            }
-            // zeroed before EVERY launch, ordered before it on the same
-            // stream: a launch that stopped partway (a fault) must not leave
-            // counters that start the next launch's scans early
-            if (!b->group_done || hipMemsetAsync(b->group_done, 0, nscan * sizeof(uint32_t), s) != hipSuccess) {
-                rc = -1;
-            }
-            for (size_t p = 0; p < nhpieces; ++p) b->piece_group.p[p] = kFusedNoGroup;
-            for (size_t i = 0; i < b->reqs.size(); ++i) {
-                const CodecRequest* r = b->reqs[i];
-                for (size_t k = 0; k < r->scans.size(); ++k) {
-                    const size_t g = b->scan_row[i] + k;
-                    b->group_pieces.p[g] = r->scan_piece_count[k];
-                    for (uint32_t q = 0; q < r->scan_piece_count[k]; ++q)
-                        b->piece_group.p[b->piece_first[i] + r->scan_piece_first[k] + q] = (uint32_t)g;
+    hipStream_t s = nullptr;
+    int rc = -1;
+    {
+        ScopedDevice on(device);
+        s = PoolStream(device);
+        b->ev = AcquireEvent();
+        rc = (s && b->ev) ? 0 : -1;
+        if (rc == 0 && fused) {
+            if (scan_in_kernel) {
+                b->group_done.reserve(nscan, 256, device);
+                // zeroed before EVERY launch, ordered before it on the same
+                // stream: a launch that stopped partway (a fault) must not leave
+                // counters that start the next launch's scans early
+                if (!b->group_done.p || hipMemsetAsync(b->group_done.p, 0, nscan * sizeof(uint32_t), s) != hipSuccess) {
+                    rc = -1;
+                }
+                for (size_t p = 0; p < nhpieces; ++p) b->piece_group.p[p] = kFusedNoGroup;
+                for (size_t i = 0; i < b->reqs.size(); ++i) {
+                    const CodecRequest* r = b->reqs[i];
+                    for (size_t k = 0; k < r->scans.size(); ++k) {
+                        const size_t g = b->scan_row[i] + k;
+                        b->group_pieces.p[g] = r->scan_piece_count[k];
+                        for (uint32_t q = 0; q < r->scan_piece_count[k]; ++q)
+                            b->piece_group.p[b->piece_first[i] + r->scan_piece_first[k] + q] = (uint32_t)g;
+                    }
                 }
             }
+            FusedCodecArgs fa;
+            fa.comp = b->comp_jobs.p;
+            fa.ncomp = (int)ncomp;
+            fa.comp_len = b->comp_len.p;
+            fa.comp_err = b->comp_err.p;
+            fa.pieces = b->piece_jobs.p;
+            fa.npieces = (int)nhpieces;
+            fa.piece_err = b->piece_job_err.p;
+            fa.piece_group = scan_in_kernel ? b->piece_group.p : nullptr;
+            fa.scans = b->scan_jobs.p;
+            fa.group_pieces = b->group_pieces.p;
+            fa.group_done = b->group_done.p;
+            fa.scan_fields = b->scan_fields.p;
+            fa.scan_n = b->scan_n.p;
+            fa.max_fields = kCodecScanFields;
+            fa.max_ulen = std::max(ncomp ? comp_max : 1u, nhpieces ? hpiece_max : 1u);
+            if (rc == 0) rc = LaunchCodecWaves(fa, s);
+            g_fused_launches.fetch_add(1, std::memory_order_relaxed);
+            ncomp = nhpieces = 0;  // nothing left for the per-stage sequence below but (maybe) the scans
+            if (scan_in_kernel) nscan = 0;
         }
-        FusedCodecArgs fa;
-        fa.comp = b->comp_jobs.p;
-        fa.ncomp = (int)ncomp;
-        fa.comp_len = b->comp_len.p;
-        fa.comp_err = b->comp_err.p;
-        fa.pieces = b->piece_jobs.p;
-        fa.npieces = (int)nhpieces;
-        fa.piece_err = b->piece_job_err.p;
-        fa.piece_group = scan_in_kernel ? b->piece_group.p : nullptr;
-        fa.scans = b->scan_jobs.p;
-        fa.group_pieces = b->group_pieces.p;
-        fa.group_done = b->group_done;
-        fa.scan_fields = b->scan_fields.p;
-        fa.scan_n = b->scan_n.p;
-        fa.max_fields = kCodecScanFields;
-        fa.max_ulen = std::max(ncomp ? comp_max : 1u, nhpieces ? hpiece_max : 1u);
-        if (rc == 0) rc = LaunchCodecWaves(fa, s);
-        g_fused_launches.fetch_add(1, std::memory_order_relaxed);
-        ncomp = nhpieces = 0;  // nothing left for the per-stage sequence below but (maybe) the scans
-        if (scan_in_kernel) nscan = 0;
-    }
-    if (rc == 0 && nruns) rc = LaunchPbRunEncode(b->run_jobs.p, (int)nruns, b->run_err.p, s);
-    g_run_chunks.fetch_add((int64_t)nruns, std::memory_order_relaxed);
-    if (rc == 0 && nmsgs) {
-        PbMsgTables mt;
-        mt.msgs = b->msg_jobs.p;
-        mt.nmsgs = (int)nmsgs;
-        mt.fields = b->msg_fields.p;
-        mt.nfields = (int)nmfields;
-        mt.chunks = b->msg_chunks.p;
-        mt.nchunks = (int)nmchunks;
-        mt.prefix = b->msg_prefix;
-        mt.base = b->msg_base;
-        mt.res = b->msg_res.p;
-        mt.fres = b->msg_fres.p;
-        rc = LaunchPbMsgEncode(mt, s);
-    }
-    g_msg_chunks.fetch_add((int64_t)nmchunks, std::memory_order_relaxed);
-    if (rc == 0 && !h2d.empty()) rc = LaunchBatchedCopy(h2d.data(), (int)h2d.size(), s);
-    if (rc == 0 && ncomp) {
-        rc = LaunchSnappyCompress(b->comp_jobs.p, (int)ncomp, comp_max, b->scratch, b->comp_len.p, b->comp_err.p, s);
-    }
-    if (rc == 0 && ndecomp) {
-        rc = LaunchSnappyDecompress(b->decomp_jobs.p, (int)ndecomp, decomp_max, b->decomp_len.p, b->decomp_err.p, s);
-    }
-    if (rc == 0 && nhpieces) {
-        rc = LaunchSnappyDecompressPieces(b->piece_jobs.p, (int)nhpieces, 0, std::min(hpiece_max, kSnappyMaxBlock),
-                                          b->piece_job_err.p, s);
-    }
-    if (rc == 0 && nstreams) {
-        // cut on the device, then small pieces (many waves per CU) and the
-        // 64 KiB fragments of CPU encoders in a second launch
-        const uint32_t small = std::min(piece_limit, kSnappyMaxBlock);
-        rc = LaunchSnappySplit(b->stream_jobs.p, (int)nstreams, small, b->pieces, b->stream_err.p, s);
-        if (rc == 0) rc = LaunchSnappyDecompressPieces(b->pieces, (int)npieces, 0, small, b->piece_err.p, s);
-        if (rc == 0 && small < kSnappyMaxBlock) {
-            rc = LaunchSnappyDecompressPieces(b->pieces, (int)npieces, small, kSnappyMaxBlock, b->piece_err.p, s);
+        if (rc == 0 && nruns) rc = LaunchPbRunEncode(b->run_jobs.p, (int)nruns, b->run_err.p, s);
+        g_run_chunks.fetch_add((int64_t)nruns, std::memory_order_relaxed);
+        if (rc == 0 && nmsgs) {
+            PbMsgTables mt;
+            mt.msgs = b->msg_jobs.p;
+            mt.nmsgs = (int)nmsgs;
+            mt.fields = b->msg_fields.p;
+            mt.nfields = (int)nmfields;
+            mt.chunks = b->msg_chunks.p;
+            mt.nchunks = (int)nmchunks;
+            mt.prefix = b->msg_prefix.p;
+            mt.base = b->msg_base.p;
+            mt.res = b->msg_res.p;
+            mt.fres = b->msg_fres.p;
+            rc = LaunchPbMsgEncode(mt, s);
         }
+        g_msg_chunks.fetch_add((int64_t)nmchunks, std::memory_order_relaxed);
+        if (rc == 0 && !h2d.empty()) rc = LaunchBatchedCopy(h2d.data(), (int)h2d.size(), s);
+        if (rc == 0 && ncomp) {
+            rc = LaunchSnappyCompress(b->comp_jobs.p, (int)ncomp, comp_max, b->scratch.p, b->comp_len.p, b->comp_err.p,
+                                      s);
+        }
+        if (rc == 0 && ndecomp) {
+            rc = LaunchSnappyDecompress(b->decomp_jobs.p, (int)ndecomp, decomp_max, b->decomp_len.p, b->decomp_err.p,
+                                        s);
+        }
+        if (rc == 0 && nhpieces) {
+            rc = LaunchSnappyDecompressPieces(b->piece_jobs.p, (int)nhpieces, 0, std::min(hpiece_max, kSnappyMaxBlock),
+                                              b->piece_job_err.p, s);
+        }
+        if (rc == 0 && nstreams) {
+            // cut on the device, then small pieces (many waves per CU) and the
+            // 64 KiB fragments of CPU encoders in a second launch
+            const uint32_t small = std::min(piece_limit, kSnappyMaxBlock);
+            rc = LaunchSnappySplit(b->stream_jobs.p, (int)nstreams, small, b->pieces.p, b->stream_err.p, s);
+            if (rc == 0) rc = LaunchSnappyDecompressPieces(b->pieces.p, (int)npieces, 0, small, b->piece_err.p, s);
+            if (rc == 0 && small < kSnappyMaxBlock) {
+                rc = LaunchSnappyDecompressPieces(b->pieces.p, (int)npieces, small, kSnappyMaxBlock, b->piece_err.p, s);
+            }
+        }
+        if (rc == 0 && nscan) {
+            rc = LaunchPbScanPtrs(b->scan_jobs.p, (int64_t)nscan, kCodecScanFields, b->scan_fields.p, b->scan_n.p, s);
+        }
+        if (rc == 0 && !d2h.empty()) rc = LaunchBatchedCopy(d2h.data(), (int)d2h.size(), s);
+        if (rc == 0 && ndec) {
+            rc = LaunchPbRunDecode(b->dec_jobs.p, (int)ndec, b->dec_counts.p, b->dec_prefix.p, b->dec_err.p, s);
+        }
+        g_dec_chunks.fetch_add((int64_t)ndec, std::memory_order_relaxed);
+        if (rc == 0 && hipEventRecord(b->ev, s) != hipSuccess) rc = -1;
     }
-    if (rc == 0 && nscan) {
-        rc = LaunchPbScanPtrs(b->scan_jobs.p, (int64_t)nscan, kCodecScanFields, b->scan_fields.p, b->scan_n.p, s);
-    }
-    if (rc == 0 && !d2h.empty()) rc = LaunchBatchedCopy(d2h.data(), (int)d2h.size(), s);
-    if (rc == 0 && ndec) rc = LaunchPbRunDecode(b->dec_jobs.p, (int)ndec, b->dec_counts.p, b->dec_prefix, b->dec_err.p, s);
-    g_dec_chunks.fetch_add((int64_t)ndec, std::memory_order_relaxed);
-    if (rc == 0 && hipEventRecord(b->ev, s) != hipSuccess) rc = -1;
-    if (prev != device) hipSetDevice(prev);
     g_launches.fetch_add(1, std::memory_order_relaxed);
     if (rc != 0) {
         // kernels already queued may still read the tables: wait them out

@@ -14,6 +14,7 @@
 #include "fiber/butex.h"
 #include "gpu/gpu.h"
 #include "gpu/hbm_pool.h"
+#include "gpu/scoped.h"
 #include "base/time.h"
 #include "base/util.h"
 #include "rpc/span.h"
@@ -66,8 +67,7 @@ struct Batch {
     std::vector<int> msg_of;        // CRC message of each segment (want_crc)
     int nmsg = 0;
     bool want_crc = false;          // some submitter asked for checksums
-    uint32_t* crc_host = nullptr;   // per-segment CRC32C, stored by the kernel (pinned)
-    size_t crc_cap = 0;
+    PinnedArray<uint32_t> crc_host;  // per-message CRC32C, stored by the kernel
     std::atomic<int>* butex = nullptr;
     hipEvent_t ev = nullptr;
     std::atomic<int> refs{0};
@@ -159,20 +159,12 @@ bool submit_resident(Batch* b, int device) {
                                          (uint32_t)std::max(10, FLAGS_copy_engine_resident_max_us),
                                          (uint32_t)FLAGS_copy_engine_resident_groups);
     if (!ring) return false;
-    if (b->want_crc && b->crc_cap < (size_t)b->nmsg) {
-        PinnedFree(b->crc_host, b->crc_cap * sizeof(uint32_t));
-        b->crc_cap = std::max<size_t>((size_t)b->nmsg, 64);
-        b->crc_host = static_cast<uint32_t*>(PinnedAlloc(b->crc_cap * sizeof(uint32_t)));
-        if (!b->crc_host) return false;
-    }
-    int prev = 0;
-    hipGetDevice(&prev);
-    if (prev != device) hipSetDevice(device);
+    if (b->want_crc && !b->crc_host.reserve((size_t)b->nmsg)) return false;
+    ScopedDevice on(device);  // nothing below waits
     uint64_t first = 0, last = 0;
     const int rc = ResidentSubmit(ring, b->segs.data(), b->want_crc ? b->msg_of.data() : nullptr, (int)b->segs.size(),
-                                  b->want_crc ? b->crc_host : nullptr, &first, &last);
+                                  b->want_crc ? b->crc_host.p : nullptr, &first, &last);
     b->t_issued = monotonic_us();
-    if (prev != device) hipSetDevice(prev);
     g_launches.fetch_add(1, std::memory_order_relaxed);
     if (rc != 0) {
         LOG_EVERY_SECOND(ERROR) << "resident copy worker refused a batch of " << b->segs.size() << " segments";
@@ -188,9 +180,7 @@ bool submit_resident(Batch* b, int device) {
 // batch's waiters are released with an error.
 void launch(Batch* b, int device) {
     if (submit_resident(b, device)) return;
-    int prev = 0;
-    hipGetDevice(&prev);
-    if (prev != device) hipSetDevice(device);
+    ScopedDevice on(device);  // nothing below waits
     hipStream_t s = PoolStream(device);
     b->ev = AcquireEvent();
     int rc = (s && b->ev) ? 0 : -1;
@@ -204,16 +194,12 @@ void launch(Batch* b, int device) {
     if (rc == 0 && b->want_crc) {
         // fused pull + checksum: the kernel stores the CRCs straight into
         // pinned host memory (one launch, no memset, no D2H copy)
-        if (b->crc_cap < (size_t)b->nmsg) {
-            PinnedFree(b->crc_host, b->crc_cap * sizeof(uint32_t));
-            b->crc_cap = std::max<size_t>((size_t)b->nmsg, 64);
-            b->crc_host = static_cast<uint32_t*>(PinnedAlloc(b->crc_cap * sizeof(uint32_t)));
-        }
+        b->crc_host.reserve((size_t)b->nmsg);
         uint64_t launch_bytes = 0;
         for (const Segment& g : b->segs) launch_bytes += g.len;
         const bool mfma = FLAGS_copy_engine_crc_mfma && launch_bytes >= (uint64_t)FLAGS_copy_engine_crc_mfma_min_bytes;
-        if (!b->crc_host ||
-            LaunchBatchedCopyCrc32cMessages(b->segs.data(), b->msg_of.data(), (int)n, b->crc_host, s, done, mfma) != 0) {
+        if (!b->crc_host.p || LaunchBatchedCopyCrc32cMessages(b->segs.data(), b->msg_of.data(), (int)n, b->crc_host.p,
+                                                              s, done, mfma) != 0) {
             rc = -1;
         }
     } else if (rc == 0) {
@@ -224,7 +210,6 @@ void launch(Batch* b, int device) {
     const bool record = !b->has_word || FLAGS_copy_engine_word_event;
     if (rc == 0 && record && hipEventRecord(b->ev, s) != hipSuccess) rc = -1;
     b->t_issued = monotonic_us();
-    if (prev != device) hipSetDevice(prev);
     g_launches.fetch_add(1, std::memory_order_relaxed);
     if (rc != 0) {
         LOG_EVERY_SECOND(ERROR) << "batched copy launch of " << b->segs.size() << " segments failed on device " << device;
@@ -346,9 +331,9 @@ int BatchedCopy(const Segment* segs, int n, int device, uint32_t* crcs, bool fol
     }
     if (rc == 0 && crcs) {
         if (fold) {
-            crcs[0] = mine->crc_host[first_msg];
+            crcs[0] = mine->crc_host.p[first_msg];
         } else {
-            memcpy(crcs, mine->crc_host + first_msg, sizeof(uint32_t) * (size_t)n);
+            memcpy(crcs, mine->crc_host.p + first_msg, sizeof(uint32_t) * (size_t)n);
             if (fold_crc) {  // too many segments to fold on the device
                 uint32_t c = crcs[0];
                 for (int i = 1; i < n; ++i) c = crc32c::Combine(c, crcs[i], segs[i].len);

@@ -11,6 +11,7 @@
 #include "gpu/gpu.h"
 #include "gpu/hbm_pool.h"
 #include "gpu/kernels.h"
+#include "gpu/scoped.h"
 #include "policy/device_payload.h"
 
 DEFINE_int32(device_payload_block_kb, 2,
@@ -218,18 +219,16 @@ int DeviceDecodePackedRuns(DevicePackedRun* runs, int n, int device) {
     if (req.dec_runs.empty()) return 0;
     // every run's final byte comes back with the batch (the host cannot read
     // HBM): one still carrying a continuation bit ends inside a varint
-    uint8_t* tail = static_cast<uint8_t*>(PinnedAlloc((size_t)n));
-    if (!tail) return -1;
+    PinnedBlock tail_block((size_t)n);
+    if (!tail_block) return -1;
+    uint8_t* tail = tail_block.as<uint8_t>();
     for (int i = 0; i < n; ++i) {
         tail[i] = 0;
         if (first[i + 1] > first[i]) {
             req.d2h.push_back(Segment{static_cast<const uint8_t*>(runs[i].src) + runs[i].len - 1, tail + i, 1});
         }
     }
-    if (RunCodecRequest(&req, device) != 0) {
-        PinnedFree(tail, (size_t)n);
-        return -1;
-    }
+    if (RunCodecRequest(&req, device) != 0) return -1;
     for (int i = 0; i < n; ++i) {
         DevicePackedRun& r = runs[i];
         if (r.err || r.len == 0) continue;
@@ -248,7 +247,6 @@ int DeviceDecodePackedRuns(DevicePackedRun* runs, int n, int device) {
         g_run_bytes.fetch_add((int64_t)r.len, std::memory_order_relaxed);
         g_run_elems.fetch_add((int64_t)count, std::memory_order_relaxed);
     }
-    PinnedFree(tail, (size_t)n);
     return 0;
 }
 
@@ -409,23 +407,21 @@ int BuildDeviceMessage(DeviceMessageField* fields, int n, Buf* out, int device) 
     }
     // an arena block even for an empty message: the job needs a destination
     const size_t cap = (size_t)std::max<uint64_t>(worst, 16);
-    void* dst = HbmAlloc(cap, device);
+    HbmBlock dst(cap, device);
     if (!dst) return -1;
     DeviceMessageJob job;
     job.fields = fields;
     job.nfields = n;
-    job.dst = dst;
+    job.dst = dst.p;
     job.cap = cap;
     const int rc = DeviceBuildMessages(&job, 1, device);
-    if (rc != 0 || job.err != 0 || job.len == 0) {
-        HbmFree(dst, cap, device);
-        return rc != 0 ? -1 : job.err;
-    }
+    if (rc != 0 || job.err != 0 || job.len == 0) return rc != 0 ? -1 : job.err;
     ArenaBlock* a = new ArenaBlock{cap, device};
-    if (AppendDevice(out, dst, (size_t)job.len, device, free_arena_block, a) != 0) {
-        free_arena_block(dst, a);
+    if (AppendDevice(out, dst.p, (size_t)job.len, device, free_arena_block, a) != 0) {
+        delete a;
         return -1;
     }
+    dst.release();  // the Buf block owns it now
     return 0;
 }
 

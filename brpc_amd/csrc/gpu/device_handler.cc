@@ -8,14 +8,11 @@
 #include "gpu/copy_engine.h"
 #include "gpu/gpu.h"
 #include "gpu/hbm_pool.h"
+#include "gpu/scoped.h"
 #include "fiber/fiber.h"
 
 namespace mrpc {
 namespace gpu {
-
-namespace {
-void pinned_deleter(void* p, void* arg) { PinnedFree(p, (size_t)reinterpret_cast<uintptr_t>(arg)); }
-}  // namespace
 
 namespace {
 
@@ -44,14 +41,11 @@ int ProcessToPinnedWithCrc(const Buf& in, Buf* out, uint32_t* crc, int device) {
     const size_t n = in.size();
     *crc = 0;
     if (n == 0) return 0;
-    char* h = static_cast<char*>(PinnedAlloc(n));
+    PinnedBlock h(n);
     if (!h) return kNoPinnedBounce;
-    const int rc = copy_with_crc(in, h, crc, device);
-    if (rc != 0) {
-        PinnedFree(h, n);
-        return rc;
-    }
-    out->append_user_data(h, n, pinned_deleter, reinterpret_cast<void*>((uintptr_t)n), MemKind::PINNED);
+    const int rc = copy_with_crc(in, h.p, crc, device);
+    if (rc != 0) return rc;
+    h.give_to(out);
     return 0;
 }
 
@@ -115,20 +109,19 @@ int copy_with_crc(const Buf& in, char* d, uint32_t* crc, int device) {
     for (size_t i = 0; i < in.backing_block_num(); ++i) {
         if (in.ref_at(i).block->kind == MemKind::HOST) pageable += in.ref_at(i).length;
     }
-    char* bounce = pageable ? static_cast<char*>(PinnedAlloc(pageable)) : nullptr;
+    PinnedBlock bounce(pageable);
     if (pageable && !bounce) return kNoPinnedBounce;
     size_t off = 0, boff = 0;
     for (size_t i = 0; i < in.backing_block_num(); ++i) {
         const BlockRef& r = in.ref_at(i);
         const char* src = r.block->data + r.offset;
         if (r.block->kind == MemKind::HOST) {
-            memcpy(bounce + boff, src, r.length);
-            src = bounce + boff;
+            memcpy(bounce.p + boff, src, r.length);
+            src = bounce.p + boff;
             boff += r.length;
         } else if (!IsHostAccessible(r.block->kind) && r.block->device != device &&
                    ArenaOffset(src, r.block->device) < 0) {
             // another device's non-arena block: not mapped here
-            if (bounce) PinnedFree(bounce, pageable);
             return kForeignBlock;
         }
         segs.push_back(Segment{src, d ? d + off : nullptr, r.length});
@@ -138,7 +131,6 @@ int copy_with_crc(const Buf& in, char* d, uint32_t* crc, int device) {
     // one message: the device folds the segment CRCs into the request's
     std::vector<uint32_t> crcs(segs.size());
     const int rc = BatchedCopy(segs.data(), (int)segs.size(), device, crcs.data(), /*fold_crc=*/true);
-    if (bounce) PinnedFree(bounce, pageable);
     if (rc != 0) return kDeviceBatchFailed;
     *crc = crcs[0];
     (void)n;
@@ -174,23 +166,20 @@ int StageToPinnedHost(const Buf& in, Buf* out) {
         out->append(in);
         return 0;
     }
-    char* h = static_cast<char*>(PinnedAlloc(dbytes));
+    PinnedBlock h(dbytes);
     if (!h) return -1;
     std::vector<Segment> segs;
     size_t off = 0;
     for (size_t i = 0; i < in.backing_block_num(); ++i) {
         const BlockRef& r = in.ref_at(i);
         if (!IsHostAccessible(r.block->kind)) {
-            segs.push_back(Segment{r.block->data + r.offset, h + off, r.length});
+            segs.push_back(Segment{r.block->data + r.offset, h.p + off, r.length});
             off += r.length;
         }
     }
-    if (BatchedCopy(segs.data(), (int)segs.size(), device) != 0) {
-        PinnedFree(h, dbytes);
-        return -1;
-    }
+    if (BatchedCopy(segs.data(), (int)segs.size(), device) != 0) return -1;
     Buf staged;
-    staged.append_user_data(h, dbytes, pinned_deleter, reinterpret_cast<void*>((uintptr_t)dbytes), MemKind::PINNED);
+    h.give_to(&staged);
     off = 0;
     for (size_t i = 0; i < in.backing_block_num(); ++i) {
         const BlockRef& r = in.ref_at(i);

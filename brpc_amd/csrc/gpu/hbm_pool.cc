@@ -11,6 +11,7 @@
 #include "base/flags.h"
 #include "base/logging.h"
 #include "gpu/gpu.h"
+#include "gpu/scoped.h"
 
 DEFINE_int32(hbm_arena_mb, 16384,
              "IPC-exportable HBM arena per device for RPC payload blocks (MiB; 288 GB HBM3E per MI355X)");
@@ -110,11 +111,11 @@ bool arena_init(int device, std::string* error) {
         const size_t bytes = (size_t)std::max(64, FLAGS_hbm_arena_mb) << 20;
         void* p = Malloc(bytes, device, error);
         if (!p) return;
-        int prev = 0;
-        hipGetDevice(&prev);
-        if (prev != device) hipSetDevice(device);
-        const hipError_t r = hipIpcGetMemHandle(&a.handle, p);
-        if (prev != device) hipSetDevice(prev);
+        hipError_t r;
+        {
+            ScopedDevice on(device);
+            r = hipIpcGetMemHandle(&a.handle, p);
+        }
         if (r != hipSuccess) {
             if (error) *error = std::string("hipIpcGetMemHandle: ") + hipGetErrorString(r);
             Free(p);

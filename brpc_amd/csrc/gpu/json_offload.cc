@@ -21,6 +21,7 @@
 #include "gpu/gpu.h"
 #include "gpu/hbm_pool.h"
 #include "gpu/kernels.h"
+#include "gpu/scoped.h"
 #include "gpu/snappy_offload.h"
 #include "json/json.h"
 #include "json/json2pb.h"
@@ -57,25 +58,6 @@ namespace {
 int g_device = -1;
 std::atomic<int64_t> g_bodies{0}, g_bytes{0}, g_failures{0};
 std::atomic<int64_t> g_sparse{0};
-
-struct Hbm {
-    void* p = nullptr;
-    size_t n = 0;
-    int dev = -1;
-    Hbm(size_t bytes, int d) : p(HbmAlloc(bytes, d)), n(bytes), dev(d) {}
-    ~Hbm() {
-        if (p) HbmFree(p, n, dev);
-    }
-};
-
-struct Pinned {
-    void* p = nullptr;
-    size_t n = 0;
-    explicit Pinned(size_t bytes) : p(PinnedAlloc(bytes)), n(bytes) {}
-    ~Pinned() {
-        if (p) PinnedFree(p, n);
-    }
-};
 
 // Structural characters per KiB in three 1 KiB windows (start, middle,
 // end). A body that is mostly one long string (the http_json_64KB leg)
@@ -123,67 +105,43 @@ int JsonIndex(const char* data, size_t n, std::vector<uint32_t>* out, int device
     if (n == 0) return 0;
     if (n > 0xFFFFFFFFull || device < 0) return -1;
     if (FLAGS_json_index_direct_host) {
-        Pinned body(n), pos(n * sizeof(uint32_t)), meta(16);  // every byte could be a position
-        Hbm scratch(JsonIndexScratchBytes(n), device);
-        if (!body.p || !pos.p || !meta.p || !scratch.p) return -1;
+        PinnedBlock body(n), pos(n * sizeof(uint32_t)), meta(16);  // every byte could be a position
+        HbmBlock scratch(JsonIndexScratchBytes(n), device);
+        if (!body || !pos || !meta || !scratch) return -1;
         memcpy(body.p, data, n);
-        uint64_t* count = static_cast<uint64_t*>(meta.p);
+        uint64_t* count = meta.as<uint64_t>();
         int* err = reinterpret_cast<int*>(count + 1);
-        int prev = 0;
-        hipGetDevice(&prev);
-        if (prev != device) hipSetDevice(device);
-        hipStream_t s = PoolStream(device);
-        int rc = s ? LaunchJsonIndex(static_cast<const uint8_t*>(body.p), n, static_cast<uint32_t*>(pos.p), n, count,
-                                     err, scratch.p, s)
-                   : -1;
-        const int wrc = s ? SyncStream(s) : -1;  // never free buffers a launched kernel may still use
-        if (prev != device) hipSetDevice(prev);
-        if (rc != 0 || wrc != 0 || *err != 0 || *count > n) return -1;
-        const uint32_t* p = static_cast<const uint32_t*>(pos.p);
-        out->assign(p, p + *count);
+        const int rc = RunOnPoolStream(device, [&](hipStream_t s) {
+            return LaunchJsonIndex(body.as<uint8_t>(), n, pos.as<uint32_t>(), n, count, err, scratch.p, s);
+        });
+        if (rc != 0 || *err != 0 || *count > n) return -1;
+        out->assign(pos.as<uint32_t>(), pos.as<uint32_t>() + *count);
         return 0;
     }
     // every byte could be a position; the count decides what comes back
-    Hbm in(n, device), pos(n * sizeof(uint32_t), device), scratch(JsonIndexScratchBytes(n), device);
-    Pinned bounce(n), meta(16);
-    if (!in.p || !pos.p || !scratch.p || !bounce.p || !meta.p) return -1;
+    HbmBlock in(n, device), pos(n * sizeof(uint32_t), device), scratch(JsonIndexScratchBytes(n), device);
+    PinnedBlock bounce(n), meta(16);
+    if (!in || !pos || !scratch || !bounce || !meta) return -1;
     memcpy(bounce.p, data, n);
-    uint64_t* count = static_cast<uint64_t*>(meta.p);
+    uint64_t* count = meta.as<uint64_t>();
     int* err = reinterpret_cast<int*>(count + 1);
-    int prev = 0;
-    hipGetDevice(&prev);
-    if (prev != device) hipSetDevice(device);
-    hipStream_t s = PoolStream(device);
-    int rc = -1;
-    if (s) {
+    int rc = RunOnPoolStream(device, [&](hipStream_t s) {
         Segment seg{bounce.p, in.p, n};
-        rc = LaunchBatchedCopy(&seg, 1, s);
-        if (rc == 0) {
-            rc = LaunchJsonIndex(static_cast<const uint8_t*>(in.p), n, static_cast<uint32_t*>(pos.p), n, count, err,
-                                 scratch.p, s);
-        }
-        const int wrc = SyncStream(s);  // never free buffers a launched kernel may still use
-        if (rc == 0) rc = wrc;
-        if (rc == 0 && *err != 0) rc = -1;
-        if (rc == 0 && *count > 0) {
-            const size_t bytes = (size_t)*count * sizeof(uint32_t);
-            Pinned back(bytes);
-            if (!back.p) {
-                rc = -1;
-            } else {
-                Segment seg2{pos.p, back.p, bytes};
-                rc = LaunchBatchedCopy(&seg2, 1, s);
-                const int w2 = SyncStream(s);
-                if (rc == 0) rc = w2;
-                if (rc == 0) {
-                    const uint32_t* p = static_cast<const uint32_t*>(back.p);
-                    out->assign(p, p + *count);
-                }
-            }
-        }
-    }
-    if (prev != device) hipSetDevice(prev);
-    return rc == 0 ? 0 : -1;
+        if (LaunchBatchedCopy(&seg, 1, s) != 0) return -1;
+        return LaunchJsonIndex(in.as<uint8_t>(), n, pos.as<uint32_t>(), n, count, err, scratch.p, s);
+    });
+    if (rc != 0 || *err != 0) return -1;
+    if (*count == 0) return 0;
+    const size_t bytes = (size_t)*count * sizeof(uint32_t);
+    PinnedBlock back(bytes);
+    if (!back) return -1;
+    rc = RunOnPoolStream(device, [&](hipStream_t s) {
+        Segment seg{pos.p, back.p, bytes};
+        return LaunchBatchedCopy(&seg, 1, s);
+    });
+    if (rc != 0) return -1;
+    out->assign(back.as<uint32_t>(), back.as<uint32_t>() + *count);
+    return 0;
 }
 
 uint64_t FloatPrintWorstCaseBytes(uint64_t count) {
@@ -195,7 +153,7 @@ int DevicePrintFloatArrays(DeviceFloatPrintJob* jobs, int n, int device) {
     if (!jobs || device < 0) return -1;
     // refuse what must not reach a kernel; count the chunks of the rest
     uint64_t nchunks = 0;
-    int live = 0;
+    std::vector<int> live;  // the jobs that go to the device, in order
     for (int i = 0; i < n; ++i) {
         DeviceFloatPrintJob& j = jobs[i];
         j.len = 0;
@@ -208,25 +166,24 @@ int DevicePrintFloatArrays(DeviceFloatPrintJob* jobs, int n, int device) {
             continue;
         }
         nchunks += (j.count + kJsonFloatChunkElems - 1) / kJsonFloatChunkElems;
-        ++live;
+        live.push_back(i);
     }
-    if (live == 0) return 0;
+    if (live.empty()) return 0;
     if (nchunks > 0x3FFFFFFFull) return -1;  // the tables are indexed with int
-    const size_t jobs_bytes = (size_t)live * sizeof(JsonFloatJob);
+    const int nlive = (int)live.size();
+    const size_t jobs_bytes = live.size() * sizeof(JsonFloatJob);
     const size_t chunks_bytes = (size_t)nchunks * sizeof(JsonFloatChunk);
-    const size_t res_bytes = (size_t)live * sizeof(JsonFloatResult);
-    Pinned tables(jobs_bytes + chunks_bytes + res_bytes);
-    Hbm prefix((size_t)(nchunks + 1) * sizeof(uint32_t), device);
-    Hbm digits((size_t)nchunks * kJsonFloatChunkElems * sizeof(shortest_double::Decimal), device);
-    if (!tables.p || !prefix.p || !digits.p) return -1;
-    JsonFloatJob* tj = static_cast<JsonFloatJob*>(tables.p);
-    JsonFloatChunk* tc = reinterpret_cast<JsonFloatChunk*>(static_cast<char*>(tables.p) + jobs_bytes);
-    JsonFloatResult* tr = reinterpret_cast<JsonFloatResult*>(static_cast<char*>(tables.p) + jobs_bytes + chunks_bytes);
+    const size_t res_bytes = live.size() * sizeof(JsonFloatResult);
+    PinnedBlock tables(jobs_bytes + chunks_bytes + res_bytes);
+    HbmBlock prefix((size_t)(nchunks + 1) * sizeof(uint32_t), device);
+    HbmBlock digits((size_t)nchunks * kJsonFloatChunkElems * sizeof(shortest_double::Decimal), device);
+    if (!tables || !prefix || !digits) return -1;
+    JsonFloatJob* tj = tables.as<JsonFloatJob>();
+    JsonFloatChunk* tc = reinterpret_cast<JsonFloatChunk*>(tables.p + jobs_bytes);
+    JsonFloatResult* tr = reinterpret_cast<JsonFloatResult*>(tables.p + jobs_bytes + chunks_bytes);
     uint32_t ci = 0;
-    int k = 0;
-    for (int i = 0; i < n; ++i) {
-        const DeviceFloatPrintJob& j = jobs[i];
-        if (j.count == 0 || j.err != 0) continue;
+    for (int k = 0; k < nlive; ++k) {
+        const DeviceFloatPrintJob& j = jobs[live[k]];
         const size_t eb = j.kind == kJsonFloat32 ? 4 : 8;
         const uint32_t nc = (uint32_t)((j.count + kJsonFloatChunkElems - 1) / kJsonFloatChunkElems);
         tj[k] = JsonFloatJob{static_cast<uint8_t*>(j.dst), j.cap, ci, nc};
@@ -239,31 +196,19 @@ int DevicePrintFloatArrays(DeviceFloatPrintJob* jobs, int n, int device) {
                                         c + 1 == nc ? 1u : 0u};
         }
         ci += nc;
-        ++k;
     }
     JsonFloatTables t;
     t.jobs = tj;
-    t.njobs = live;
+    t.njobs = nlive;
     t.chunks = tc;
     t.nchunks = (int)nchunks;
-    t.prefix = static_cast<uint32_t*>(prefix.p);
+    t.prefix = prefix.as<uint32_t>();
     t.digits = digits.p;
     t.res = tr;
-    int prev = 0;
-    hipGetDevice(&prev);
-    if (prev != device) hipSetDevice(device);
-    hipStream_t s = PoolStream(device);
-    const int rc = s ? LaunchJsonFloatPrint(t, s) : -1;
-    const int wrc = s ? SyncStream(s) : -1;  // never free buffers a launched kernel may still use
-    if (prev != device) hipSetDevice(prev);
-    if (rc != 0 || wrc != 0) return -1;
-    k = 0;
-    for (int i = 0; i < n; ++i) {
-        DeviceFloatPrintJob& j = jobs[i];
-        if (j.count == 0 || j.err != 0) continue;
-        j.len = tr[k].len;
-        j.err = tr[k].err;
-        ++k;
+    if (RunOnPoolStream(device, [&](hipStream_t s) { return LaunchJsonFloatPrint(t, s); }) != 0) return -1;
+    for (int k = 0; k < nlive; ++k) {
+        jobs[live[k]].len = tr[k].len;
+        jobs[live[k]].err = tr[k].err;
     }
     return 0;
 }
@@ -278,8 +223,8 @@ int PrintFloatsOnDevice(const void* values, size_t n, uint32_t kind, std::string
     const size_t eb = kind == kJsonFloat32 ? 4 : 8;
     const uint64_t cap = FloatPrintWorstCaseBytes(n);
     if (cap > 0xFFFFFFFFull) return -1;
-    Pinned stage(n * eb), text((size_t)cap);
-    if (!stage.p || !text.p) return -1;
+    PinnedBlock stage(n * eb), text((size_t)cap);
+    if (!stage || !text) return -1;
     memcpy(stage.p, values, n * eb);
     DeviceFloatPrintJob job;
     job.src = stage.p;
@@ -288,7 +233,7 @@ int PrintFloatsOnDevice(const void* values, size_t n, uint32_t kind, std::string
     job.dst = text.p;
     job.cap = cap;
     if (DevicePrintFloatArrays(&job, 1, device) != 0 || job.err != 0 || job.len > cap) return -1;
-    out->assign(static_cast<const char*>(text.p), (size_t)job.len);
+    out->assign(text.p, (size_t)job.len);
     return 0;
 }
 
@@ -297,7 +242,7 @@ int DeviceParseNumberArrays(DeviceNumberParseJob* jobs, int n, int device) {
     if (!jobs || device < 0) return -1;
     // refuse what must not reach a kernel; count the blocks of the rest
     uint64_t nblocks = 0;
-    int live = 0;
+    std::vector<int> live;  // the jobs that go to the device, in order
     for (int i = 0; i < n; ++i) {
         DeviceNumberParseJob& j = jobs[i];
         j.n_redo = 0;
@@ -313,42 +258,33 @@ int DeviceParseNumberArrays(DeviceNumberParseJob* jobs, int n, int device) {
             continue;
         }
         nblocks += (j.count + 255) / 256;
-        ++live;
+        live.push_back(i);
     }
-    if (live == 0) return 0;
+    if (live.empty()) return 0;
     if (nblocks > 0x7FFFFFFFull) return -1;  // one grid
-    Pinned tables((size_t)live * (sizeof(JsonNumberJob) + sizeof(JsonNumberResult)));
-    Hbm counters((size_t)live * sizeof(JsonNumberResult), device);
-    if (!tables.p || !counters.p) return -1;
-    JsonNumberJob* tj = static_cast<JsonNumberJob*>(tables.p);
-    JsonNumberResult* tr = reinterpret_cast<JsonNumberResult*>(tj + live);
+    const int nlive = (int)live.size();
+    PinnedBlock tables(live.size() * (sizeof(JsonNumberJob) + sizeof(JsonNumberResult)));
+    HbmBlock counters(live.size() * sizeof(JsonNumberResult), device);
+    if (!tables || !counters) return -1;
+    JsonNumberJob* tj = tables.as<JsonNumberJob>();
+    JsonNumberResult* tr = reinterpret_cast<JsonNumberResult*>(tj + nlive);
     uint32_t block = 0;
-    int k = 0;
-    for (int i = 0; i < n; ++i) {
-        const DeviceNumberParseJob& j = jobs[i];
-        if (j.count == 0 || j.err != 0) continue;
+    for (int k = 0; k < nlive; ++k) {
+        const DeviceNumberParseJob& j = jobs[live[k]];
         tj[k] = JsonNumberJob{j.text, j.seps, j.out, j.classes, j.redo, (uint32_t)j.count, j.mode, j.redo_cap, block};
         tr[k] = JsonNumberResult{0xFFFFFFFFu, 0};
         block += (uint32_t)((j.count + 255) / 256);
-        ++k;
     }
-    int prev = 0;
-    hipGetDevice(&prev);
-    if (prev != device) hipSetDevice(device);
-    hipStream_t s = PoolStream(device);
-    const int rc = s ? LaunchJsonNumberArrays(tj, live, block, static_cast<JsonNumberResult*>(counters.p), tr, s) : -1;
-    const int wrc = s ? SyncStream(s) : -1;  // never free buffers a launched kernel may still use
-    if (prev != device) hipSetDevice(prev);
-    if (rc != 0 || wrc != 0) return -1;
-    k = 0;
-    for (int i = 0; i < n; ++i) {
-        DeviceNumberParseJob& j = jobs[i];
-        if (j.count == 0 || j.err != 0) continue;
+    const int rc = RunOnPoolStream(device, [&](hipStream_t s) {
+        return LaunchJsonNumberArrays(tj, nlive, block, counters.as<JsonNumberResult>(), tr, s);
+    });
+    if (rc != 0) return -1;
+    for (int k = 0; k < nlive; ++k) {
+        DeviceNumberParseJob& j = jobs[live[k]];
         j.first_bad = tr[k].bad;
         j.n_redo = tr[k].n_redo;
         if (j.first_bad != 0xFFFFFFFFu) j.err = 1;
         else if (j.n_redo > j.redo_cap) j.err = 3;
-        ++k;
     }
     return 0;
 }
@@ -370,19 +306,19 @@ bool ParseNumbersOnDevice(const char* base, const uint32_t* seps, size_t nseps, 
     const uint32_t lo = seps[0] + 1, hi = seps[nseps - 1];
     if (hi < lo) return false;
     const size_t vals_bytes = n * sizeof(uint64_t);
-    Pinned text((size_t)(hi - lo) + 1), sep(nseps * sizeof(uint32_t)),
+    PinnedBlock text((size_t)(hi - lo) + 1), sep(nseps * sizeof(uint32_t)),
         vals(vals_bytes + kRedoCap * sizeof(uint32_t) + n);
-    if (!text.p || !sep.p || !vals.p) return false;
+    if (!text || !sep || !vals) return false;
     memcpy(text.p, base + lo, hi - lo);
-    uint32_t* sp = static_cast<uint32_t*>(sep.p);
+    uint32_t* sp = sep.as<uint32_t>();
     for (size_t i = 0; i < nseps; ++i) sp[i] = seps[i] - lo;  // the first becomes 0xFFFFFFFF
     DeviceNumberParseJob job;
-    job.text = static_cast<const char*>(text.p);
+    job.text = text.p;
     job.seps = sp;
     job.count = n;
     job.mode = kJsonParseNumbers;
     job.out = vals.p;
-    job.redo = reinterpret_cast<uint32_t*>(static_cast<char*>(vals.p) + vals_bytes);
+    job.redo = reinterpret_cast<uint32_t*>(vals.p + vals_bytes);
     job.redo_cap = kRedoCap;
     job.classes = reinterpret_cast<uint8_t*>(job.redo + kRedoCap);
     if (DeviceParseNumberArrays(&job, 1, device) != 0 || job.err != 0) return false;
@@ -434,15 +370,6 @@ bool array_offload(const void* values, size_t n, uint32_t kind, std::string* tex
 
 std::atomic<int64_t> g_int_arrays{0}, g_int_array_fallbacks{0};
 
-struct PinnedTmp {
-    void* p = nullptr;
-    size_t n = 0;
-    explicit PinnedTmp(size_t bytes) : p(PinnedAlloc(bytes)), n(bytes) {}
-    ~PinnedTmp() {
-        if (p) PinnedFree(p, n);
-    }
-};
-
 // json2pb integer arrays (SURVEY K6 parse half): the array's text and its
 // separators go to pinned memory, json_int_array_kernel parses one element
 // per lane, one fiber-friendly wait.
@@ -451,28 +378,21 @@ bool int_array_offload(const char* base, const uint32_t* seps, size_t nseps, std
     if (dev < 0 || nseps < 2) return false;
     const uint32_t lo = seps[0], hi = seps[nseps - 1];
     const size_t n = nseps - 1;
-    PinnedTmp text(hi - lo + 1), sep(nseps * sizeof(uint32_t)), vals(n * sizeof(int64_t) + 64);
-    if (!text.p || !sep.p || !vals.p) return false;
+    PinnedBlock text(hi - lo + 1), sep(nseps * sizeof(uint32_t)), vals(n * sizeof(int64_t) + 64);
+    if (!text || !sep || !vals) return false;
     memcpy(text.p, base + lo, hi - lo + 1);
-    uint32_t* sp = static_cast<uint32_t*>(sep.p);
+    uint32_t* sp = sep.as<uint32_t>();
     for (size_t i = 0; i < nseps; ++i) sp[i] = seps[i] - lo;
-    int32_t* bad = reinterpret_cast<int32_t*>(static_cast<char*>(vals.p) + n * sizeof(int64_t));
+    int32_t* bad = reinterpret_cast<int32_t*>(vals.as<int64_t>() + n);
     *bad = 0;
-    int prev = 0;
-    hipGetDevice(&prev);
-    if (prev != dev) hipSetDevice(dev);
-    hipStream_t s = PoolStream(dev);
-    int rc = s ? LaunchJsonIntArray(static_cast<const char*>(text.p), sp, (uint32_t)n,
-                                    static_cast<int64_t*>(vals.p), bad, s)
-               : -1;
-    const int wrc = s ? SyncStream(s) : -1;  // buffers stay until the kernel is done
-    if (prev != dev) hipSetDevice(prev);
-    if (rc != 0 || wrc != 0 || *bad != 0) {
+    const int rc = RunOnPoolStream(dev, [&](hipStream_t s) {
+        return LaunchJsonIntArray(text.p, sp, (uint32_t)n, vals.as<int64_t>(), bad, s);
+    });
+    if (rc != 0 || *bad != 0) {
         g_int_array_fallbacks.fetch_add(1, std::memory_order_relaxed);
         return false;
     }
-    const int64_t* v = static_cast<const int64_t*>(vals.p);
-    out->assign(v, v + n);
+    out->assign(vals.as<int64_t>(), vals.as<int64_t>() + n);
     g_int_arrays.fetch_add(1, std::memory_order_relaxed);
     return true;
 }

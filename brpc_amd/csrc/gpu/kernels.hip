@@ -27,6 +27,7 @@
 
 #include "base/crc32c.h"
 #include "gpu/kernels.h"
+#include "gpu/scoped.h"
 
 namespace mrpc {
 namespace gpu {
@@ -1625,9 +1626,7 @@ ResidentRing* ResidentRingFor(int device, uint32_t idle_us, uint32_t max_us, uin
     if (device < 0 || device >= 64) return nullptr;
     std::lock_guard<std::mutex> g(g_resident_mu);
     if (g_resident[device]) return g_resident[device];
-    int prev = 0;
-    hipGetDevice(&prev);
-    if (prev != device) hipSetDevice(device);
+    ScopedDevice on(device);
     ResidentRing* r = new ResidentRing;
     r->device = device;
     int khz = 0;
@@ -1653,7 +1652,6 @@ ResidentRing* ResidentRingFor(int device, uint32_t idle_us, uint32_t max_us, uin
              hipMemset(r->scratch, 0, sizeof(uint32_t) * 2 * kInlineSegments * kResidentSlots) == hipSuccess &&
              hipDeviceSynchronize() == hipSuccess;
     }
-    if (prev != device) hipSetDevice(prev);
     if (!ok) return nullptr;  // leaks the partial ring; the engine falls back to launches
     g_resident[device] = r;
     return r;

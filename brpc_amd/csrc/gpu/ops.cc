@@ -6,6 +6,7 @@
 #include "base/crc32c.h"
 #include "gpu/hbm_pool.h"
 #include "gpu/kernels.h"
+#include "gpu/scoped.h"
 
 namespace mrpc {
 namespace gpu {
@@ -14,9 +15,6 @@ int Crc32cDevice(const void* const* ptrs, const uint64_t* lens, int n, uint32_t*
     if (n <= 0) return 0;
     if (Init(device) != 0) return -1;
     if (device < 0) device = CurrentDevice();
-    int prev = 0;
-    hipGetDevice(&prev);
-    if (prev != device) hipSetDevice(device);
     // one device allocation: [starts n][lens n][scratch n+1][out n (u32)]
     std::vector<uint64_t> desc(2 * (size_t)n);
     uint64_t total = 0, maxlen = 0;
@@ -27,26 +25,20 @@ int Crc32cDevice(const void* const* ptrs, const uint64_t* lens, int n, uint32_t*
         if (lens[i] > maxlen) maxlen = lens[i];
     }
     const size_t desc_bytes = desc.size() * sizeof(uint64_t);
-    const size_t bytes = desc_bytes + Crc32cScratchBytes(n) + sizeof(uint32_t) * n;
-    int rc = -1;
     // pooled scratch: a hipFree here would synchronise the whole device
-    char* mem = static_cast<char*>(HbmAlloc(bytes, device));
-    hipStream_t s = PoolStream(device);
-    if (mem && s) {
-        uint64_t* d_starts = reinterpret_cast<uint64_t*>(mem);
-        uint64_t* d_lens = d_starts + n;
-        void* scratch = mem + desc_bytes;
-        uint32_t* out_dev = reinterpret_cast<uint32_t*>(mem + desc_bytes + Crc32cScratchBytes(n));
-        if (hipMemcpyAsync(d_starts, desc.data(), desc_bytes, hipMemcpyHostToDevice, s) == hipSuccess &&
+    HbmBlock mem(desc_bytes + Crc32cScratchBytes(n) + sizeof(uint32_t) * n, device);
+    if (!mem) return -1;
+    uint64_t* d_starts = mem.as<uint64_t>();
+    uint64_t* d_lens = d_starts + n;
+    void* scratch = mem.as<char>() + desc_bytes;
+    uint32_t* out_dev = reinterpret_cast<uint32_t*>(mem.as<char>() + desc_bytes + Crc32cScratchBytes(n));
+    return RunOnPoolStream(device, [&](hipStream_t s) {
+        const bool queued =
+            hipMemcpyAsync(d_starts, desc.data(), desc_bytes, hipMemcpyHostToDevice, s) == hipSuccess &&
             LaunchCrc32cSegments(d_starts, d_lens, n, total, maxlen, out_dev, scratch, s) == 0 &&
-            hipMemcpyAsync(out_host, out_dev, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s) == hipSuccess) {
-            rc = SyncStream(s);
-        }
-    }
-    if (mem && rc != 0 && s) SyncStream(s);  // never recycle scratch a launch may still use
-    HbmFree(mem, bytes, device);
-    if (prev != device) hipSetDevice(prev);
-    return rc;
+            hipMemcpyAsync(out_host, out_dev, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s) == hipSuccess;
+        return queued ? 0 : -1;
+    });
 }
 
 int Crc32cOfBuf(const Buf& b, uint32_t* out, int device) {

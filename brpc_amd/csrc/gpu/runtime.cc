@@ -20,6 +20,7 @@
 #include "fiber/fiber.h"
 #include "gpu/hbm_pool.h"
 #include "gpu/kernels.h"
+#include "gpu/scoped.h"
 #include "rdma/rdma.h"
 
 DEFINE_bool(pinned_coherent, true,
@@ -454,16 +455,13 @@ bool AcquireDoneWord(int device, DoneWord* out, uint32_t* slot) {
     if (!d.init) {
         d.init = true;
         const uint32_t n = (uint32_t)std::max(64, FLAGS_gpu_done_word_slots);
-        int prev = 0;
-        hipGetDevice(&prev);
-        if (prev != device) hipSetDevice(device);
+        ScopedDevice on(device);
         void* c = nullptr;
         if (hipMalloc(&c, n * sizeof(uint32_t)) == hipSuccess && hipMemset(c, 0, n * sizeof(uint32_t)) == hipSuccess &&
             hipDeviceSynchronize() == hipSuccess) {
             d.counters = static_cast<uint32_t*>(c);
             d.words = static_cast<uint64_t*>(HostMallocPinned(n * 4 * sizeof(uint64_t)));
         }
-        if (prev != device) hipSetDevice(prev);
         if (d.counters && d.words) {
             memset(d.words, 0, n * 4 * sizeof(uint64_t));
             for (uint32_t i = n; i > 0; --i) d.free.push_back(i - 1);
@@ -508,12 +506,9 @@ void* Malloc(size_t n, int device, std::string* error) {
         if (error) *error = "no HIP device available";
         return nullptr;
     }
-    int prev = 0;
-    hipGetDevice(&prev);
-    if (prev != device) hipSetDevice(device);
+    ScopedDevice on(device);
     void* p = nullptr;
     hipError_t r = hipMalloc(&p, n ? n : 1);
-    if (prev != device) hipSetDevice(prev);
     if (r != hipSuccess) {
         if (error) *error = std::string("hipMalloc failed: ") + hipGetErrorString(r);
         return nullptr;

@@ -45,6 +45,7 @@
 #include "gpu/gpu.h"
 #include "gpu/hbm_pool.h"
 #include "gpu/kernels.h"
+#include "gpu/scoped.h"
 #include "pb/descriptor.h"
 #include "pb/message.h"
 #include "rpc/compress.h"
@@ -85,43 +86,6 @@ namespace {
 
 int g_device = -1;
 std::atomic<int64_t> g_comp_calls{0}, g_decomp_calls{0}, g_fallbacks{0};
-
-void pinned_deleter(void* p, void* arg) { PinnedFree(p, (size_t)reinterpret_cast<uintptr_t>(arg)); }
-
-// A pinned host buffer owned by a Buf block (kind PINNED).
-struct PinnedBuf {
-    char* p = nullptr;
-    size_t n = 0;
-    explicit PinnedBuf(size_t bytes) : p(bytes ? static_cast<char*>(PinnedAlloc(bytes)) : nullptr), n(bytes) {}
-    ~PinnedBuf() {
-        if (p) PinnedFree(p, n);
-    }
-    PinnedBuf(const PinnedBuf&) = delete;
-    PinnedBuf& operator=(PinnedBuf&& o) noexcept {
-        if (this != &o) {
-            if (p) PinnedFree(p, n);
-            p = o.p;
-            n = o.n;
-            o.p = nullptr;
-        }
-        return *this;
-    }
-    // hand ownership to *b as one block
-    void give_to(Buf* b) {
-        b->append_user_data(p, n, pinned_deleter, reinterpret_cast<void*>((uintptr_t)n), MemKind::PINNED);
-        p = nullptr;
-    }
-};
-
-struct HbmTmp {
-    void* p = nullptr;
-    size_t n = 0;
-    int dev = -1;
-    HbmTmp(size_t bytes, int d) : p(bytes ? HbmAlloc(bytes, d) : nullptr), n(bytes), dev(d) {}
-    ~HbmTmp() {
-        if (p) HbmFree(p, n, dev);
-    }
-};
 
 int varint_len(uint64_t v) {
     int n = 1;
@@ -203,7 +167,7 @@ struct RunCollector : public pb::PackedRunSink {
 
 // The runs' values copied into one pinned buffer (the kernel cannot read
 // pageable vectors) and cut into device chunks.
-bool stage_runs(const RunCollector& col, PinnedBuf* stage, std::vector<PbRunChunk>* chunks) {
+bool stage_runs(const RunCollector& col, PinnedBlock* stage, std::vector<PbRunChunk>* chunks) {
     size_t off = 0;
     for (const pb::PackedRun& r : col.runs) {
         char* v = stage->p + off;
@@ -232,10 +196,10 @@ std::atomic<int64_t> g_unpack_runs{0}, g_unpack_fallbacks{0};
 // Decodes packed runs whose bytes are device-readable (pinned) into one
 // pinned array per call: chunks of every run in one codec request.
 // Returns false when nothing could be decoded on the device.
-bool decode_runs(std::vector<pb::PackedRunIn>* runs, PinnedBuf* out, int device) {
+bool decode_runs(std::vector<pb::PackedRunIn>* runs, PinnedBlock* out, int device) {
     size_t cap = 0;
     for (const pb::PackedRunIn& r : *runs) cap += ((r.len * r.elem_bytes) + 15) & ~(size_t)15;
-    *out = PinnedBuf(cap ? cap : 1);
+    *out = PinnedBlock(cap ? cap : 1);
     if (!out->p) return false;
     CodecRequest req;
     std::vector<size_t> first_chunk;
@@ -284,7 +248,7 @@ bool decode_runs(std::vector<pb::PackedRunIn>* runs, PinnedBuf* out, int device)
 }
 
 struct DeviceRunDecoder : public pb::PackedRunDecoder {
-    PinnedBuf out{1};
+    PinnedBlock out{1};
     int calls = 0;  // runs handed to the device by this parse
     size_t min_bytes() const override { return (size_t)std::max(1, FLAGS_gpu_pb_unpack_min_bytes); }
     void Decode(std::vector<pb::PackedRunIn>* runs) override {
@@ -311,8 +275,8 @@ bool gpu_compress(const Buf& in, Buf* out, const std::vector<PbRunChunk>* runs =
     const bool direct = FLAGS_gpu_snappy_direct_host && in.all_host_accessible();
     const bool one_pinned = in.backing_block_num() == 1 && in.ref_at(0).block->kind == MemKind::PINNED;
     const size_t pageable = direct ? 0 : pageable_bytes(in);
-    HbmTmp raw(direct ? 0 : n, dev);
-    PinnedBuf flat(direct && !one_pinned ? n : 1), bounce(pageable ? pageable : 1), comp(nblk * cap);
+    HbmBlock raw(direct ? 0 : n, dev);
+    PinnedBlock flat(direct && !one_pinned ? n : 1), bounce(pageable ? pageable : 1), comp(nblk * cap);
     if ((!direct && !raw.p) || !flat.p || !bounce.p || !comp.p) return false;
     CodecRequest req;
     const char* src;
@@ -498,8 +462,8 @@ bool gpu_decompress(const Buf& in, Buf* out, PbIndex* index = nullptr) {
     const bool direct = host_cut && FLAGS_gpu_snappy_direct_host;
     const bool one_pinned = in.backing_block_num() == 1 && in.ref_at(0).block->kind == MemKind::PINNED;
     const size_t pageable = direct ? 0 : pageable_bytes(in);
-    PinnedBuf bounce(pageable ? pageable : 1), dst(total), cflat(direct && !one_pinned ? in.size() : 1);
-    HbmTmp dcomp(direct ? 0 : in.size(), dev), dbody(index && !direct ? total : 0, dev);
+    PinnedBlock bounce(pageable ? pageable : 1), dst(total), cflat(direct && !one_pinned ? in.size() : 1);
+    HbmBlock dcomp(direct ? 0 : in.size(), dev), dbody(index && !direct ? total : 0, dev);
     if (!bounce.p || !dst.p || !cflat.p || (!direct && !dcomp.p) || (index && !direct && !dbody.p)) return false;
     char* out_base = index && !direct ? static_cast<char*>(dbody.p) : dst.p;
     CodecRequest req;
@@ -659,7 +623,7 @@ bool offload(const Buf& in, Buf* out, bool compress) {
 // kernel reads the body (SURVEY K2 on the path).
 bool pack_offload(const pb::Message& msg, size_t n, Buf* out) {
     if (g_device < 0 || n == 0 || !FLAGS_gpu_snappy_direct_host) return false;
-    PinnedBuf body(n);
+    PinnedBlock body(n);
     if (!body.p) return false;
     RunCollector col;
     pb::PackedRunSink* prev = pb::SetThreadPackedRunSink(FLAGS_gpu_pb_pack_min_elems > 0 ? &col : nullptr);
@@ -668,8 +632,8 @@ bool pack_offload(const pb::Message& msg, size_t n, Buf* out) {
     if ((size_t)(e - reinterpret_cast<uint8_t*>(body.p)) != n) return false;
     std::vector<PbRunChunk> chunks;
     bool device_runs = !col.runs.empty();
-    PinnedBuf stage(0);  // values of the runs, only when there are any
-    if (device_runs) stage = PinnedBuf(col.value_bytes + 16 * col.runs.size());
+    PinnedBlock stage(0);  // values of the runs, only when there are any
+    if (device_runs) stage = PinnedBlock(col.value_bytes + 16 * col.runs.size());
     if (device_runs && (!stage.p || !stage_runs(col, &stage, &chunks))) {
         for (const pb::PackedRun& r : col.runs) pb::EncodePackedRunOnHost(r);
         device_runs = false;
@@ -784,7 +748,7 @@ int EncodeRunOnDevice(const void* values, size_t n, uint32_t kind, uint32_t form
         chunks.push_back(ch);
         total += cb;
     }
-    PinnedBuf stage(n * eb), dst(total ? total : 1);
+    PinnedBlock stage(n * eb), dst(total ? total : 1);
     if (!stage.p || !dst.p) return -1;
     memcpy(stage.p, values, n * eb);
     size_t off = 0;
@@ -807,7 +771,7 @@ int DecodeRunOnDevice(const void* bytes, size_t len, uint32_t kind, std::string*
     out->clear();
     if (kind > PB_RUN_BOOL || device < 0 || Init(device) != 0) return -1;
     if (len == 0) return 0;
-    PinnedBuf in(len);
+    PinnedBlock in(len);
     if (!in.p) return -1;
     memcpy(in.p, bytes, len);
     std::vector<pb::PackedRunIn> runs(1);
@@ -819,7 +783,7 @@ int DecodeRunOnDevice(const void* bytes, size_t len, uint32_t kind, std::string*
                                            pb::FieldType::INT64,  pb::FieldType::UINT64, pb::FieldType::SINT64,
                                            pb::FieldType::BOOL};
     runs[0].type = kTypes[kind];
-    PinnedBuf dec(1);
+    PinnedBlock dec(1);
     if (!decode_runs(&runs, &dec, device) || !runs[0].values) return -1;
     out->assign(static_cast<const char*>(runs[0].values), runs[0].count * runs[0].elem_bytes);
     return 0;

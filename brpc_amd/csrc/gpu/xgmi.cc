@@ -24,6 +24,7 @@
 #include "gpu/gpu.h"
 #include "gpu/hbm_pool.h"
 #include "gpu/kernels.h"
+#include "gpu/scoped.h"
 #include "mrpc/proto/options.pb.h"
 #include "mrpc/proto/rpc_meta.pb.h"
 #include "net/socket.h"
@@ -282,9 +283,7 @@ std::shared_ptr<PeerMap> map_peer(const policy::XgmiHello& h, std::string* err) 
         }
         memcpy(&handle, h.ipc_handle().data(), sizeof(handle));
         void* p = nullptr;
-        int prev = 0;
-        hipGetDevice(&prev);
-        hipSetDevice(g_device);
+        ScopedDevice on(g_device);
         // a peer on another GPU of this node: the pull kernel reads its HBM
         // directly over xGMI, which needs peer access from our device
         if (h.device() != g_device && h.device() >= 0 && h.device() < DeviceCount()) {
@@ -301,7 +300,6 @@ std::shared_ptr<PeerMap> map_peer(const policy::XgmiHello& h, std::string* err) 
             }
         }
         const hipError_t r = hipIpcOpenMemHandle(&p, handle, hipIpcMemLazyEnablePeerAccess);
-        hipSetDevice(prev);
         if (r != hipSuccess) {
             if (err) *err = std::string("hipIpcOpenMemHandle: ") + hipGetErrorString(r);
             return nullptr;
