@@ -28,6 +28,13 @@ def cgroup_cpu_stat():
         pass
     return out
 
+def socket_counters(native):
+    """The process-wide socket call and message counters (net/socket.cc)."""
+    return {k: int(v) for k, v in native.dump_vars("socket_*").items()
+            if k in ("socket_write_calls", "socket_read_calls", "socket_out_messages", "socket_in_messages",
+                     "socket_write_lingers", "socket_write_linger_hits")}
+
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -129,6 +136,7 @@ def main():
     x0 = native.gpu.xgmi_stats()
     t0 = time.perf_counter()
     r0 = resource.getrusage(resource.RUSAGE_SELF)
+    k0, n0 = socket_counters(native), p.stats()
     th.start()
     if a.no_profile:
         time.sleep(a.seconds)
@@ -136,6 +144,7 @@ def main():
     else:
         folded, n = native.profile_cpu(a.seconds, 999)
     th.join()
+    k1 = socket_counters(native)
     r1 = resource.getrusage(resource.RUSAGE_SELF)
     wall = time.perf_counter() - t0
     c1 = cgroup_cpu_stat()
@@ -144,6 +153,15 @@ def main():
     thr = {k: c1.get(k, 0) - c0.get(k, 0) for k in ("nr_throttled", "throttled_usec", "nr_periods")}
     print("leg=%s qps=%.0f p50=%s p99=%s errors=%d samples=%d cpus_used=%.2f cgroup=%s" % (
         a.leg, st["qps"], st["p50_us"], st["p99_us"], st["error"], n, cpu, thr))
+    # client and server share the process: an RPC is two messages each way
+    kd = {k[len("socket_"):]: k1.get(k, 0) - k0.get(k, 0) for k in k1}
+    rpcs = max(1, st["success"] + st["error"] - n0["success"] - n0["error"])
+    print("socket calls per RPC: write %.3f read %.3f; %.2f messages per write call; lingers %.3f hits %.3f per RPC "
+          "(-socket_write_linger=%s, %d RPCs)" % (
+              kd.get("write_calls", 0) / rpcs, kd.get("read_calls", 0) / rpcs,
+              kd.get("out_messages", 0) / max(1, kd.get("write_calls", 0)),
+              kd.get("write_lingers", 0) / rpcs, kd.get("write_linger_hits", 0) / rpcs,
+              native.list_flags().get("socket_write_linger"), rpcs))
     if st["error"]:
         print("last_error:", st.get("last_error"), "codes:", st.get("error_codes"))
     x1 = native.gpu.xgmi_stats()

@@ -142,7 +142,7 @@ void InputMessenger::OnNewMessages(Socket* m) {
             msg->_received_us = monotonic_us();
             m->AddRef();
             msg->_socket.reset(m);
-            m->in_messages.fetch_add(1, std::memory_order_relaxed);
+            m->AddInMessage();
             if (h.verify && !m->_server_verified.load(std::memory_order_acquire)) {
                 if (!h.verify(msg)) {
                     m->SetFailed(ERPCAUTH, "fail to authenticate %s", m->remote_side().to_string().c_str());

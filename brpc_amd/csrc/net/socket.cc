@@ -20,6 +20,7 @@
 #include "http/http_client.h"
 #include "net/event_dispatcher.h"
 #include "rpc/errno.h"
+#include "var/var.h"
 
 DEFINE_int64(socket_max_unwritten_bytes, 64 * 1024 * 1024,
              "Max unwritten bytes in each socket; writes beyond fail with EOVERCROWDED");
@@ -33,6 +34,11 @@ DEFINE_int32(health_check_timeout_ms, 500,
 DEFINE_int32(socket_recv_buffer_size, -1, "SO_RCVBUF of sockets if positive");
 DEFINE_int32(socket_send_buffer_size, -1, "SO_SNDBUF of sockets if positive");
 DEFINE_int32(max_connection_pool_size, 100, "max pooled connections to one endpoint");
+DEFINE_int32(socket_write_linger, 1,
+             "A KeepWrite fiber that has drained the write queue yields to the other runnable fibers before it gives "
+             "up the writer role, so that what they write goes out in one call with no new writer started; it leaves "
+             "after this many consecutive yields that found nothing (0: leave at once)");
+MRPC_VALIDATE_FLAG(socket_write_linger, mrpc::NonNegativeIntegerValidator);
 
 namespace mrpc {
 
@@ -72,6 +78,20 @@ void Socket::AddFailureCallback(std::function<void()> cb) {
 }
 
 static std::atomic<int64_t> g_nsocket{0};
+
+// Process-wide sums of the per-socket call and message counters (/vars).
+struct SocketVars {
+    var::Adder<int64_t> write_calls{"socket_write_calls"};
+    var::Adder<int64_t> read_calls{"socket_read_calls"};
+    var::Adder<int64_t> out_messages{"socket_out_messages"};
+    var::Adder<int64_t> in_messages{"socket_in_messages"};
+    var::Adder<int64_t> write_lingers{"socket_write_lingers"};          // yields of a drained writer
+    var::Adder<int64_t> write_linger_hits{"socket_write_linger_hits"};  // ... that found new requests
+};
+static SocketVars& socket_vars() {
+    static SocketVars* v = new SocketVars;  // never destroyed: sockets outlive static destructors
+    return *v;
+}
 
 static inline uint64_t make_vref(uint32_t ver, uint32_t nref) { return ((uint64_t)ver << 32) | nref; }
 static inline uint32_t vref_ver(uint64_t v) { return (uint32_t)(v >> 32); }
@@ -149,6 +169,7 @@ int Socket::Create(const SocketOptions& opt, SocketId* id) {
     uint32_t slot;
     Socket* m = get_resource<Socket>(&slot);
     if (!m) return -1;
+    socket_vars();  // expose the counters with the first socket
     const uint32_t ver = vref_ver(m->_versioned_ref.load(std::memory_order_relaxed));
     m->_this_id = make_sid(slot, ver);
     m->_remote_side = opt.remote_side;
@@ -188,6 +209,7 @@ int Socket::Create(const SocketOptions& opt, SocketId* id) {
     m->_hc_started.store(false);
     m->ninflight_health_check = 0;
     m->in_bytes = m->out_bytes = m->in_messages = m->out_messages = 0;
+    m->write_calls = m->read_calls = m->write_eagains = 0;
     {
         std::lock_guard<std::mutex> g(m->_mu);
         m->_transport.reset();
@@ -427,6 +449,11 @@ void Socket::StartInputEvent(SocketId id, uint32_t events) {
     }
 }
 
+void Socket::AddInMessage() {
+    in_messages.fetch_add(1, std::memory_order_relaxed);
+    socket_vars().in_messages << 1;
+}
+
 void* Socket::ProcessEvent(void* arg) {
     Socket* s = static_cast<Socket*>(arg);
     if (s->_on_edge_triggered_events) s->_on_edge_triggered_events(s);
@@ -444,6 +471,8 @@ ssize_t Socket::DoRead(size_t size_hint) {
         errno = EBADF;
         return -1;
     }
+    read_calls.fetch_add(1, std::memory_order_relaxed);
+    socket_vars().read_calls << 1;
     if (_rdma_state.load(std::memory_order_acquire) != RDMA_OFF) return RdmaRead(fd, size_hint);
     if (_ssl_state.load(std::memory_order_acquire) != SSL_OFF) return SslRead(fd, size_hint);
     ssize_t n = _read_buf.append_from_fd(fd, size_hint);
@@ -854,6 +883,7 @@ void Socket::GivebackPipelinedInfo(const PipelinedInfo& pi) {
 int Socket::StartWrite(WriteRequest* req, const WriteOptions& opt) {
     _unwritten_bytes.fetch_add((int64_t)req->data.size(), std::memory_order_relaxed);
     out_messages.fetch_add(1, std::memory_order_relaxed);
+    socket_vars().out_messages << 1;
     WriteRequest* const prev_head = _write_head.exchange(req, std::memory_order_release);
     if (prev_head != nullptr) {
         // Someone is writing; it will pick up this request.
@@ -880,6 +910,7 @@ int Socket::StartWrite(WriteRequest* req, const WriteOptions& opt) {
         } else {
             nw = req->data.cut_into_fd(fd);
         }
+        CountWriteCall(nw);
         if (nw < 0) {
             if (errno != EAGAIN && errno != EWOULDBLOCK && errno != EOVERCROWDED && errno != EINPROGRESS) {
                 saved_errno = errno;
@@ -902,8 +933,15 @@ int Socket::StartWrite(WriteRequest* req, const WriteOptions& opt) {
     // the next connection.
     AddRef();
     fiber::fiber_t th;
-    if (fiber::start_background(&th, &fiber::ATTR_NORMAL, KeepWrite, req) != 0) KeepWrite(req);
+    // Without a fiber of its own the writer runs on the caller: no linger.
+    if (fiber::start_background(&th, &fiber::ATTR_NORMAL, KeepWrite, req) != 0) KeepWriteLoop(req, false);
     return 0;
+}
+
+void Socket::CountWriteCall(ssize_t rc) {
+    write_calls.fetch_add(1, std::memory_order_relaxed);
+    socket_vars().write_calls << 1;
+    if (rc < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) write_eagains.fetch_add(1, std::memory_order_relaxed);
 }
 
 ssize_t Socket::DoWrite(WriteRequest* req) {
@@ -916,14 +954,20 @@ ssize_t Socket::DoWrite(WriteRequest* req) {
         return -1;
     }
     ssize_t nw = WriteList(fd, list, n);
+    CountWriteCall(nw);
     if (nw > 0) out_bytes.fetch_add(nw, std::memory_order_relaxed);
     return nw;
 }
 
 void* Socket::KeepWrite(void* arg) {
-    WriteRequest* req = static_cast<WriteRequest*>(arg);
+    KeepWriteLoop(static_cast<WriteRequest*>(arg), fiber::in_fiber());
+    return nullptr;
+}
+
+void Socket::KeepWriteLoop(WriteRequest* req, bool may_linger) {
     Socket* s = req->socket;
     WriteRequest* cur_tail = nullptr;
+    int idle_lingers = 0;  // consecutive yields that found the queue still empty
     for (;;) {
         if (req->next != nullptr && req->data.empty()) {
             WriteRequest* saved = req;
@@ -977,15 +1021,34 @@ void* Socket::KeepWrite(void* arg) {
             for (cur_tail = req; cur_tail->next != nullptr; cur_tail = cur_tail->next) {
             }
         }
+        // About to give up the writer role with everything written. The
+        // fibers that write next (the siblings cut from the same read batch,
+        // or the callers our responses just woke) are often still in the run
+        // queues: let them run once, so that IsWriteComplete below finds
+        // their requests and one DoWrite carries them all, instead of each
+        // becoming a writer with a write of its own. yield() requeues this
+        // fiber with a signal, so an idle worker takes the writer over if
+        // this one stays busy. A half-close must not wait.
+        if (may_linger && nw > 0 && idle_lingers < FLAGS_socket_write_linger && req == cur_tail &&
+            req->data.empty() && !req->shutdown_after && !s->Failed()) {
+            SocketVars& v = socket_vars();
+            v.write_lingers << 1;
+            fiber::yield();
+            if (s->_write_head.load(std::memory_order_relaxed) != cur_tail) {
+                v.write_linger_hits << 1;
+                idle_lingers = 0;
+            } else {
+                ++idle_lingers;
+            }
+        }
         if (s->IsWriteComplete(cur_tail, req == cur_tail, &cur_tail)) {
             finish_write_request(req, s->fd());
             s->Dereference();
-            return nullptr;
+            return;
         }
     }
     s->ReleaseAllFailedWriteRequests(req);
     s->Dereference();
-    return nullptr;
 }
 
 // ---------------------------------------------------------------- pool / short

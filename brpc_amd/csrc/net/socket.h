@@ -6,7 +6,10 @@
 // docs/en/io.md):
 //  * Write() exchanges the request into _write_head; the first writer writes
 //    in place, later writers return immediately and a KeepWrite fiber
-//    drains the queue batching up to 256 requests per writev.
+//    drains the queue batching up to 256 requests per writev. Before that
+//    fiber gives up the writer role it yields once to the other runnable
+//    fibers (-socket_write_linger), so that what they write joins its next
+//    writev instead of starting a writer each.
 //  * one reader fiber per fd at a time via the _nevent counter.
 //  * SetFailed() bumps the version so Address() fails; with health checking
 //    the id is revived in place when the peer comes back (LBs keep ids).
@@ -244,6 +247,11 @@ public:
 
     // stats
     std::atomic<int64_t> in_bytes{0}, out_bytes{0}, in_messages{0}, out_messages{0};
+    // System calls (or transport calls) of the write and the read path, EAGAIN
+    // results included; write_eagains is the EAGAIN share of write_calls.
+    // out_messages / write_calls is how many messages one call carries.
+    std::atomic<int64_t> write_calls{0}, read_calls{0}, write_eagains{0};
+    void AddInMessage();  // a message was cut from _read_buf (InputMessenger)
     std::string description() const;
 
     static int64_t nsocket();
@@ -262,6 +270,8 @@ private:
     int ConnectIfNot(const timespec* abstime, WriteRequest* req);
     int StartWrite(WriteRequest* req, const WriteOptions& opt);
     static void* KeepWrite(void* arg);
+    static void KeepWriteLoop(WriteRequest* req, bool may_linger);
+    void CountWriteCall(ssize_t rc);
     ssize_t DoWrite(WriteRequest* req);
     bool IsWriteComplete(WriteRequest* old_head, bool singular_node, WriteRequest** new_tail);
     void ReturnFailedWriteRequest(WriteRequest* req, int error_code, const std::string& error_text);
