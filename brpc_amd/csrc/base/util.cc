@@ -11,6 +11,7 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "base/base64.h"
 #include "base/time.h"
 
 namespace mrpc {
@@ -316,47 +317,79 @@ uint32_t md5_hash32(const void* data, size_t n) {
 }
 
 // ---------------------------------------------------------------- base64
-static const char* kB64 = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
-
-std::string base64_encode(const void* data, size_t n) {
+// Both directions run on base/base64.h, the coder the device kernels use
+// (gpu/base64_kernels.hip): whole groups, no table, the output sized once.
+void base64_encode_to(const void* data, size_t n, char* dst) {
     const uint8_t* p = (const uint8_t*)data;
-    std::string out;
-    out.reserve((n + 2) / 3 * 4);
     size_t i = 0;
-    for (; i + 2 < n; i += 3) {
-        uint32_t v = (p[i] << 16) | (p[i + 1] << 8) | p[i + 2];
-        out.push_back(kB64[v >> 18]);
-        out.push_back(kB64[(v >> 12) & 63]);
-        out.push_back(kB64[(v >> 6) & 63]);
-        out.push_back(kB64[v & 63]);
+    // four bytes are read for every three used, so stop one group early
+    for (; i + 4 <= n; i += 3, dst += 4) {
+        uint32_t le;
+        memcpy(&le, p + i, 4);
+        const uint32_t sym = base64::Encode3LE(le);
+        memcpy(dst, &sym, 4);
+    }
+    for (; i + 3 <= n; i += 3, dst += 4) {
+        const uint32_t sym = base64::Encode3((uint32_t)p[i] << 16 | (uint32_t)p[i + 1] << 8 | p[i + 2]);
+        memcpy(dst, &sym, 4);
     }
     if (i < n) {
-        uint32_t v = p[i] << 16;
-        if (i + 1 < n) v |= p[i + 1] << 8;
-        out.push_back(kB64[v >> 18]);
-        out.push_back(kB64[(v >> 12) & 63]);
-        out.push_back(i + 1 < n ? kB64[(v >> 6) & 63] : '=');
-        out.push_back('=');
+        const bool two = i + 1 < n;
+        const uint32_t sym = base64::Encode3((uint32_t)p[i] << 16 | (two ? (uint32_t)p[i + 1] << 8 : 0u));
+        dst[0] = (char)sym;
+        dst[1] = (char)(sym >> 8);
+        dst[2] = two ? (char)(sym >> 16) : '=';
+        dst[3] = '=';
     }
+}
+
+std::string base64_encode(const void* data, size_t n) {
+    std::string out((size_t)base64::Base64EncodedBytes(n), '\0');
+    base64_encode_to(data, n, &out[0]);
     return out;
 }
 
-bool base64_decode(const std::string& in, std::string* out) {
-    int8_t rev[256];
-    memset(rev, -1, sizeof(rev));
-    for (int i = 0; i < 64; ++i) rev[(uint8_t)kB64[i]] = (int8_t)i;
-    out->clear();
+bool base64_decode(const char* in, size_t len, std::string* out) {
+    // the fast loop: whole groups of four alphabet symbols, three bytes each
+    out->resize((size_t)base64::Base64DecodedMaxBytes(len));
+    char* d = &(*out)[0];
+    size_t i = 0, w = 0;
+    // eight symbols, six bytes, stored as eight: only while the groups after
+    // this one leave room for the two extra
+    for (; i + 16 <= len; i += 8, w += 6) {
+        uint64_t sym;
+        memcpy(&sym, in + i, 8);
+        bool ok;
+        const uint64_t be = __builtin_bswap64(base64::Decode8(sym, &ok) << 16);
+        if (!ok) break;
+        memcpy(d + w, &be, 8);
+    }
+    for (; i + 4 <= len; i += 4, w += 3) {
+        uint32_t sym;
+        memcpy(&sym, in + i, 4);
+        bool ok;
+        const uint32_t v = base64::Decode4(sym, &ok);
+        if (!ok) break;
+        d[w] = (char)(v >> 16);
+        d[w + 1] = (char)(v >> 8);
+        d[w + 2] = (char)v;
+    }
+    out->resize(w);
+    // anything else (whitespace, padding, junk, a short tail): symbol by
+    // symbol from here, with the state whole groups leave behind (no pending
+    // bits, i symbols seen)
     uint32_t acc = 0;
     int bits = 0;
-    size_t n = 0, pad = 0;
-    for (char c : in) {
+    size_t n = i, pad = 0;
+    for (; i < len; ++i) {
+        const char c = in[i];
         if (c == '\n' || c == '\r' || c == ' ') continue;
         if (c == '=') {
             ++pad;
             continue;
         }
         if (pad) return false;  // data after padding
-        int v = rev[(uint8_t)c];
+        const int v = base64::Value((uint8_t)c);
         if (v < 0) return false;
         ++n;
         acc = (acc << 6) | (uint32_t)v;
@@ -371,6 +404,8 @@ bool base64_decode(const std::string& in, std::string* out) {
     if (n % 4 == 1 || pad > 2 || (pad && (n + pad) % 4 != 0)) return false;
     return true;
 }
+
+bool base64_decode(const std::string& in, std::string* out) { return base64_decode(in.data(), in.size(), out); }
 
 // ---------------------------------------------------------------- errno
 namespace {

@@ -44,8 +44,14 @@ uint32_t md5_hash32(const void* data, size_t n);
 std::string sha1_hex(const void* data, size_t n);
 
 // ---- base64
+// Standard alphabet, '=' padding. The decoder skips '\n', '\r' and ' ',
+// accepts unpadded input and leaves what it decoded so far in *out when it
+// returns false.
 std::string base64_encode(const void* data, size_t n);
+// Writes Base64EncodedBytes(n) = (n + 2) / 3 * 4 symbols at dst, no terminator.
+void base64_encode_to(const void* data, size_t n, char* dst);
 bool base64_decode(const std::string& in, std::string* out);
+bool base64_decode(const char* in, size_t n, std::string* out);
 
 // ---- big endian packing
 inline void pack_be32(void* p, uint32_t v) {

@@ -701,13 +701,23 @@ int LaunchJsonNumberArrays(const JsonNumberJob* jobs, int njobs, uint32_t nblock
                            JsonNumberResult* res_out, hipStream_t s) {
     if (njobs <= 0 || nblocks == 0) return 0;
     if (!jobs || !res_dev || !res_out) return -1;
-    const dim3 small((unsigned)(njobs + 255) / 256);
-    hipLaunchKernelGGL(json_number_init_kernel, small, dim3(256), 0, s, res_dev, njobs);
-    if (hipGetLastError() != hipSuccess) return -1;
+    if (LaunchJsonNumberResultInit(res_dev, njobs, s) != 0) return -1;
     hipLaunchKernelGGL(json_number_array_kernel, dim3(nblocks), dim3(256), 0, s, jobs, njobs, res_dev);
     if (hipGetLastError() != hipSuccess) return -1;
-    hipLaunchKernelGGL(json_number_publish_kernel, small, dim3(256), 0, s, (const JsonNumberResult*)res_dev, res_out,
-                       njobs);
+    return LaunchJsonNumberResultPublish(res_dev, res_out, njobs, s);
+}
+
+int LaunchJsonNumberResultInit(JsonNumberResult* res_dev, int njobs, hipStream_t s) {
+    if (njobs <= 0) return 0;
+    hipLaunchKernelGGL(json_number_init_kernel, dim3((unsigned)(njobs + 255) / 256), dim3(256), 0, s, res_dev, njobs);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int LaunchJsonNumberResultPublish(const JsonNumberResult* res_dev, JsonNumberResult* res_out, int njobs,
+                                  hipStream_t s) {
+    if (njobs <= 0) return 0;
+    hipLaunchKernelGGL(json_number_publish_kernel, dim3((unsigned)(njobs + 255) / 256), dim3(256), 0, s, res_dev,
+                       res_out, njobs);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

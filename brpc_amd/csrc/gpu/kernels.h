@@ -431,6 +431,42 @@ struct JsonNumberResult {
 };
 int LaunchJsonNumberArrays(const JsonNumberJob* jobs, int njobs, uint32_t nblocks, JsonNumberResult* res_dev,
                            JsonNumberResult* res_out, hipStream_t s);
+// The two small kernels around it, for other job kernels that keep a pair of
+// counters per job in device memory: res_dev[0, njobs) = {0xFFFFFFFF, 0}, and
+// res_out[0, njobs) = res_dev[0, njobs).
+int LaunchJsonNumberResultInit(JsonNumberResult* res_dev, int njobs, hipStream_t s);
+int LaunchJsonNumberResultPublish(const JsonNumberResult* res_dev, JsonNumberResult* res_out, int njobs,
+                                  hipStream_t s);
+
+// Base64 of bytes in device memory (gpu/base64_kernels.hip; the arithmetic is
+// base/base64.h, the code base64_encode / base64_decode run on the host).
+// All jobs share one launch: job j owns the blocks [first_block, first_block
+// + chunks), a workgroup takes one chunk of kBase64ChunkBytes data bytes <->
+// kBase64ChunkSymbols symbols, a lane 12 bytes <-> 16 symbols. src and dst
+// may have any byte alignment and must not overlap.
+//   encode  n data bytes at src -> (n + 2) / 3 * 4 symbols at dst, '=' padded;
+//           chunks = ceil(n / kBase64ChunkBytes)
+//   decode  n bytes of canonical text at src (a body of alphabet symbols and
+//           p = 0..2 trailing '=') -> the data at dst, which must hold
+//           n / 4 * 3 + (n % 4) * 3 / 4 bytes; chunks = ceil(n /
+//           kBase64ChunkSymbols). res[j].bad: the lowest offset of a body
+//           byte outside the alphabet (atomicMin), n when the body length
+//           m = n - p breaks a rule (m % 4 == 1, or p > 0 and n % 4 != 0),
+//           0xFFFFFFFF for canonical text; when it is set nothing of dst may
+//           be trusted. res[j].n_redo: the decoded length m / 4 * 3 +
+//           (m % 4) * 3 / 4. The counters live in device memory (res_dev,
+//           initialised by the launch) and a last small kernel copies them to
+//           res_out (device-writable, pinned host or device).
+constexpr uint32_t kBase64ChunkBytes = 3072, kBase64ChunkSymbols = 4096;
+struct Base64Job {
+    const uint8_t* src;  // device-readable, never null
+    uint8_t* dst;        // device-writable, never null
+    uint32_t n;          // 1 .. 2^32 - 1: data bytes (encode), text bytes (decode)
+    uint32_t first_block;
+};
+int LaunchBase64Encode(const Base64Job* jobs, int njobs, uint32_t nblocks, hipStream_t s);
+int LaunchBase64Decode(const Base64Job* jobs, int njobs, uint32_t nblocks, JsonNumberResult* res_dev,
+                       JsonNumberResult* res_out, hipStream_t s);
 // scratch must hold JsonIndexScratchBytes(n).
 size_t JsonIndexScratchBytes(uint64_t n);
 int LaunchJsonIndex(const uint8_t* in, uint64_t n, uint32_t* out_pos, uint64_t max_out, uint64_t* count_dev,

@@ -12,6 +12,7 @@
 
 #include "base/time.h"
 #include "fiber/fiber.h"
+#include "gpu/base64_offload.h"
 #include "gpu/copy_engine.h"
 #include "gpu/device_codec.h"
 #include "policy/device_payload.h"
@@ -396,6 +397,53 @@ void bind_gpu_ops(py::module_& g) {
         return py::make_tuple(py::bytes(reinterpret_cast<const char*>(payload.data()), n * 8), py::bytes(classes),
                               n_redo);
     }, py::arg("text"), py::arg("device") = 0);
+    // Base64 of bytes in device memory, all jobs in one launch
+    // (gpu::DeviceBase64Encode / DeviceBase64Decode): n bytes at src -> dst
+    // (cap bytes), any alignment. Encode returns [(len, err)], decode
+    // [(len, err, first_odd)]; err 0 done, 1 (decode) not canonical text, 2
+    // refused before any launch, 3 cap too small (len = the size needed).
+    auto base64_jobs = [](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& ns,
+                          const std::vector<uintptr_t>& dsts, const std::vector<uint64_t>& caps) {
+        if (srcs.size() != ns.size() || dsts.size() != ns.size() || caps.size() != ns.size())
+            throw std::invalid_argument("size mismatch");
+        std::vector<gpu::DeviceBase64Job> jobs(ns.size());
+        for (size_t i = 0; i < ns.size(); ++i) {
+            jobs[i].src = (const void*)srcs[i];
+            jobs[i].n = ns[i];
+            jobs[i].dst = (void*)dsts[i];
+            jobs[i].cap = caps[i];
+        }
+        return jobs;
+    };
+    g.def("device_base64_encode", [base64_jobs](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& ns,
+                                                const std::vector<uintptr_t>& dsts, const std::vector<uint64_t>& caps,
+                                                int device) {
+        std::vector<gpu::DeviceBase64Job> jobs = base64_jobs(srcs, ns, dsts, caps);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceBase64Encode(jobs.data(), (int)jobs.size(), device);
+        }
+        check(rc, "device_base64_encode");
+        py::list out;
+        for (const gpu::DeviceBase64Job& j : jobs) out.append(py::make_tuple(j.len, j.err));
+        return out;
+    }, py::arg("srcs"), py::arg("ns"), py::arg("dsts"), py::arg("caps"), py::arg("device") = 0);
+    g.def("device_base64_decode", [base64_jobs](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& ns,
+                                                const std::vector<uintptr_t>& dsts, const std::vector<uint64_t>& caps,
+                                                int device) {
+        std::vector<gpu::DeviceBase64Job> jobs = base64_jobs(srcs, ns, dsts, caps);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceBase64Decode(jobs.data(), (int)jobs.size(), device);
+        }
+        check(rc, "device_base64_decode");
+        py::list out;
+        for (const gpu::DeviceBase64Job& j : jobs) out.append(py::make_tuple(j.len, j.err, j.first_odd));
+        return out;
+    }, py::arg("srcs"), py::arg("ns"), py::arg("dsts"), py::arg("caps"), py::arg("device") = 0);
+    g.def("base64_chunk_bytes", [] { return gpu::kBase64ChunkBytes; });
     // Field table of a message already in device memory -> (nfields, fields)
     g.def("device_pb_scan", [](uintptr_t buf, uint64_t len, int device) {
         const void* p = (const void*)buf;

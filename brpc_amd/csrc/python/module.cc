@@ -6,8 +6,10 @@
 #include <sstream>
 #include <unistd.h>
 
+#include "base/base64.h"
 #include "base/crc32c.h"
 #include "base/decimal_to_double.h"
+#include "base/util.h"
 #include "builtin/cpu_profiler.h"
 #include "base/snappy.h"
 #include "base/flags.h"
@@ -522,6 +524,27 @@ PYBIND11_MODULE(_native, m) {
             throw py::value_error("element " + std::to_string(bad) + " is not a JSON number");
         return py::make_tuple(py::bytes(reinterpret_cast<const char*>(payload.data()), n * 8), py::bytes(classes));
     }, py::arg("text"), py::arg("exact") = true);
+    // The host base64 coder (base/util.h over base/base64.h), reading the
+    // bytes object in place: the text pb2json gives a bytes field, and what
+    // json2pb makes of one (None where base64_decode refuses the text).
+    m.def("base64_encode", [](py::bytes data) {
+        char* p = nullptr;
+        Py_ssize_t n = 0;
+        if (PyBytes_AsStringAndSize(data.ptr(), &p, &n) != 0) throw py::error_already_set();
+        const size_t len = (size_t)base64::Base64EncodedBytes((uint64_t)n);
+        PyObject* out = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)len);
+        if (!out) throw py::error_already_set();
+        base64_encode_to(p, (size_t)n, PyBytes_AS_STRING(out));
+        return py::reinterpret_steal<py::bytes>(out);
+    });
+    m.def("base64_decode", [](py::bytes text) -> py::object {
+        char* p = nullptr;
+        Py_ssize_t n = 0;
+        if (PyBytes_AsStringAndSize(text.ptr(), &p, &n) != 0) throw py::error_already_set();
+        std::string out;
+        if (!base64_decode(p, (size_t)n, &out)) return py::none();
+        return py::bytes(out);
+    });
     m.def("narrow_double_bits", [](uint64_t bits) { return decimal_to_double::NarrowDoubleBits(bits); });
     m.def("json_max_device_number_chars", [] { return decimal_to_double::kMaxDeviceNumberChars; });
     // json::Parse alone (the DOM is dropped): (ok, error). packed=False parses

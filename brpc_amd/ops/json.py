@@ -159,3 +159,72 @@ def json_parse_floats(text, dtype=torch.float64):
         vals = [native.json_parse_double(bytes(t[b:e].cpu().numpy()).strip(b" \t\n\r")) for b, e in zip(begins, ends)]
         out[idx] = torch.tensor(vals, dtype=torch.float64).to(dtype).to(dev)  # narrowed on the host
     return out
+
+
+def base64_encode(data):
+    """Any contiguous device tensor -> uint8 device tensor of the base64 text
+    of its bytes (standard alphabet, ``=`` padded): the form pb2json gives a
+    ``bytes`` field, 4/3 the size of the data. The bytes never leave HBM
+    (``gpu::DeviceBase64Encode``).
+
+    The coder runs on a pool stream, not on torch's: the caller's current
+    stream is synchronized before the call, and the text is complete when
+    this returns."""
+    require_gpu_tensor(data, "data")
+    if not data.is_contiguous():
+        raise ValueError("data must be contiguous")
+    dev = data.device
+    n = data.numel() * data.element_size()
+    cap = (n + 2) // 3 * 4
+    if cap >= 1 << 32:
+        raise ValueError("base64_encode handles outputs below 4 GiB")
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (length, err), = native.gpu.device_base64_encode([data.data_ptr()], [n], [out.data_ptr()], [cap],
+                                                        dev.index or 0)
+    if err:
+        raise ValueError("base64_encode: refused (code %d)" % err)
+    return out[:length]
+
+
+def base64_decode(text):
+    """uint8 device tensor of base64 text -> uint8 device tensor of the bytes,
+    the inverse of ``base64_encode``. Canonical text (alphabet symbols and up
+    to two trailing ``=``, padded or not) is decoded in HBM
+    (``gpu::DeviceBase64Decode``). Anything else is fetched and given to the
+    host decoder ``native.base64_decode``, which skips line breaks and
+    spaces: its result is returned, or ValueError raised naming the offset of
+    the first byte the device found odd.
+
+    The coder runs on a pool stream, not on torch's: the caller's current
+    stream is synchronized before the call, and the bytes are complete when
+    this returns."""
+    require_gpu_tensor(text, "text")
+    if text.dtype != torch.uint8:
+        raise TypeError("text must be uint8")
+    dev = text.device
+    t = text.contiguous().view(-1)
+    n = t.numel()
+    if n >= (1 << 32) - 1:
+        raise ValueError("base64_decode handles inputs below 4 GiB")
+    cap = n // 4 * 3 + (n % 4) * 3 // 4
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (length, err, first_odd), = native.gpu.device_base64_decode([t.data_ptr()], [n], [out.data_ptr()], [cap],
+                                                                   dev.index or 0)
+    if err == 1:
+        lax = native.base64_decode(bytes(t.cpu().numpy()))
+        if lax is None:
+            raise ValueError("base64_decode: not base64 text (offset %d)" % first_odd)
+        if not lax:
+            return out[:0]
+        return torch.frombuffer(bytearray(lax), dtype=torch.uint8).to(dev)
+    if err:
+        raise ValueError("base64_decode: refused (code %d)" % err)
+    return out[:length]
