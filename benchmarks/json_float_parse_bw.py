@@ -1,4 +1,4 @@
-"""What a float / double array costs to parse from JSON text, four ways:
+"""What a float / double array costs to parse from JSON text:
 
   a  element-wise  json::Parse with packed numbers switched off
                    (native.json_parse_check(text, False)): std::from_chars
@@ -16,8 +16,17 @@
                    one wait, payload and classes copied out)
   d  device, HBM -> HBM  native.gpu.device_json_parse_numbers on text and
                    separators in device memory into a device array
-  e  the op        ops.json_parse_floats on the same text: d and the
-                   separators found with torch ops on the device
+  e  the op        ops.json_parse_floats on the same text: one call of f,
+                   the output sized for the worst case
+  f  device, HBM text alone  native.gpu.device_json_parse_text: the same
+                   text with no separator table (the device counts, ranks
+                   and converts), into a device array of n elements
+  g  the op as it was  d behind separators found with torch ops on the
+                   device (nonzero, cat, where and two reads of single
+                   bytes): what ops.json_parse_floats did before f existed
+  h  rows          the same values as "[[v x 1024],[...],...]": f on that
+                   text with a row_ends buffer (h_rows_entry_us) and
+                   ops.json_parse_float_rows (h_rows_op_us)
 
 over "[v,v,...]" of standard-normal float32 / float64 values printed by
 native.json_format_floats. a to c build and drop the DOM inside the timed
@@ -57,6 +66,25 @@ def timed(call, warmup, iters):
     return statistics.median(out)
 
 
+def op_with_torch_separators(native, t, dtype, mode):
+    """Column g: the separator pass ops.json_parse_floats ran before the
+    device found the elements itself (bracketed text, no redo elements)."""
+    dev, n = t.device, t.numel()
+    assert int(t[0]) == 0x5B and int(t[-1]) == 0x5D
+    commas = torch.nonzero(t == 0x2C).view(-1)
+    seps64 = torch.cat([torch.tensor([0], dtype=torch.int64, device=dev), commas,
+                        torch.tensor([n - 1], dtype=torch.int64, device=dev)])
+    seps = torch.where(seps64 >= 1 << 31, seps64 - (1 << 32), seps64).to(torch.int32)
+    count = seps.numel() - 1
+    out = torch.zeros(count, dtype=dtype, device=dev)
+    redo = torch.zeros(64, dtype=torch.int32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    (err, _, n_redo), = native.gpu.device_json_parse_numbers([t.data_ptr()], [seps.data_ptr()], [count], [mode],
+                                                             [out.data_ptr()], [0], [redo.data_ptr()], [64], 0)
+    assert err == 0 and n_redo == 0
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes-ki", default="4,16,64,256,1024")
@@ -89,13 +117,41 @@ def main():
                     return native.gpu.device_json_parse_numbers([dtext.data_ptr()], [dseps.data_ptr()], [n], [mode],
                                                                 [out.data_ptr()], [0], [0], [0], 0)
 
+                def text_entry():
+                    return native.gpu.device_json_parse_text([dtext.data_ptr()], [len(text)], [mode], [out.data_ptr()],
+                                                             [0], [n], [0], [0], [0], [0], 0)
+
+                # the same values in rows of 1024 (one short row when n is no multiple)
+                row_texts = [native.json_format_floats(vals[i:i + 1024].tobytes(), kind) for i in range(0, n, 1024)]
+                nested = b"[[" + b"],[".join(row_texts) + b"]]"
+                dnested = torch.from_numpy(np.frombuffer(nested, dtype=np.uint8).copy()).to(dev)
+                row_ends = torch.zeros(len(row_texts), dtype=torch.int32, device=dev)
+
+                def rows_entry():
+                    return native.gpu.device_json_parse_text([dnested.data_ptr()], [len(nested)], [mode], [out.data_ptr()],
+                                                             [0], [n], [row_ends.data_ptr()], [len(row_texts)], [0], [0], 0)
+
                 # every path parses the same values
+                out.zero_()
+                assert text_entry() == [(0, 1, n, 0, 0, 0xFFFFFFFF)] and out.cpu().numpy().tobytes() == vals.tobytes()
+                out.zero_()
+                assert rows_entry() == [(0, 2, n, len(row_texts), 0, 0xFFFFFFFF)]
+                assert out.cpu().numpy().tobytes() == vals.tobytes()
+                assert row_ends.tolist() == [min(i + 1024, n) for i in range(0, n, 1024)]
+                assert ops.json_parse_float_rows(dnested, dtype=out.dtype, ragged=True)[0].cpu().numpy().tobytes() == vals.tobytes()
+                assert op_with_torch_separators(native, dtext, out.dtype, mode).cpu().numpy().tobytes() == vals.tobytes()
+                out.zero_()
                 assert native.gpu.json_parse_numbers(text, 0)[:2] == (want_payload, want_classes)
                 assert hbm() == [(0, 0xFFFFFFFF, 0)] and out.cpu().numpy().tobytes() == vals.tobytes()
                 assert ops.json_parse_floats(dtext, dtype=out.dtype).cpu().numpy().tobytes() == vals.tobytes()
                 assert native.json_parse_check(text, False) == (True, "") and native.json_parse_check(text, True) == (True, "")
                 t_d = timed(hbm, args.warmup, args.iters)
                 t_e = timed(lambda: ops.json_parse_floats(dtext, dtype=out.dtype), args.warmup, args.iters)
+                t_f = timed(text_entry, args.warmup, args.iters)
+                t_g = timed(lambda: op_with_torch_separators(native, dtext, out.dtype, mode), args.warmup, args.iters)
+                t_hf = timed(rows_entry, args.warmup, args.iters)
+                t_ho = timed(lambda: ops.json_parse_float_rows(dnested, dtype=out.dtype, ragged=n % 1024 != 0),
+                             args.warmup, args.iters)
                 native.set_flag("gpu_json2pb_float_min_elems", "1")
                 native.gpu.enable_json_index(0, 65536)
                 try:
@@ -116,7 +172,9 @@ def main():
                     "a_elementwise_us": round(t_a * 1e6, 1), "b_host_packed_us": round(t_b * 1e6, 1),
                     "c_device_from_host_us": round(t_c * 1e6, 1),
                     "d_hbm_to_hbm_us": round(t_d * 1e6, 1), "e_op_us": round(t_e * 1e6, 1),
-                    "a_over_b": round(t_a / t_b, 1), "b_over_c": round(t_b / t_c, 2),
+                    "f_text_entry_us": round(t_f * 1e6, 1), "g_op_torch_separators_us": round(t_g * 1e6, 1),
+                    "h_rows_entry_us": round(t_hf * 1e6, 1), "h_rows_op_us": round(t_ho * 1e6, 1),
+                    "a_over_b": round(t_a / t_b, 1), "b_over_c": round(t_b / t_c, 2), "g_over_e": round(t_g / t_e, 2),
                     "d_text_gb_per_s": round(len(text) / t_d / 1e9, 2)}), flush=True)
     crossover = {}
     for kind, name in ((FLOAT, "float32"), (DOUBLE, "float64")):

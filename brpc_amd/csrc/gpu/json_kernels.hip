@@ -32,6 +32,7 @@
 #include <cstdint>
 
 #include "base/decimal_to_double.h"
+#include "base/number_text.h"
 #include "base/shortest_double.h"
 #include "gpu/kernels.h"
 
@@ -555,6 +556,292 @@ __global__ void __launch_bounds__(256) json_number_array_kernel(const JsonNumber
     }
 }
 
+// Number text without a separator table (kernels.h JsonTextJob): the text is
+// cut into chunks of kJsonTextChunkBytes, a workgroup per chunk in both
+// passes, a lane per 16 bytes of it. The scanner and every rule of the shape
+// are base/number_text.h, the code json::ParseNumberText runs.
+namespace nt = ::mrpc::number_text;
+typedef uint32_t jt_u32x4 __attribute__((ext_vector_type(4)));
+static_assert(sizeof(nt::TextState) == kJsonTextStateBytes, "kernels.h sizes the state table");
+constexpr uint32_t kJtChunk = kJsonTextChunkBytes;
+constexpr int kJtThreads = 256;
+constexpr uint32_t kJtPer = kJtChunk / kJtThreads;  // 16: one 128-bit LDS read
+constexpr uint32_t kJtPre = 16, kJtPost = 112;      // staged before / after the chunk
+constexpr uint32_t kJtWin = kJtPre + kJtChunk + kJtPost;
+static_assert(kJtPer == 16 && kJtPre % 16 == 0 && kJtChunk < 65536, "a lane's bytes are one aligned uint4; offsets fit 16 bits");
+
+// Reads of the staged window, eight bytes per LDS access: a scan walks its
+// piece byte by byte, and every byte fetched alone is a round trip to LDS the
+// next step waits for. k - wlo is below kJtWin, a multiple of 8.
+struct JtWindowAt {
+    const uint64_t* win8;  // the window, 16-byte aligned
+    uint32_t wlo;
+    mutable uint32_t have = 0xFFFFFFFFu;
+    mutable uint64_t word = 0;
+    __device__ __forceinline__ char operator()(uint32_t k) const {
+        const uint32_t j = k - wlo;
+        if ((j >> 3) != have) {
+            have = j >> 3;
+            word = win8[have];
+        }
+        return (char)(word >> ((j & 7) * 8));
+    }
+};
+static_assert(kJtWin % 16 == 0 && kJtWin / 16 <= 2 * kJtThreads, "the window is read in 8-byte words and staged in at most two 16-byte loads a lane");
+
+// the job that owns chunk ci: the last whose first_chunk is not past it
+__device__ __forceinline__ int jt_job_of(const JsonTextJob* __restrict__ jobs, int njobs, uint32_t ci) {
+    int ja = 0, jb = njobs - 1;
+    while (ja < jb) {
+        const int mid = (ja + jb + 1) / 2;
+        if (jobs[mid].first_chunk <= ci) ja = mid;
+        else jb = mid - 1;
+    }
+    return ja;
+}
+
+// commas in the low half, ']' bytes in the high half (a chunk has at most 4096 of each)
+__device__ __forceinline__ uint32_t jt_tally(char c) { return c == ',' ? 1u : c == ']' ? 0x10000u : 0u; }
+
+// how many of the 16 bytes equal the byte broadcast in pat
+__device__ __forceinline__ uint32_t jt_count_eq(jt_u32x4 q, uint32_t pat) {
+    return (uint32_t)(__builtin_popcount(bytes_eq(q.x, pat)) + __builtin_popcount(bytes_eq(q.y, pat)) +
+                      __builtin_popcount(bytes_eq(q.z, pat)) + __builtin_popcount(bytes_eq(q.w, pat)));
+}
+
+// prefix[0, nchunks]: commas per chunk and a 0; prefix[nchunks + 1, 2 * nchunks + 2): the same for ']'
+__global__ void __launch_bounds__(kJtThreads) json_text_count_kernel(const JsonTextJob* __restrict__ jobs, int njobs,
+                                                                     JsonTextJob* __restrict__ jobs_dev,
+                                                                     uint32_t nchunks, uint32_t* __restrict__ prefix,
+                                                                     nt::TextState* __restrict__ state,
+                                                                     uint32_t* __restrict__ n_redo) {
+    __shared__ uint32_t wave_tot[kJtThreads / 64];
+    __shared__ JsonTextJob job_s;
+    const uint32_t ci = blockIdx.x, t = threadIdx.x;
+    // the table is host memory: one lane reads the job once, the later
+    // kernels find it in device memory (a field read where it is used would
+    // cross the bus every time)
+    if (t == 0) {
+        const int ja = jt_job_of(jobs, njobs, ci);
+        job_s = jobs[ja];
+        if (ci == 0) prefix[nchunks] = prefix[2 * nchunks + 1] = 0;  // become the totals under the scan
+        if (ci == job_s.first_chunk) {
+            jobs_dev[ja] = job_s;
+            state[ja] = nt::TextState{nt::kNone, nt::kNone, 0u, 0u, 0u};
+            n_redo[ja] = 0;
+        }
+    }
+    __syncthreads();
+    const JsonTextJob& job = job_s;
+    const uint64_t s64 = (uint64_t)(ci - job.first_chunk) * kJtChunk;
+    uint32_t v = 0;
+    if (s64 < job.n) {
+        const uint32_t s = (uint32_t)s64, len = job.n - s < kJtChunk ? job.n - s : kJtChunk;
+        if (len == kJtChunk && ((uintptr_t)(job.text + s) & 15) == 0) {  // a whole chunk, aligned: one load a lane
+            const jt_u32x4 q = reinterpret_cast<const jt_u32x4*>(job.text + s)[t];
+            v = jt_count_eq(q, 0x2C2C2C2Cu) | jt_count_eq(q, 0x5D5D5D5Du) << 16;
+        } else {
+            char c[kJtPer];
+#pragma unroll
+            for (uint32_t k = 0; k < kJtPer; ++k) {
+                const uint32_t j = t + k * kJtThreads;
+                c[k] = j < len ? job.text[s + j] : 0;
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < kJtPer; ++k) v += jt_tally(c[k]);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((t & 63) == 0) wave_tot[t >> 6] = v;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t total = 0;
+#pragma unroll
+        for (int w = 0; w < kJtThreads / 64; ++w) total += wave_tot[w];
+        prefix[ci] = total & 0xFFFFu;
+        prefix[nchunks + 1 + ci] = total >> 16;
+    }
+}
+
+__global__ void __launch_bounds__(kJtThreads) json_text_parse_kernel(const JsonTextJob* __restrict__ jobs, int njobs,
+                                                                     uint32_t nchunks,
+                                                                     const uint32_t* __restrict__ prefix,
+                                                                     nt::TextState* __restrict__ state,
+                                                                     uint32_t* __restrict__ n_redo) {
+    __shared__ __attribute__((aligned(16))) char win[kJtWin];
+    __shared__ uint16_t cpos[kJtChunk];  // the chunk's commas, as offsets into it
+    __shared__ uint32_t wave_tot[kJtThreads / 64];
+    __shared__ JsonTextJob job_s;
+    __shared__ int ja_s;
+    const uint32_t ci = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t == 0) {
+        ja_s = jt_job_of(jobs, njobs, ci);
+        job_s = jobs[ja_s];
+    }
+    __syncthreads();
+    const int ja = ja_s;
+    const JsonTextJob& job = job_s;
+    const char* __restrict__ text = job.text;
+    const uint32_t n = job.n;
+    const uint32_t lc = ci - job.first_chunk;
+    const uint64_t s64 = (uint64_t)lc * kJtChunk;
+    if (s64 >= n) return;  // uniform: a chunk the host did not mean for this job
+    const uint32_t s = (uint32_t)s64, e = n - s < kJtChunk ? n : s + kJtChunk;  // the chunk [s, e)
+    // the scan runs over every job's chunks (mod 2^32): differences within a
+    // job are its own counts. Loaded here so that they arrive with the text.
+    const uint32_t* __restrict__ cprefix = prefix;
+    const uint32_t* __restrict__ rprefix = prefix + nchunks + 1;
+    const uint32_t commas_before = cprefix[ci] - cprefix[job.first_chunk];
+    const uint32_t closes_before = rprefix[ci] - rprefix[job.first_chunk];
+    const uint32_t closes_all = rprefix[job.first_chunk + job.nchunks] - rprefix[job.first_chunk];
+    // the staged window [wlo, whi), text[k] at win[k - wlo]
+    const uint32_t wlo = s >= kJtPre ? s - kJtPre : 0, whi = n - e < kJtPost ? n : e + kJtPost;
+    if (whi - wlo == kJtWin && ((uintptr_t)(text + wlo) & 15) == 0) {  // a whole window, aligned: 16 bytes a load
+        constexpr uint32_t kWin16 = kJtWin / 16;
+        const jt_u32x4* from = reinterpret_cast<const jt_u32x4*>(text + wlo);
+        jt_u32x4* to = reinterpret_cast<jt_u32x4*>(win);
+        const jt_u32x4 a = from[t];
+        jt_u32x4 b = {0, 0, 0, 0};
+        if (t + kJtThreads < kWin16) b = from[t + kJtThreads];
+        to[t] = a;
+        if (t + kJtThreads < kWin16) to[t + kJtThreads] = b;
+    } else {
+        constexpr uint32_t kLoads = (kJtWin + kJtThreads - 1) / kJtThreads;
+        char v[kLoads];
+#pragma unroll
+        for (uint32_t k = 0; k < kLoads; ++k) {
+            const uint32_t j = t + k * kJtThreads;
+            v[k] = j < whi - wlo ? text[wlo + j] : 0;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kLoads; ++k) {
+            const uint32_t j = t + k * kJtThreads;
+            if (j < kJtWin) win[j] = v[k];  // zeros past whi: never a comma or a bracket
+        }
+    }
+    __syncthreads();
+    // this lane's 16 bytes of the chunk: s - wlo is 0 or kJtPre, so they are
+    // one aligned uint4. One bit per byte for ',' and for ']' (the SWAR
+    // compares of the structural index), bytes past the chunk masked off.
+    const uint32_t lo = s - wlo + t * kJtPer;  // index into win
+    const uint32_t mine = s + t * kJtPer < e ? (e - (s + t * kJtPer) < kJtPer ? e - (s + t * kJtPer) : kJtPer) : 0;
+    const jt_u32x4 own = *reinterpret_cast<const jt_u32x4*>(win + lo);
+    const uint32_t keep = mine >= kJtPer ? 0xFFFFu : (1u << mine) - 1u;
+    uint32_t comma_bits = (gather4(bytes_eq(own.x, 0x2C2C2C2Cu)) | gather4(bytes_eq(own.y, 0x2C2C2C2Cu)) << 4 |
+                           gather4(bytes_eq(own.z, 0x2C2C2C2Cu)) << 8 | gather4(bytes_eq(own.w, 0x2C2C2C2Cu)) << 12) & keep;
+    uint32_t close_bits = (gather4(bytes_eq(own.x, 0x5D5D5D5Du)) | gather4(bytes_eq(own.y, 0x5D5D5D5Du)) << 4 |
+                           gather4(bytes_eq(own.z, 0x5D5D5D5Du)) << 8 | gather4(bytes_eq(own.w, 0x5D5D5D5Du)) << 12) & keep;
+    const uint32_t own_commas = comma_bits;
+    const uint32_t tally = (uint32_t)__builtin_popcount(comma_bits) | (uint32_t)__builtin_popcount(close_bits) << 16;
+    uint32_t incl = tally;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(incl, off, 64);
+        if (lane >= (uint32_t)off) incl += y;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    uint32_t before = incl - tally, total = 0;
+#pragma unroll
+    for (int w = 0; w < kJtThreads / 64; ++w) {
+        const uint32_t x = wave_tot[w];
+        if ((uint32_t)w < wave) before += x;
+        total += x;
+    }
+    const uint32_t ncommas = total & 0xFFFFu;  // of this chunk
+    {
+        uint32_t c_at = before & 0xFFFFu;
+        for (; comma_bits; comma_bits &= comma_bits - 1) cpos[c_at++] = (uint16_t)(t * kJtPer + __builtin_ctz(comma_bits));
+        // the k-th ']' of the text ends row k; the last one closes the outer array
+        uint32_t r = closes_before + (before >> 16);
+        for (; close_bits; close_bits &= close_bits - 1, ++r) {
+            const uint32_t k = (uint32_t)__builtin_ctz(close_bits);
+            const uint32_t commas_to_here = (before & 0xFFFFu) + (uint32_t)__builtin_popcount(own_commas & ((1u << k) - 1u));
+            if (job.row_ends && r + 1 < closes_all && r < job.row_cap) job.row_ends[r] = commas_before + commas_to_here + 1;
+        }
+    }
+    __syncthreads();
+    // positions stay absolute; an LDS pointer must never be offset below the
+    // array (a flat address below the LDS aperture is a global address)
+    auto at = [&](uint32_t k) -> char { return k >= wlo && k < whi ? win[k - wlo] : text[k]; };
+    // nearly every piece lies inside the window: it is scanned as if the text ended at whi, from LDS alone
+    const JtWindowAt at_win{reinterpret_cast<const uint64_t*>(win), wlo};
+    nt::TextState* __restrict__ st = state + ja;
+    // piece q + 1 of the chunk follows its comma q; the text's first chunk
+    // also owns the piece before any comma (q = -1). A chunk holds 0 to
+    // kJtChunk commas, so the lanes go round.
+    for (int q = (int)t - (lc == 0 ? 1 : 0); q < (int)ncommas; q += kJtThreads) {
+        const uint32_t b = q < 0 ? 0 : s + cpos[q] + 1;  // <= n
+        const uint32_t idx = q < 0 ? 0 : commas_before + (uint32_t)q + 1;
+        nt::Piece piece;
+        bool inside = b <= whi;  // b >= s >= wlo
+        if (inside) {
+            nt::ScanPiece(at_win, b, whi, &piece);
+            inside = !piece.fits || piece.end < whi || whi == n;  // a refusal is one whatever follows
+        }
+        if (!inside) nt::ScanPiece(at, b, n, &piece);
+        bool closes = false;
+        if (q >= 0) {  // nt::ClosesBefore(at, b - 1), in the window as far as it reaches
+            uint32_t k = b - 1;
+            while (k > wlo && nt::IsSpace(win[k - 1 - wlo])) --k;
+            closes = k > wlo ? win[k - 1 - wlo] == ']' : nt::ClosesBefore(at, k);
+        }
+        const uint32_t verdict = nt::JudgePiece(piece, idx, n, closes);
+        if (verdict & nt::kPieceBad) {
+            atomicMin(&st->bad, idx);
+            continue;
+        }
+        if (idx == 0) st->lead0 = piece.lead;
+        if (piece.end == n) st->trail_last = piece.trail;
+        if (verdict & nt::kPieceBlank) {
+            st->blank = 1;
+            continue;
+        }
+        if (verdict & nt::kPieceNested) atomicMin(&st->nested_min, idx);
+        dd::NumberResult r;
+        if (inside) dd::ParseJsonNumberAt(at_win, piece.nb, piece.ne, &r);
+        else dd::ParseJsonNumberAt(at, piece.nb, piece.ne, &r);
+        if (r.cls == dd::kMalformed) {
+            atomicMin(&st->bad, idx);
+            continue;
+        }
+        if (r.cls == dd::kNeedsExact) {
+            const uint32_t slot = atomicAdd(&n_redo[ja], 1u);
+            if (slot < job.redo_cap) {
+                job.redo[2 * (uint64_t)slot] = idx;
+                job.redo[2 * (uint64_t)slot + 1] = b;
+            }
+            continue;
+        }
+        if (idx >= job.cap) continue;  // counted, not stored: the publish step reports it
+        if (job.mode == JSON_PARSE_NUMBERS) {
+            static_cast<uint64_t*>(job.out)[idx] = r.bits;
+            job.classes[idx] = r.cls;
+        } else if (job.mode == JSON_PARSE_FLOAT64) {
+            static_cast<uint64_t*>(job.out)[idx] = dd::NumberToDoubleBits(r);
+        } else {
+            static_cast<uint32_t*>(job.out)[idx] = dd::NarrowDoubleBits(dd::NumberToDoubleBits(r));
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) json_text_publish_kernel(const JsonTextJob* __restrict__ jobs, int njobs,
+                                                                uint32_t nchunks,
+                                                                const uint32_t* __restrict__ prefix,
+                                                                const nt::TextState* __restrict__ state,
+                                                                const uint32_t* __restrict__ n_redo,
+                                                                JsonTextResult* __restrict__ res) {
+    const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (j >= njobs) return;
+    const JsonTextJob job = jobs[j];
+    const uint32_t* rprefix = prefix + nchunks + 1;
+    const uint32_t commas = prefix[job.first_chunk + job.nchunks] - prefix[job.first_chunk];
+    const uint32_t closes = rprefix[job.first_chunk + job.nchunks] - rprefix[job.first_chunk];
+    const nt::TextVerdict v = nt::CombineNumberText(state[j], commas, closes, job.row_ends != nullptr);
+    res[j] = JsonTextResult{v.first_bad, n_redo[j], v.depth, v.count, v.rows, 0u};
+}
+
 // pb2json float / double arrays (kernels.h: size, prefix, place). The
 // reference prints them element by element on the host through rapidjson's
 // Writer (src/json2pb/pb_to_json.cpp); here one lane formats one element
@@ -705,6 +992,23 @@ int LaunchJsonNumberArrays(const JsonNumberJob* jobs, int njobs, uint32_t nblock
     hipLaunchKernelGGL(json_number_array_kernel, dim3(nblocks), dim3(256), 0, s, jobs, njobs, res_dev);
     if (hipGetLastError() != hipSuccess) return -1;
     return LaunchJsonNumberResultPublish(res_dev, res_out, njobs, s);
+}
+
+int LaunchJsonNumberText(const JsonTextTables& t, hipStream_t s) {
+    if (t.njobs <= 0 || t.nchunks == 0) return 0;
+    if (!t.jobs || !t.jobs_dev || !t.prefix || !t.state || !t.n_redo || !t.res) return -1;
+    nt::TextState* state = static_cast<nt::TextState*>(t.state);
+    hipLaunchKernelGGL(json_text_count_kernel, dim3(t.nchunks), dim3(kJtThreads), 0, s, t.jobs, t.njobs, t.jobs_dev,
+                       t.nchunks, t.prefix, state, t.n_redo);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (LaunchPbRunPrefix(t.prefix, (int)(2 * t.nchunks + 2), s) != 0) return -1;
+    const JsonTextJob* jobs_dev = t.jobs_dev;
+    hipLaunchKernelGGL(json_text_parse_kernel, dim3(t.nchunks), dim3(kJtThreads), 0, s, jobs_dev, t.njobs, t.nchunks,
+                       t.prefix, state, t.n_redo);
+    if (hipGetLastError() != hipSuccess) return -1;
+    hipLaunchKernelGGL(json_text_publish_kernel, dim3((unsigned)(t.njobs + 255) / 256), dim3(256), 0, s, jobs_dev,
+                       t.njobs, t.nchunks, t.prefix, state, t.n_redo, t.res);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int LaunchJsonNumberResultInit(JsonNumberResult* res_dev, int njobs, hipStream_t s) {

@@ -289,6 +289,77 @@ int DeviceParseNumberArrays(DeviceNumberParseJob* jobs, int n, int device) {
     return 0;
 }
 
+uint32_t JsonTextChunkBytes() { return kJsonTextChunkBytes; }
+
+int DeviceParseNumberText(DeviceNumberTextJob* jobs, int n, int device) {
+    if (n <= 0) return 0;
+    if (!jobs || device < 0) return -1;
+    // refuse what must not reach a kernel; count the chunks of the rest
+    uint64_t nchunks = 0;
+    std::vector<int> live;  // the jobs that go to the device, in order
+    for (int i = 0; i < n; ++i) {
+        DeviceNumberTextJob& j = jobs[i];
+        j.depth = 0;
+        j.count = j.rows = 0;
+        j.n_redo = 0;
+        j.first_bad = 0xFFFFFFFFu;
+        j.err = 0;
+        const size_t align = j.mode == kJsonParseFloat32 ? 4 : 8;
+        if (j.mode > kJsonParseFloat32 || (!j.text && j.n > 0) || (!j.out && j.cap > 0) ||
+            (j.mode == kJsonParseNumbers && !j.classes && j.cap > 0) || (j.redo_cap > 0 && !j.redo) ||
+            (j.row_cap > 0 && !j.row_ends) || ((uintptr_t)j.out & (align - 1)) != 0 ||
+            ((uintptr_t)j.row_ends & 3) != 0 || ((uintptr_t)j.redo & 3) != 0 || j.n > 0xFFFFFFFEull) {
+            j.err = 2;
+            continue;
+        }
+        if (j.n == 0) continue;
+        nchunks += (j.n + kJsonTextChunkBytes - 1) / kJsonTextChunkBytes;
+        live.push_back(i);
+    }
+    if (live.empty()) return 0;
+    if (nchunks > 0x3FFFFFFFull) return -1;  // one grid, and 2 * nchunks + 2 table entries
+    const int nlive = (int)live.size();
+    const size_t prefix_bytes = (2 * (size_t)nchunks + 2) * sizeof(uint32_t);
+    PinnedBlock tables(live.size() * (sizeof(JsonTextJob) + sizeof(JsonTextResult)));
+    const size_t jobs_bytes = live.size() * sizeof(JsonTextJob);  // first: the most aligned
+    HbmBlock scratch(jobs_bytes + prefix_bytes + live.size() * (kJsonTextStateBytes + sizeof(uint32_t)), device);
+    if (!tables || !scratch) return -1;
+    JsonTextJob* tj = tables.as<JsonTextJob>();
+    JsonTextResult* tr = reinterpret_cast<JsonTextResult*>(tj + nlive);
+    uint32_t chunk = 0;
+    for (int k = 0; k < nlive; ++k) {
+        const DeviceNumberTextJob& j = jobs[live[k]];
+        const uint32_t nc = (uint32_t)((j.n + kJsonTextChunkBytes - 1) / kJsonTextChunkBytes);
+        auto clamp = [](uint64_t v) { return (uint32_t)std::min<uint64_t>(v, 0xFFFFFFFFull); };
+        tj[k] = JsonTextJob{j.text,      j.out,        j.classes,        j.row_ends, j.redo, (uint32_t)j.n, j.mode,
+                            clamp(j.cap), clamp(j.row_cap), j.redo_cap, chunk,      nc};
+        tr[k] = JsonTextResult{0xFFFFFFFFu, 0, 0, 0, 0, 0};
+        chunk += nc;
+    }
+    JsonTextTables t;
+    t.jobs = tj;
+    t.njobs = nlive;
+    t.nchunks = chunk;
+    t.jobs_dev = scratch.as<JsonTextJob>();
+    t.prefix = reinterpret_cast<uint32_t*>(static_cast<char*>(scratch.p) + jobs_bytes);
+    t.state = static_cast<char*>(scratch.p) + jobs_bytes + prefix_bytes;
+    t.n_redo = reinterpret_cast<uint32_t*>(static_cast<char*>(t.state) + live.size() * kJsonTextStateBytes);
+    t.res = tr;
+    if (RunOnPoolStream(device, [&](hipStream_t s) { return LaunchJsonNumberText(t, s); }) != 0) return -1;
+    for (int k = 0; k < nlive; ++k) {
+        DeviceNumberTextJob& j = jobs[live[k]];
+        j.depth = tr[k].depth;
+        j.count = tr[k].count;
+        j.rows = tr[k].rows;
+        j.n_redo = tr[k].n_redo;
+        j.first_bad = tr[k].first_bad;
+        if (j.first_bad != 0xFFFFFFFFu) j.err = 1;
+        else if (j.count > j.cap || j.rows > j.row_cap) j.err = 5;
+        else if (j.n_redo > j.redo_cap) j.err = 3;
+    }
+    return 0;
+}
+
 namespace {
 // elements of one array the device may hand back for exact arithmetic before
 // the whole array goes to the host (they are rare: a 20-digit number whose

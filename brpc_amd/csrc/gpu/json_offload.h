@@ -101,6 +101,60 @@ int DeviceParseNumberArrays(DeviceNumberParseJob* jobs, int n, int device);
 bool ParseNumbersOnDevice(const char* base, const uint32_t* seps, size_t nseps, uint64_t* payload, uint8_t* classes,
                           int device, uint32_t* n_redo = nullptr);
 
+// ---- JSON number text parsed on the device with no separator table: the
+// caller has bytes in HBM (a string field, a peer's printed embedding, the
+// text behind a "key": prefix) and nothing else. Accepted, with JSON
+// whitespace wherever JSON allows it:
+//   depth 0  v,v,...,v
+//   depth 1  [v,v,...,v]
+//   depth 2  [[v,..],[v,..],..]   rows of any (nonzero) lengths
+// every v a number of the RFC 8259 grammar. Empty text, whitespace and "[ ]"
+// are count 0. Everything else is malformed: first_bad is the lowest index
+// of a piece (the text between consecutive commas or the ends) that does not
+// fit. json::ParseNumberText is the host twin: the same scanner
+// (base/number_text.h), the same verdicts.
+struct DeviceNumberTextJob {
+    const char* text = nullptr;  // device or pinned host, any byte alignment
+    uint64_t n = 0;              // bytes, below 2^32 - 1
+    uint32_t mode = 0;           // kJsonParse*: out / classes exactly as in DeviceNumberParseJob
+    void* out = nullptr;         // cap elements, 8-byte aligned (4 for float32)
+    uint8_t* classes = nullptr;  // kJsonParseNumbers only, cap bytes
+    uint64_t cap = 0;
+    // depth 2: row_ends[r] = the elements in rows 0..r. Null: nested text is
+    // malformed (first_bad 0).
+    uint32_t* row_ends = nullptr;
+    uint64_t row_cap = 0;
+    // elements the device does not decide (see DeviceNumberParseJob): nothing
+    // is written to out for them; each takes a pair {element index, offset of
+    // the first byte after the element's preceding separator} (0 for the
+    // first element), in no particular order. The element is the number in
+    // the piece that starts there, within its brackets and whitespace.
+    uint32_t* redo = nullptr;  // 2 * redo_cap entries, device-writable
+    uint32_t redo_cap = 0;
+    // out
+    uint32_t depth = 0;
+    uint64_t count = 0;  // elements (with err 5: what the text holds; with err 1: its pieces)
+    uint64_t rows = 0;   // depth 2 only
+    uint32_t n_redo = 0;
+    uint32_t first_bad = 0xFFFFFFFFu;
+    // 0 parsed; 1 malformed (trust nothing of out); 2 refused before any
+    // launch (null text with n > 0, bad mode, null out with cap > 0,
+    // misaligned out / row_ends / redo, n above 2^32 - 2, classes missing in
+    // numbers mode, redo_cap without redo, row_cap without row_ends); 3 more
+    // than redo_cap undecided elements (n_redo is the true number); 5 more
+    // than cap elements or more than row_cap rows (count and rows are what is
+    // needed; nothing is written beyond the capacities). 5 is reported
+    // before 3.
+    int err = 0;
+};
+// All jobs share one launch sequence (count, prefix, parse, publish) on a
+// pool stream and one fiber-friendly wait; nothing is read back in between.
+// Returns -1 only on a device error; per-job codes in jobs[i].err. A job of
+// n 0 launches nothing (count 0, err 0).
+int DeviceParseNumberText(DeviceNumberTextJob* jobs, int n, int device);
+// Bytes of text one workgroup takes (tests aim at its edges).
+uint32_t JsonTextChunkBytes();
+
 struct GpuJsonStats {
     // json2pb number arrays (floats) parsed on the device; fallbacks: arrays the device declined
     int64_t number_arrays = 0, number_elems = 0, number_array_fallbacks = 0, number_redo_elems = 0;

@@ -438,6 +438,59 @@ int LaunchJsonNumberResultInit(JsonNumberResult* res_dev, int njobs, hipStream_t
 int LaunchJsonNumberResultPublish(const JsonNumberResult* res_dev, JsonNumberResult* res_out, int njobs,
                                   hipStream_t s);
 
+// JSON number text with no separator table: bare "v,v,...,v", "[v,...,v]" or
+// "[[v,..],[v,..],..]" in device (or pinned) memory -> the outputs of
+// JSON_PARSE_* above. The device finds the elements and the rows itself; the
+// shape rules are base/number_text.h, the code json::ParseNumberText runs.
+// A text is cut into chunks of kJsonTextChunkBytes; all jobs share the
+// launches, ordered by the stream alone (no count is read back between them):
+//   count   a workgroup per chunk counts its ',' and ']' bytes into prefix
+//           (and resets the job's state, and copies the job to device memory
+//           for the passes that follow)
+//   prefix  LaunchPbRunPrefix scans both tables
+//   parse   a workgroup per chunk stages it with 16 bytes before and 112
+//           after in LDS, ranks its commas, and lanes take the pieces that
+//           follow them in rounds (a chunk holds 0 to kJsonTextChunkBytes
+//           pieces; the text's first chunk also takes the piece before any
+//           comma): piece index = commas before the chunk + rank + 1. A piece
+//           that leaves the staged window is read from memory directly. The
+//           lane that holds the k-th ']' of the text writes row_ends[k] (the
+//           last ']' closes the outer array and ends no row).
+//   publish a lane per job combines depth, brackets and counts into res
+// Stores go below cap (out, classes), row_cap and redo_cap only. An element a
+// lane does not decide takes a slot of redo as the pair {index, offset of the
+// byte after the comma before it}; n_redo keeps counting past redo_cap.
+constexpr uint32_t kJsonTextChunkBytes = 4096;
+struct JsonTextJob {
+    const char* text;    // device-readable, any alignment
+    void* out;           // device-writable, naturally aligned for the mode; may be null when cap is 0
+    uint8_t* classes;    // JSON_PARSE_NUMBERS only
+    uint32_t* row_ends;  // null: depth 2 is malformed
+    uint32_t* redo;      // 2 * redo_cap entries, may be null when redo_cap is 0
+    uint32_t n;          // 1 .. 2^32 - 2 bytes
+    uint32_t mode;
+    uint32_t cap, row_cap, redo_cap;
+    uint32_t first_chunk, nchunks;  // nchunks = ceil(n / kJsonTextChunkBytes)
+};
+struct JsonTextResult {
+    uint32_t first_bad;  // lowest index of a piece that does not fit, 0xFFFFFFFF when all do
+    uint32_t n_redo;
+    uint32_t depth, count, rows;  // count / rows: what the text holds, also beyond cap / row_cap
+    uint32_t pad;
+};
+constexpr size_t kJsonTextStateBytes = 20;  // number_text::TextState, per job
+struct JsonTextTables {
+    const JsonTextJob* jobs = nullptr;  // device-readable (pinned host)
+    int njobs = 0;
+    JsonTextJob* jobs_dev = nullptr;    // device memory, njobs: the count pass copies the table there
+    uint32_t nchunks = 0;        // of all jobs
+    uint32_t* prefix = nullptr;  // device memory, 2 * nchunks + 2 entries
+    void* state = nullptr;       // device memory, njobs * kJsonTextStateBytes
+    uint32_t* n_redo = nullptr;  // device memory, njobs entries
+    JsonTextResult* res = nullptr;  // device-writable (pinned host), njobs
+};
+int LaunchJsonNumberText(const JsonTextTables& t, hipStream_t s);
+
 // Base64 of bytes in device memory (gpu/base64_kernels.hip; the arithmetic is
 // base/base64.h, the code base64_encode / base64_decode run on the host).
 // All jobs share one launch: job j owns the blocks [first_block, first_block

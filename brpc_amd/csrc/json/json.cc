@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "base/decimal_to_double.h"
+#include "base/number_text.h"
 
 namespace mrpc {
 namespace json {
@@ -444,6 +445,92 @@ bool ParseNumberArray(const char* base, const uint32_t* seps, size_t nseps, uint
         payload[i] = r.bits;
         classes[i] = r.cls;
     }
+    return true;
+}
+
+bool ParseNumberText(const char* text, size_t n, uint32_t mode, NumberText* out, bool exact, bool nested_ok) {
+    namespace nt = number_text;
+    *out = NumberText();
+    if (mode > 2 || n >= 0xFFFFFFFFull || (!text && n > 0)) {
+        out->err = 2;
+        return false;
+    }
+    if (n == 0) return true;
+    const uint32_t N = (uint32_t)n;
+    // the k-th ']' ends row k (the last one closes the outer array)
+    uint32_t commas = 0, closes = 0;
+    for (uint32_t i = 0; i < N; ++i) {
+        if (text[i] == ',') ++commas;
+        else if (text[i] == ']') {
+            ++closes;
+            if (nested_ok) out->row_ends.push_back(commas + 1);
+        }
+    }
+    const dd::PointerAt at{text};
+    const size_t width = mode == 2 ? 4 : 8;
+    out->out.reserve(((size_t)commas + 1) * width);
+    nt::TextState st{nt::kNone, nt::kNone, 0, 0, 0};
+    uint32_t b = 0;
+    // in index order, so the first piece found wanting is the lowest
+    for (uint32_t idx = 0;; ++idx) {
+        nt::Piece s;
+        nt::ScanPiece(at, b, N, &s);
+        const uint32_t verdict = nt::JudgePiece(s, idx, N, idx > 0 && nt::ClosesBefore(at, b - 1));
+        if (verdict & nt::kPieceBad) {
+            st.bad = idx;
+            break;
+        }
+        if (idx == 0) st.lead0 = s.lead;
+        if (s.end == N) st.trail_last = s.trail;
+        if (verdict & nt::kPieceBlank) {
+            st.blank = 1;
+            break;
+        }
+        if ((verdict & nt::kPieceNested) && st.nested_min == nt::kNone) st.nested_min = idx;
+        dd::NumberResult r;
+        dd::ParseJsonNumber(text + s.nb, text + s.ne, &r);
+        if (r.cls == dd::kNeedsExact) {
+            if (!exact) {
+                out->redo.push_back(idx);
+                out->redo.push_back(b);
+                r.bits = 0;
+            } else if (!ParseNumberExact(text + s.nb, text + s.ne, &r.bits, &r.cls)) {
+                r.cls = dd::kMalformed;
+            }
+        }
+        if (r.cls == dd::kMalformed) {
+            st.bad = idx;
+            break;
+        }
+        if (mode == 0) {
+            out->out.append(reinterpret_cast<const char*>(&r.bits), 8);
+            out->classes.push_back((char)r.cls);
+        } else {
+            const uint64_t d = r.cls == dd::kNeedsExact ? 0 : dd::NumberToDoubleBits(r);
+            if (mode == 1) {
+                out->out.append(reinterpret_cast<const char*>(&d), 8);
+            } else {
+                const uint32_t f = dd::NarrowDoubleBits(d);
+                out->out.append(reinterpret_cast<const char*>(&f), 4);
+            }
+        }
+        if (s.end == N) break;
+        b = s.end + 1;
+    }
+    const nt::TextVerdict v = nt::CombineNumberText(st, commas, closes, nested_ok);
+    out->depth = v.depth;
+    out->count = v.count;
+    out->rows = v.rows;
+    out->first_bad = v.first_bad;
+    if (v.first_bad != nt::kNone) {
+        out->err = 1;
+        out->out.clear();
+        out->classes.clear();
+        out->row_ends.clear();
+        out->redo.clear();
+        return false;
+    }
+    out->row_ends.resize(v.rows);
     return true;
 }
 

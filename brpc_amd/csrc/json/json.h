@@ -193,6 +193,31 @@ bool ParseNumberExact(const char* b, const char* e, uint64_t* payload, uint8_t* 
 // '[', every ',' and the ']'; of bare "v,v,...,v" every ',' between
 // 0xFFFFFFFF (a separator before the first byte) and n. Text below 4 GiB.
 void NumberArraySeparators(const char* text, size_t n, std::vector<uint32_t>* seps);
+// The host twin of gpu::DeviceParseNumberText (gpu/json_offload.h): number
+// text with no separator table, bare "v,v,...,v" (depth 0), "[v,v,...,v]"
+// (depth 1) or "[[v,..],[v,..],..]" (depth 2, rows of any lengths), JSON
+// whitespace wherever JSON allows it. One scanner, base/number_text.h, gives
+// the device and this function the same verdict on every text. mode: 0 eight
+// bytes of payload per element in `out` and a class byte in `classes` (as
+// ParseNumberArray), 1 doubles, 2 floats (the narrowed double).
+struct NumberText {
+    int err = 0;  // 0 parsed; 1 malformed (first_bad set, out / classes / row_ends empty); 2 bad mode or n >= 2^32 - 1
+    uint32_t depth = 0;
+    uint32_t count = 0;  // elements; with err 1 the pieces (commas + 1)
+    uint32_t rows = 0;   // depth 2 only
+    uint32_t first_bad = 0xFFFFFFFFu;  // lowest index of a piece (the text between commas) that does not fit
+    std::string out, classes;
+    std::vector<uint32_t> row_ends;  // rows entries: the elements in rows 0..r
+    // exact == false only: the elements a device lane hands back (class 3 /
+    // a zero in out), as pairs {index, offset of the byte after the comma
+    // before the element}
+    std::vector<uint32_t> redo;
+};
+// Empty text, whitespace and "[ ]" are count 0. nested_ok == false refuses
+// depth 2 (first_bad 0), as the device does without a row_ends buffer.
+// Returns err == 0.
+bool ParseNumberText(const char* text, size_t n, uint32_t mode, NumberText* out, bool exact = true,
+                     bool nested_ok = true);
 // Test and benchmark hook: false makes the reader parse number arrays element
 // by element with std::from_chars, as it did before packed numbers (the DOM
 // is the same either way; only storage and speed differ). Default true.

@@ -374,6 +374,47 @@ void bind_gpu_ops(py::module_& g) {
         return out;
     }, py::arg("texts"), py::arg("seps"), py::arg("counts"), py::arg("modes"), py::arg("outs"), py::arg("classes"),
        py::arg("redos"), py::arg("redo_caps"), py::arg("device") = 0);
+    // Number text in device (or pinned) memory with no separator table ->
+    // values, all jobs in one launch sequence (gpu::DeviceParseNumberText).
+    // Per job: text, n bytes, mode, out, classes, cap (elements), row_ends,
+    // row_cap, redo (2 * redo_cap uint32: {index, offset} pairs), redo_cap.
+    // Returns [(err, depth, count, rows, n_redo, first_bad)].
+    g.def("device_json_parse_text", [](const std::vector<uintptr_t>& texts, const std::vector<uint64_t>& ns,
+                                       const std::vector<uint32_t>& modes, const std::vector<uintptr_t>& outs,
+                                       const std::vector<uintptr_t>& classes, const std::vector<uint64_t>& caps,
+                                       const std::vector<uintptr_t>& row_ends, const std::vector<uint64_t>& row_caps,
+                                       const std::vector<uintptr_t>& redos, const std::vector<uint32_t>& redo_caps,
+                                       int device) {
+        const size_t n = ns.size();
+        if (texts.size() != n || modes.size() != n || outs.size() != n || classes.size() != n || caps.size() != n ||
+            row_ends.size() != n || row_caps.size() != n || redos.size() != n || redo_caps.size() != n)
+            throw std::invalid_argument("size mismatch");
+        std::vector<gpu::DeviceNumberTextJob> jobs(n);
+        for (size_t i = 0; i < n; ++i) {
+            jobs[i].text = (const char*)texts[i];
+            jobs[i].n = ns[i];
+            jobs[i].mode = modes[i];
+            jobs[i].out = (void*)outs[i];
+            jobs[i].classes = (uint8_t*)classes[i];
+            jobs[i].cap = caps[i];
+            jobs[i].row_ends = (uint32_t*)row_ends[i];
+            jobs[i].row_cap = row_caps[i];
+            jobs[i].redo = (uint32_t*)redos[i];
+            jobs[i].redo_cap = redo_caps[i];
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceParseNumberText(jobs.data(), (int)jobs.size(), device);
+        }
+        check(rc, "device_json_parse_text");
+        py::list out;
+        for (const gpu::DeviceNumberTextJob& j : jobs)
+            out.append(py::make_tuple(j.err, j.depth, j.count, j.rows, j.n_redo, j.first_bad));
+        return out;
+    }, py::arg("texts"), py::arg("ns"), py::arg("modes"), py::arg("outs"), py::arg("classes"), py::arg("caps"),
+       py::arg("row_ends"), py::arg("row_caps"), py::arg("redos"), py::arg("redo_caps"), py::arg("device") = 0);
+    g.def("json_text_chunk_bytes", &gpu::JsonTextChunkBytes);
     // Host text "[v,v,...]" or "v,v,...,v" -> (payload, classes, n_redo)
     // through the device (gpu::ParseNumbersOnDevice: pinned stage, one wait,
     // redo elements repaired on the host); ValueError when the device

@@ -524,6 +524,22 @@ PYBIND11_MODULE(_native, m) {
             throw py::value_error("element " + std::to_string(bad) + " is not a JSON number");
         return py::make_tuple(py::bytes(reinterpret_cast<const char*>(payload.data()), n * 8), py::bytes(classes));
     }, py::arg("text"), py::arg("exact") = true);
+    // The host twin of gpu::DeviceParseNumberText (json::ParseNumberText):
+    // bare, "[...]" or "[[...],[...]]" number text with no separator table ->
+    // (err, depth, count, rows, first_bad, out, classes, row_ends). mode 0:
+    // out holds 8 bytes of payload per element and classes a byte each; 1:
+    // doubles; 2: floats. exact=False leaves the elements a device lane would
+    // hand back as class 3 / zeros. nested=False refuses depth 2, as the
+    // device does without a row_ends buffer.
+    m.def("json_parse_number_text", [](py::bytes text, uint32_t mode, bool exact, bool nested) {
+        char* p = nullptr;  // read in place
+        Py_ssize_t n = 0;
+        if (PyBytes_AsStringAndSize(text.ptr(), &p, &n) != 0) throw py::error_already_set();
+        json::NumberText r;
+        json::ParseNumberText(p, (size_t)n, mode, &r, exact, nested);
+        return py::make_tuple(r.err, r.depth, r.count, r.rows, r.first_bad, py::bytes(r.out), py::bytes(r.classes),
+                              r.row_ends);
+    }, py::arg("text"), py::arg("mode"), py::arg("exact") = true, py::arg("nested") = true);
     // The host base64 coder (base/util.h over base/base64.h), reading the
     // bytes object in place: the text pb2json gives a bytes field, and what
     // json2pb makes of one (None where base64_decode refuses the text).

@@ -94,15 +94,76 @@ _PARSE_MODES = {torch.float64: 1, torch.float32: 2}
 _REDO_CAP = 64
 
 
-def json_parse_floats(text, dtype=torch.float64):
-    """uint8 device tensor of JSON text ``v,v,...,v`` (or ``[v,v,...]``) ->
-    float64 / float32 device tensor, the inverse of ``json_print_floats``.
-    Every element is converted exactly as the host's json2pb converts it:
-    the correctly rounded double (``base/decimal_to_double.h``, the code the
-    host reader runs; an integer literal becomes the double of its value),
-    and for float32 ``(float)`` of that double. The text never leaves HBM
-    (``gpu::DeviceParseNumberArrays``); the separators are found with torch
-    ops on the device.
+def _redo_text(t, offset):
+    """The number in the piece of `t` that starts at byte `offset`: fetched
+    in windows that double until the piece's comma (or the end) is in one."""
+    n, size = t.numel(), 256
+    while True:
+        piece = bytes(t[offset:offset + size].cpu().numpy())
+        cut = piece.find(b",")
+        if cut >= 0 or offset + size >= n:
+            return (piece if cut < 0 else piece[:cut]).strip(b" \t\n\r[]")
+        size *= 2
+
+
+def _parse_number_text(name, text, dtype, max_elems, nested):
+    """One call of gpu::DeviceParseNumberText on `text`: (values, depth,
+    row_ends or None). The redo elements are repaired from their offsets."""
+    require_gpu_tensor(text, "text")
+    if text.dtype != torch.uint8:
+        raise TypeError("text must be uint8")
+    if dtype not in _PARSE_MODES:
+        raise TypeError("dtype must be float32 or float64, not %s" % dtype)
+    dev = text.device
+    t = text.contiguous().view(-1)
+    n = t.numel()
+    if n >= (1 << 32) - 1:
+        raise ValueError("%s handles inputs below 4 GiB" % name)
+    if n == 0:
+        return torch.empty(0, dtype=dtype, device=dev), 0, None
+    # an element and its comma take two bytes at least; a row "[v]," four
+    cap = (n + 1) // 2 if max_elems is None else int(max_elems)
+    row_cap = min(n // 4 + 1, cap) if nested else 0
+    out = torch.empty(max(cap, 1), dtype=dtype, device=dev)
+    row_ends = torch.empty(max(row_cap, 1), dtype=torch.int32, device=dev) if nested else None
+    redo_cap = _REDO_CAP
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        while True:
+            redo = torch.empty(2 * redo_cap, dtype=torch.int32, device=dev)
+            (err, depth, count, rows, n_redo, first_bad), = native.gpu.device_json_parse_text(
+                [t.data_ptr()], [n], [_PARSE_MODES[dtype]], [out.data_ptr()], [0], [cap],
+                [row_ends.data_ptr() if nested else 0], [row_cap], [redo.data_ptr()], [redo_cap], dev.index or 0)
+            if err != 3:
+                break
+            redo_cap = n_redo  # every listed element is repaired below: list them all
+    if err == 1:
+        raise ValueError("%s: element %d is not a JSON number" % (name, first_bad))
+    if err == 5:
+        raise ValueError("%s: more than max_elems=%d elements (the text holds %d)" % (name, cap, count))
+    if err:
+        raise ValueError("%s: refused (bad arguments, code %d)" % (name, err))
+    if n_redo:
+        pairs = redo[:2 * n_redo].view(-1, 2).cpu().to(torch.int64) & 0xFFFFFFFF
+        vals = [native.json_parse_double(_redo_text(t, off)) for off in pairs[:, 1].tolist()]
+        out[pairs[:, 0].to(dev)] = torch.tensor(vals, dtype=torch.float64).to(dtype).to(dev)  # narrowed on the host
+    # the worst case is many times the result: do not pin it behind a view
+    values = out[:count] if 2 * count >= out.numel() else out[:count].clone()
+    return values, depth, (row_ends[:rows] if depth == 2 else None)
+
+
+def json_parse_floats(text, dtype=torch.float64, max_elems=None):
+    """uint8 device tensor of JSON text ``v,v,...,v`` (or ``[v,v,...]``,
+    whitespace allowed wherever JSON allows it) -> float64 / float32 device
+    tensor, the inverse of ``json_print_floats``. Every element is converted
+    exactly as the host's json2pb converts it: the correctly rounded double
+    (``base/decimal_to_double.h``, the code the host reader runs; an integer
+    literal becomes the double of its value), and for float32 ``(float)`` of
+    that double. The text never leaves HBM and the device finds the elements
+    itself (``gpu::DeviceParseNumberText``): one call, no separator table.
+
+    The output is sized for the worst case, ``(n + 1) // 2`` elements, unless
+    ``max_elems`` bounds it (ValueError when the text holds more).
 
     The rare elements a device lane does not decide (more than 19
     significant digits whose truncation leaves the rounding open) are
@@ -113,52 +174,38 @@ def json_parse_floats(text, dtype=torch.float64):
     The parser runs on a pool stream, not on torch's: the caller's current
     stream is synchronized before the call, and the values are complete when
     this returns."""
-    require_gpu_tensor(text, "text")
-    if text.dtype != torch.uint8:
-        raise TypeError("text must be uint8")
-    if dtype not in _PARSE_MODES:
-        raise TypeError("dtype must be float32 or float64, not %s" % dtype)
-    dev = text.device
-    t = text.contiguous().view(-1)
-    n = t.numel()
-    if n >= (1 << 32) - 1:
-        raise ValueError("json_parse_floats handles inputs below 4 GiB")
-    if n == 0:
-        return torch.empty(0, dtype=dtype, device=dev)
-    bracketed = n >= 2 and int(t[0]) == 0x5B and int(t[-1]) == 0x5D
-    commas = torch.nonzero(t == 0x2C).view(-1)
-    if bracketed and n == 2:
-        return torch.empty(0, dtype=dtype, device=dev)
-    first, last = (0, n - 1) if bracketed else (-1, n)  # -1: a separator before the first byte
-    seps64 = torch.cat([torch.tensor([first], dtype=torch.int64, device=dev), commas,
-                        torch.tensor([last], dtype=torch.int64, device=dev)])
-    # uint32 offsets in an int32 tensor (two's complement: -1 is 0xFFFFFFFF)
-    seps = torch.where(seps64 >= 1 << 31, seps64 - (1 << 32), seps64).to(torch.int32)
-    count = seps.numel() - 1
-    out = torch.zeros(count, dtype=dtype, device=dev)
-    redo = torch.zeros(_REDO_CAP, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        torch.cuda.current_stream(dev).synchronize()
-        cap = _REDO_CAP
-        while True:
-            (err, first_bad, n_redo), = native.gpu.device_json_parse_numbers(
-                [t.data_ptr()], [seps.data_ptr()], [count], [_PARSE_MODES[dtype]], [out.data_ptr()], [0],
-                [redo.data_ptr()], [cap], dev.index or 0)
-            if err != 3:
-                break
-            cap = n_redo  # every listed element is repaired below: list them all
-            redo = torch.zeros(cap, dtype=torch.int32, device=dev)
-    if err == 1:
-        raise ValueError("json_parse_floats: element %d is not a JSON number" % first_bad)
-    if err:
-        raise ValueError("json_parse_floats: refused (bad arguments, code %d)" % err)
-    if n_redo:
-        idx = redo[:n_redo].to(torch.int64)
-        begins = (seps64[idx] + 1).tolist()
-        ends = seps64[idx + 1].tolist()
-        vals = [native.json_parse_double(bytes(t[b:e].cpu().numpy()).strip(b" \t\n\r")) for b, e in zip(begins, ends)]
-        out[idx] = torch.tensor(vals, dtype=torch.float64).to(dtype).to(dev)  # narrowed on the host
-    return out
+    return _parse_number_text("json_parse_floats", text, dtype, max_elems, False)[0]
+
+
+def json_parse_float_rows(text, dtype=torch.float64, ragged=False, max_elems=None):
+    """uint8 device tensor of JSON text ``[[v,...],[v,...],...]`` -> a 2-D
+    float64 / float32 device tensor, one row per inner array: the batch shape
+    of http+json model APIs, parsed in HBM by the same single call as
+    ``json_parse_floats`` (the device finds the row boundaries too). It
+    round-trips with ``json_print_floats`` applied per row.
+
+    Rows of different lengths raise ValueError naming the first row that
+    differs from row 0; with ``ragged=True`` the result is ``(values,
+    row_ends)`` instead: all elements in order and an int64 tensor with the
+    number of elements in rows 0..r. ``[ ]`` is a tensor of shape (0, 0)."""
+    name = "json_parse_float_rows"
+    values, depth, row_ends = _parse_number_text(name, text, dtype, max_elems, True)
+    if depth != 2:
+        if values.numel():
+            raise ValueError(name + ": the text is not an array of arrays")
+        row_ends = torch.empty(0, dtype=torch.int32, device=values.device)
+    if ragged:
+        return values, row_ends.to(torch.int64)
+    rows = row_ends.numel()
+    if rows == 0:
+        return values.view(0, 0)
+    ends = row_ends.cpu().to(torch.int64)
+    sizes = torch.diff(ends, prepend=torch.zeros(1, dtype=torch.int64))
+    odd = torch.nonzero(sizes != sizes[0]).view(-1)
+    if odd.numel():
+        r = int(odd[0])
+        raise ValueError("%s: row %d has %d elements, row 0 has %d" % (name, r, int(sizes[r]), int(sizes[0])))
+    return values.view(rows, int(sizes[0]))
 
 
 def base64_encode(data):
