@@ -6,6 +6,7 @@
 
 #include "base/buf.h"
 #include "base/flags.h"
+#include "base/pb_rows.h"
 #include "base/pool.h"
 #include "gpu/codec_batch.h"
 #include "gpu/gpu.h"
@@ -27,6 +28,7 @@ namespace {
 std::atomic<int64_t> g_encodes{0}, g_enc_bytes{0}, g_enc_out{0}, g_decodes{0}, g_dec_bytes{0}, g_bad_tables{0},
     g_dec_err{0}, g_scans{0}, g_runs{0}, g_run_bytes{0}, g_run_elems{0}, g_run_err{0};
 std::atomic<int64_t> g_built{0}, g_built_fields{0}, g_built_bytes{0}, g_build_err{0};
+std::atomic<int64_t> g_built_row_jobs{0}, g_built_rows{0}, g_built_row_bytes{0};
 
 uint32_t varint_len(uint64_t v) {
     uint32_t n = 1;
@@ -447,8 +449,138 @@ int DeviceEncodePackedRuns(DevicePackedEncodeRun* runs, int n, int device) {
     return rc;
 }
 
+namespace {
+
+// What the host can check of a rows job without reading device memory.
+bool rows_job_ok(const DeviceRowsJob& j) {
+    if (pb_rows::WorstCaseBytes(j.number, j.inner, j.kind, j.count, j.rows) == 0) return false;
+    if (!j.row_ends || ((uintptr_t)j.row_ends & 3) != 0 || !j.dst) return false;
+    return j.count == 0 || (j.src && ((uintptr_t)j.src & (pb_rows::SourceBytes(j.kind) - 1)) == 0);
+}
+
+}  // namespace
+
+uint64_t DeviceRowsWorstCaseBytes(const DeviceRowsJob& job) {
+    return pb_rows::WorstCaseBytes(job.number, job.inner, job.kind, job.count, job.rows);
+}
+
+// The jobs go to a pool stream of their own rather than into the cross-RPC
+// codec batch: a rows job brings scratch sized by its rows and groups (three
+// words per row), which the batch's recycled tables do not hold, and its
+// seven launches share nothing with the small codec jobs of other RPCs.
+int DeviceBuildRows(DeviceRowsJob* jobs, int n, int device) {
+    if (n <= 0) return 0;
+    if (!jobs || device < 0) return -1;
+    std::vector<int> live;  // the jobs that go to the device, in order
+    uint64_t nchunks = 0, nrblocks = 0, ngroups = 0, nrows = 0;
+    for (int i = 0; i < n; ++i) {
+        DeviceRowsJob& j = jobs[i];
+        j.len = 0;
+        j.first_bad = 0xFFFFFFFFu;
+        j.err = 0;
+        if (!rows_job_ok(j)) {
+            j.err = 2;
+            g_build_err.fetch_add(1, std::memory_order_relaxed);
+            continue;
+        }
+        nchunks += (j.count + kPbRowsChunkElems - 1) / kPbRowsChunkElems;
+        nrblocks += (j.rows + kPbRowsBlockRows - 1) / kPbRowsBlockRows;
+        if (pb_rows::IsVarintKind(j.kind)) ngroups += j.count / kPbRowsGroupElems + 2;
+        nrows += j.rows;
+        live.push_back(i);
+    }
+    if (live.empty()) return 0;
+    // one grid per pass, 32-bit table indices
+    if (nchunks > 0x7FFFFFFFull || nrblocks > 0x7FFFFFFFull || ngroups > 0x7FFFFFFFull || nrows > 0x7FFFFFFFull) {
+        return -1;
+    }
+    const size_t nlive = live.size();
+    PinnedBlock tables(nlive * (sizeof(PbRowsJob) + sizeof(PbRowsResult)));
+    const size_t jobs_bytes = nlive * sizeof(PbRowsJob);  // first: the most aligned
+    const size_t words = (size_t)ngroups + 3 * (size_t)nrows + (size_t)nrblocks + 2 * nlive;
+    HbmBlock scratch(jobs_bytes + words * sizeof(uint32_t), device);
+    if (!tables || !scratch) return -1;
+    PbRowsJob* tj = tables.as<PbRowsJob>();
+    PbRowsResult* tr = reinterpret_cast<PbRowsResult*>(tj + nlive);
+    PbRowsTables t;
+    for (size_t k = 0; k < nlive; ++k) {
+        const DeviceRowsJob& j = jobs[live[k]];
+        PbRowsJob& o = tj[k];
+        o.src = j.src;
+        o.row_ends = j.row_ends;
+        o.dst = static_cast<uint8_t*>(j.dst);
+        o.cap = j.cap;
+        o.count = (uint32_t)j.count;
+        o.rows = (uint32_t)j.rows;
+        o.number = j.number;
+        o.inner = j.inner;
+        o.kind = j.kind;
+        o.first_chunk = t.nchunks;
+        o.nchunks = (uint32_t)((j.count + kPbRowsChunkElems - 1) / kPbRowsChunkElems);
+        o.first_rblock = t.nrblocks;
+        o.first_row = t.nrows;
+        o.first_group = t.ngroups;
+        t.nchunks += o.nchunks;
+        t.nrblocks += (uint32_t)((j.rows + kPbRowsBlockRows - 1) / kPbRowsBlockRows);
+        t.nrows += o.rows;
+        if (pb_rows::IsVarintKind(j.kind)) t.ngroups += o.count / kPbRowsGroupElems + 2;
+        tr[k] = PbRowsResult{0, 0xFFFFFFFFu, 0};
+    }
+    t.jobs = tj;
+    t.njobs = (int)nlive;
+    t.jobs_dev = scratch.as<PbRowsJob>();
+    t.groups = reinterpret_cast<uint32_t*>(static_cast<char*>(scratch.p) + jobs_bytes);
+    t.row_size = t.groups + t.ngroups;
+    t.row_pay = t.row_size + t.nrows;
+    t.row_delta = t.row_pay + t.nrows;
+    t.block_off = t.row_delta + t.nrows;
+    t.first_bad = t.block_off + t.nrblocks + nlive;
+    t.res = tr;
+    if (RunOnPoolStream(device, [&](hipStream_t s) { return LaunchPbRowsBuild(t, s); }) != 0) return -1;
+    for (size_t k = 0; k < nlive; ++k) {
+        DeviceRowsJob& j = jobs[live[k]];
+        j.len = tr[k].len;
+        j.err = tr[k].err;
+        if (j.err == 1) j.first_bad = tr[k].first_bad;
+        if (j.err) {
+            g_build_err.fetch_add(1, std::memory_order_relaxed);
+            continue;
+        }
+        g_built_row_jobs.fetch_add(1, std::memory_order_relaxed);
+        g_built_rows.fetch_add((int64_t)j.rows, std::memory_order_relaxed);
+        g_built_row_bytes.fetch_add((int64_t)j.len, std::memory_order_relaxed);
+    }
+    return 0;
+}
+
+int BuildDeviceRows(const DeviceRowsJob& job, Buf* out, int device) {
+    const uint64_t worst = DeviceRowsWorstCaseBytes(job);
+    if (!out || worst == 0) {
+        g_build_err.fetch_add(1, std::memory_order_relaxed);
+        return 2;
+    }
+    const size_t cap = (size_t)std::max<uint64_t>(worst, 16);
+    HbmBlock dst(cap, device);
+    if (!dst) return -1;
+    DeviceRowsJob j = job;
+    j.dst = dst.p;
+    j.cap = cap;
+    const int rc = DeviceBuildRows(&j, 1, device);
+    if (rc != 0 || j.err != 0) return rc != 0 ? -1 : j.err;
+    ArenaBlock* a = new ArenaBlock{cap, device};
+    if (AppendDevice(out, dst.p, (size_t)j.len, device, free_arena_block, a) != 0) {
+        delete a;
+        return -1;
+    }
+    dst.release();  // the Buf block owns it now
+    return 0;
+}
+
 DeviceCodecStats GetDeviceCodecStats() {
     DeviceCodecStats s;
+    s.built_row_jobs = g_built_row_jobs.load();
+    s.built_rows = g_built_rows.load();
+    s.built_row_bytes = g_built_row_bytes.load();
     s.built_messages = g_built.load();
     s.built_fields = g_built_fields.load();
     s.built_bytes = g_built_bytes.load();

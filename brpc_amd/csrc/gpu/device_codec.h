@@ -141,12 +141,61 @@ struct DevicePackedEncodeRun {
 };
 int DeviceEncodePackedRuns(DevicePackedEncodeRun* runs, int n, int device);
 
+// ---- rows: a ragged batch in device memory (all rows' elements back to back
+// plus the table of row ends that gpu::DeviceParseNumberText writes) -> the
+// occurrences of one repeated field, one per row:
+//   message Row   { repeated float v = 2 [packed = true]; }
+//   message Batch { repeated Row rows = 4; repeated bytes blobs = 5; }
+// `rows` is number 4, inner 2, kind 8; `blobs` is number 5, inner 0, kind
+// bytes. The wire rules (and the empty-row rules) are base/pb_rows.h;
+// pb::SerializeRows (pb/rows.h) is the host twin. Sub-messages with several
+// fields and rows of rows are not built.
+//
+// The output is a sequence of occurrences of one field, which is a valid
+// message by itself; protobuf concatenation is merge, so a caller composes
+// Batch by appending a BuildDeviceMessage block (the scalar and flat fields)
+// and a BuildDeviceRows block to the same Buf.
+constexpr uint32_t kDeviceFieldFixed32 = 8;  // 4-byte elements: packed float / fixed32 / sfixed32
+constexpr uint32_t kDeviceFieldFixed64 = 9;  // 8-byte elements: packed double / fixed64 / sfixed64
+struct DeviceRowsJob {
+    uint32_t number = 0;  // the repeated field, 1 .. 2^29-1
+    uint32_t inner = 0;   // the packed field inside each row's sub-message; 0: no wrapper (kind bytes only)
+    uint32_t kind = 0;    // gpu::PbRunKind, kDeviceFieldBytes, kDeviceFieldFixed32 / 64
+    const void* src = nullptr;           // device; all rows' elements, naturally aligned for the kind
+    uint64_t count = 0;                  // elements at src
+    const uint32_t* row_ends = nullptr;  // device, 4-byte aligned: row_ends[r] = elements in rows 0..r
+    uint64_t rows = 0;                   // >= 1; equal neighbours in row_ends are an empty row
+    void* dst = nullptr;                 // device, any alignment
+    uint64_t cap = 0;
+    uint64_t len = 0;  // out: serialized size (with err 3: the size it needs)
+    uint32_t first_bad = 0xFFFFFFFFu;  // out, with err 1
+    // out: 0 built; 1 row_ends decreases at row first_bad, or its last entry
+    // is not count (first_bad = rows - 1): found on the device, the host never
+    // reads row_ends; 2 refused before any launch (a null pointer with a
+    // nonzero size, bad number / inner / kind, inner 0 with a kind other than
+    // bytes, misaligned src or row_ends, rows 0, count or the worst case above
+    // 2^32-1); 3 longer than cap; 4 a source changed while the rows were
+    // built. With 1 and 3 dst is untouched; no store ever goes beyond cap.
+    int err = 0;
+};
+// Host only: the bytes a destination needs for any values; 0 when the job
+// would be refused for its fields, rows or sizes.
+uint64_t DeviceRowsWorstCaseBytes(const DeviceRowsJob& job);
+// All jobs share one sequence of launches on a pool stream and one wait.
+// Returns -1 only on a device error; per-job codes in jobs[i].err.
+int DeviceBuildRows(DeviceRowsJob* jobs, int n, int device);
+// Builds job's rows (its dst / cap are ignored) into a fresh arena block of
+// the worst-case size and appends exactly their bytes to *out as one DEVICE
+// block, as BuildDeviceMessage does. 0, a DeviceRowsJob::err code, or -1.
+int BuildDeviceRows(const DeviceRowsJob& job, Buf* out, int device);
+
 struct DeviceCodecStats {
     int64_t encodes = 0, encoded_bytes = 0, encoded_out_bytes = 0;
     int64_t decodes = 0, decoded_bytes = 0, bad_tables = 0, decode_errors = 0;
     int64_t scans = 0;
     int64_t packed_runs = 0, packed_bytes = 0, packed_elems = 0, packed_errors = 0;
     int64_t built_messages = 0, built_fields = 0, built_bytes = 0, build_errors = 0;
+    int64_t built_row_jobs = 0, built_rows = 0, built_row_bytes = 0;  // failed row jobs count in build_errors
 };
 DeviceCodecStats GetDeviceCodecStats();
 

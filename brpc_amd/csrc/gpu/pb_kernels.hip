@@ -20,6 +20,7 @@
 // the lane walks them) and writes its field rows with 16-byte stores.
 #include <hip/hip_runtime.h>
 
+#include "base/pb_rows.h"
 #include "gpu/kernels.h"
 #include "gpu/device_pb.h"
 
@@ -770,7 +771,444 @@ __global__ void __launch_bounds__(kRunThreads) pb_msg_place_kernel(const PbMsgCh
     copy_out_aligned(dst, image, sh, total);
 }
 
+// ------------------------------------------------------------- row builder
+// One flat array + row ends -> the occurrences of one repeated field
+// (kernels.h: init, size, prefix, rows, prefix, heads, place; the wire rules
+// are base/pb_rows.h). No lane walks a row: a row's payload size is the
+// difference of two byte prefixes, each a group prefix plus at most 63
+// element sizes.
+constexpr int kRowsRounds = kPbRowsChunkElems / kRunThreads;
+constexpr uint32_t kRowsFewRows = 16;  // a chunk meeting at most this many rows leaves segment by segment
+constexpr uint32_t kNoRow = 0xFFFFFFFFu;
+
+// The job owning chunk (or row block) x: the last one that starts at or
+// before it (a job without chunks shares its start with the next job).
+__device__ __forceinline__ int rows_job_of(const PbRowsJob* jobs, int njobs, uint32_t x, bool by_rblock) {
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        const uint32_t first = by_rblock ? jobs[mid].first_rblock : jobs[mid].first_chunk;
+        if (first <= x) {
+            lo = mid;
+        } else {
+            hi = mid - 1;
+        }
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(64) pb_rows_init_kernel(const PbRowsJob* __restrict__ jobs, int njobs,
+                                                          PbRowsJob* __restrict__ jobs_dev,
+                                                          uint32_t* __restrict__ groups,
+                                                          uint32_t* __restrict__ first_bad) {
+    const int j = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (j >= njobs) return;
+    const PbRowsJob job = jobs[j];
+    jobs_dev[j] = job;
+    first_bad[j] = kNoRow;
+    if (pb_rows::IsVarintKind(job.kind)) {
+        // the group behind the last element (written again by the size pass
+        // when it holds elements) and the one whose prefix is the total
+        const uint32_t g = job.first_group + job.count / kPbRowsGroupElems;
+        groups[g] = 0;
+        groups[g + 1] = 0;
+    }
+}
+
+__global__ void __launch_bounds__(kRunThreads) pb_rows_size_kernel(const PbRowsJob* __restrict__ jobs, int njobs,
+                                                                   uint32_t* __restrict__ groups) {
+    const PbRowsJob job = jobs[rows_job_of(jobs, njobs, blockIdx.x, false)];
+    if (!pb_rows::IsVarintKind(job.kind)) return;
+    const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbRowsChunkElems;
+    const uint32_t n = job.count - cs < kPbRowsChunkElems ? job.count - cs : kPbRowsChunkElems;
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    // a wave's 64 elements of a round are one group; all loads go out first
+    uint64_t v[kRowsRounds];
+#pragma unroll
+    for (int r = 0; r < kRowsRounds; ++r) {
+        const uint32_t i = (uint32_t)r * kRunThreads + t;
+        v[r] = i < n ? pb_rows::WireValue(job.src, (uint64_t)cs + i, job.kind) : 0;
+    }
+#pragma unroll
+    for (int r = 0; r < kRowsRounds; ++r) {
+        const uint32_t i = (uint32_t)r * kRunThreads + t;
+        uint32_t len = i < n ? run_varint_len(v[r]) : 0;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) len += __shfl_xor(len, off, 64);
+        const uint32_t g0 = (uint32_t)r * kRunThreads + wave * 64;  // the group's first element in the chunk
+        if (lane == 0 && g0 < n) groups[job.first_group + (cs + g0) / kPbRowsGroupElems] = len;
+    }
+}
+
+// Encoded bytes of elements [0, e) of the job, e <= count.
+__device__ __forceinline__ uint32_t rows_bytes_before(const PbRowsJob& job, const uint32_t* groups, uint32_t e) {
+    if (!pb_rows::IsVarintKind(job.kind)) return e * pb_rows::SourceBytes(job.kind);
+    uint32_t b = groups[job.first_group + e / kPbRowsGroupElems] - groups[job.first_group];
+    for (uint32_t i = e & ~(kPbRowsGroupElems - 1); i < e; ++i) {
+        b += run_varint_len(pb_rows::WireValue(job.src, i, job.kind));
+    }
+    return b;
+}
+
+// Sum of v over the workgroup's 256 lanes (every lane calls it), and the sum
+// over the lanes before this one in *before.
+__device__ __forceinline__ uint32_t rows_block_scan(uint32_t v, uint32_t* wave_tot, uint32_t* before) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(incl, off, 64);
+        if (lane >= (uint32_t)off) incl += y;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    uint32_t sum = 0, mine = incl - v;
+#pragma unroll
+    for (uint32_t k = 0; k < kPbRowsBlockRows / 64; ++k) {
+        const uint32_t x = wave_tot[k];
+        if (k < wave) mine += x;
+        sum += x;
+    }
+    *before = mine;
+    return sum;
+}
+
+__global__ void __launch_bounds__(kPbRowsBlockRows) pb_rows_measure_kernel(const PbRowsJob* __restrict__ jobs,
+                                                                           int njobs,
+                                                                           const uint32_t* __restrict__ groups,
+                                                                           uint32_t* __restrict__ row_size,
+                                                                           uint32_t* __restrict__ row_pay,
+                                                                           uint32_t* __restrict__ row_delta,
+                                                                           uint32_t* __restrict__ block_off,
+                                                                           uint32_t* __restrict__ first_bad) {
+    __shared__ uint32_t wave_tot[kPbRowsBlockRows / 64];
+    const int j = rows_job_of(jobs, njobs, blockIdx.x, true);
+    const PbRowsJob job = jobs[j];
+    const uint32_t block = blockIdx.x - job.first_rblock;
+    const uint64_t r64 = (uint64_t)block * kPbRowsBlockRows + threadIdx.x;
+    const uint32_t r = (uint32_t)r64;
+    uint32_t size = 0;
+    if (r64 < job.rows) {
+        uint32_t s = r ? job.row_ends[r - 1] : 0, e = job.row_ends[r];
+        if (e < s || (r + 1 == job.rows && e != job.count)) atomicMin(&first_bad[j], r);
+        // a malformed table gets nothing written; until then it must not make
+        // a lane read past the source
+        s = s < job.count ? s : job.count;
+        e = e < job.count ? e : job.count;
+        e = e < s ? s : e;
+        const uint32_t before = rows_bytes_before(job, groups, s);
+        const uint32_t p = rows_bytes_before(job, groups, e) - before;
+        size = p + pb_rows::HeaderBytes(job.number, job.inner, job.kind, e - s, p);
+        const uint32_t at = job.first_row + r;
+        row_size[at] = size;
+        row_pay[at] = p;
+        row_delta[at] = before;
+    }
+    uint32_t unused;
+    const uint32_t sum = rows_block_scan(size, wave_tot, &unused);
+    if (threadIdx.x == 0) {
+        // the job's blocks, then one entry that becomes its total under the scan
+        const uint32_t at = blockIdx.x + (uint32_t)j;
+        block_off[at] = sum;
+        if ((uint64_t)(block + 1) * kPbRowsBlockRows >= job.rows) block_off[at + 1] = 0;
+    }
+}
+
+// The job's serialized size, from the scanned block sums.
+__device__ __forceinline__ uint32_t rows_job_total(const PbRowsJob& job, int j, const uint32_t* block_off) {
+    const uint32_t first = job.first_rblock + (uint32_t)j;
+    const uint32_t nblocks = (uint32_t)(((uint64_t)job.rows + kPbRowsBlockRows - 1) / kPbRowsBlockRows);
+    return block_off[first + nblocks] - block_off[first];
+}
+
+__global__ void __launch_bounds__(kPbRowsBlockRows) pb_rows_heads_kernel(const PbRowsJob* __restrict__ jobs, int njobs,
+                                                                         const uint32_t* __restrict__ row_size,
+                                                                         const uint32_t* __restrict__ row_pay,
+                                                                         uint32_t* __restrict__ row_delta,
+                                                                         const uint32_t* __restrict__ block_off,
+                                                                         const uint32_t* __restrict__ first_bad,
+                                                                         PbRowsResult* __restrict__ res) {
+    __shared__ uint32_t wave_tot[kPbRowsBlockRows / 64];
+    const int j = rows_job_of(jobs, njobs, blockIdx.x, true);
+    const PbRowsJob job = jobs[j];
+    const uint64_t r64 = (uint64_t)(blockIdx.x - job.first_rblock) * kPbRowsBlockRows + threadIdx.x;
+    const bool live = r64 < job.rows;
+    const uint32_t r = (uint32_t)r64;
+    const uint32_t bad = first_bad[j];
+    const uint32_t total = rows_job_total(job, j, block_off);
+    const bool ok = bad == kNoRow && total <= job.cap;
+    if (r64 == 0) res[j] = PbRowsResult{total, bad, bad != kNoRow ? 1 : (total > job.cap ? 3 : 0)};
+    if (!ok) return;  // the whole workgroup
+    const uint32_t at = job.first_row + r;
+    // the row's offset: the blocks before this one, then the rows before it here
+    uint32_t off;
+    rows_block_scan(live ? row_size[at] : 0, wave_tot, &off);
+    if (!live) return;
+    off += block_off[blockIdx.x + (uint32_t)j] - block_off[job.first_rblock + (uint32_t)j];
+    const uint32_t nelems = job.row_ends[r] - (r ? job.row_ends[r - 1] : 0);
+    const uint32_t p = row_pay[at];
+    const uint32_t hn = pb_rows::HeaderBytes(job.number, job.inner, job.kind, nelems, p);
+    if ((uint64_t)off + hn + p > total) return;  // row_ends changed since the rows pass: nothing leaves the message
+    pb_rows::PutHeader(job.dst + off, job.number, job.inner, job.kind, nelems, p);
+    row_delta[at] = off + hn - row_delta[at];
+}
+
+// res[j].err = 4 below: a source (or row_ends) changed under the builder's
+// hands, seen as a size that no longer matches or a store that would leave
+// the message.
+__global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRowsJob* __restrict__ jobs, int njobs,
+                                                                    const uint32_t* __restrict__ groups,
+                                                                    const uint32_t* __restrict__ block_off,
+                                                                    const uint32_t* __restrict__ row_delta,
+                                                                    const uint32_t* __restrict__ first_bad,
+                                                                    PbRowsResult* __restrict__ res) {
+    __shared__ u32x4 image16[kMsgImage16];
+    // few rows: the position of every element in the image (and the total);
+    // many rows: the row of every element, relative to the chunk's first
+    __shared__ uint32_t aux[kPbRowsChunkElems + 1];
+    __shared__ uint32_t wave_tot[kRowsRounds][kRunThreads / 64];
+    __shared__ uint32_t wave_max[kRunThreads / 64];
+    uint8_t* image = reinterpret_cast<uint8_t*>(image16);
+    const int j = rows_job_of(jobs, njobs, blockIdx.x, false);
+    const PbRowsJob job = jobs[j];
+    if (first_bad[j] != kNoRow) return;
+    const uint32_t total = rows_job_total(job, j, block_off);
+    if (total > job.cap) return;
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbRowsChunkElems;
+    const uint32_t n = job.count - cs < kPbRowsChunkElems ? job.count - cs : kPbRowsChunkElems;
+    const uint32_t ce = cs + n;
+    const uint32_t* ends = job.row_ends;
+    // the rows that hold the chunk's first and last element
+    uint32_t lo = 0, hi = job.rows - 1;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (ends[mid] > cs) {
+            hi = mid;
+        } else {
+            lo = mid + 1;
+        }
+    }
+    const uint32_t r_lo = lo;
+    hi = job.rows - 1;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (ends[mid] >= ce) {
+            hi = mid;
+        } else {
+            lo = mid + 1;
+        }
+    }
+    const uint32_t r_hi = lo;
+
+    const bool varints = pb_rows::IsVarintKind(job.kind);
+    const uint32_t w = pb_rows::SourceBytes(job.kind);
+    uint64_t vals[kRowsRounds];
+#pragma unroll
+    for (int r = 0; r < kRowsRounds; ++r) {
+        const uint32_t i = (uint32_t)r * kRunThreads + t;
+        vals[r] = i < n ? pb_rows::WireValue(job.src, (uint64_t)cs + i, job.kind) : 0;
+    }
+    // every element's size and its position among the chunk's bytes
+    uint32_t lens[kRowsRounds], poss[kRowsRounds];
+    uint32_t before_cs, want, bytes = 0;
+    if (varints) {
+        const uint32_t g0 = groups[job.first_group];
+        before_cs = groups[job.first_group + cs / kPbRowsGroupElems] - g0;
+        const uint32_t gend = ce == job.count ? job.count / kPbRowsGroupElems + 1 : ce / kPbRowsGroupElems;
+        want = groups[job.first_group + gend] - g0 - before_cs;
+#pragma unroll
+        for (int r = 0; r < kRowsRounds; ++r) {
+            const uint32_t i = (uint32_t)r * kRunThreads + t;
+            lens[r] = i < n ? run_varint_len(vals[r]) : 0;
+            uint32_t incl = lens[r];
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t y = __shfl_up(incl, off, 64);
+                if (lane >= (uint32_t)off) incl += y;
+            }
+            poss[r] = incl - lens[r];
+            if (lane == 63) wave_tot[r][wave] = incl;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < kRowsRounds; ++r) {
+            poss[r] += bytes;
+#pragma unroll
+            for (int k = 0; k < kRunThreads / 64; ++k) {
+                const uint32_t x = wave_tot[r][k];
+                if ((uint32_t)k < wave) poss[r] += x;
+                bytes += x;
+            }
+        }
+    } else {
+        before_cs = cs * w;
+        want = bytes = n * w;
+#pragma unroll
+        for (int r = 0; r < kRowsRounds; ++r) {
+            const uint32_t i = (uint32_t)r * kRunThreads + t;
+            lens[r] = i < n ? w : 0;
+            poss[r] = i * w;
+        }
+    }
+    if (bytes != want) {
+        if (t == 0) res[j].err = 4;
+        return;
+    }
+    const uint32_t* delta = row_delta + job.first_row;
+
+    if (r_hi - r_lo < kRowsFewRows) {
+        // the image sits at the 16-byte phase of the chunk's first byte in dst
+        // (the first row's segment always leaves aligned, a chunk inside one
+        // row entirely)
+        uint32_t sh = (uint32_t)((uintptr_t)(job.dst + (uint32_t)(delta[r_lo] + before_cs)) & 15);
+        if (sh % w) sh = 0;
+#pragma unroll
+        for (int r = 0; r < kRowsRounds; ++r) {
+            const uint32_t i = (uint32_t)r * kRunThreads + t;
+            if (i >= n) continue;
+            uint8_t* o = image + sh + poss[r];
+            if (varints) {
+                uint64_t v = vals[r];
+                for (uint32_t k = 0; k < lens[r]; ++k) {
+                    o[k] = (uint8_t)((v & 0x7f) | (k + 1 < lens[r] ? 0x80 : 0));
+                    v >>= 7;
+                }
+                aux[i] = poss[r];
+            } else if (w == 1) {
+                *o = (uint8_t)vals[r];
+            } else if (w == 4) {
+                *reinterpret_cast<uint32_t*>(o) = (uint32_t)vals[r];
+            } else {
+                *reinterpret_cast<uint64_t*>(o) = vals[r];
+            }
+        }
+        if (t == 0 && varints) aux[n] = bytes;
+        __syncthreads();
+        for (uint32_t row = r_lo; row <= r_hi; ++row) {
+            uint32_t s = row ? ends[row - 1] : 0, e = ends[row];
+            s = s > cs ? s : cs;
+            e = e < ce ? e : ce;
+            if (e <= s) continue;
+            const uint32_t a = varints ? aux[s - cs] : (s - cs) * w;
+            const uint32_t b = varints ? aux[e - cs] : (e - cs) * w;
+            const uint32_t off = delta[row] + before_cs + a;
+            if (b < a || (uint64_t)off + (b - a) > total) {
+                if (t == 0) res[j].err = 4;
+                continue;
+            }
+            uint8_t* d = job.dst + off;
+            if (((uint32_t)(uintptr_t)d & 15) == ((sh + a) & 15)) {
+                copy_out_aligned(d, image, sh + a, b - a);
+            } else {
+                copy_out(d, image + sh + a, b - a);
+            }
+        }
+        return;
+    }
+
+    // many rows: every nonempty row that starts in the chunk (the first may
+    // start before it) marks its first element; a max-scan spreads the marks
+    for (uint32_t i = t; i < n; i += kRunThreads) aux[i] = 0;
+    __syncthreads();
+    for (uint64_t row = (uint64_t)r_lo + t; row <= r_hi; row += kRunThreads) {
+        const uint32_t s = row ? ends[row - 1] : 0, e = ends[row];
+        if (e <= s) continue;
+        const uint32_t i = s > cs ? s - cs : 0;
+        if (i < n) aux[i] = (uint32_t)(row - r_lo) + 1;
+    }
+    __syncthreads();
+    {
+        constexpr uint32_t kPer = kPbRowsChunkElems / kRunThreads;  // consecutive elements per thread
+        uint32_t m[kPer], run = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kPer; ++k) {
+            const uint32_t i = t * kPer + k;
+            const uint32_t x = i < n ? aux[i] : 0;
+            run = run > x ? run : x;
+            m[k] = run;
+        }
+        uint32_t incl = run;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t y = __shfl_up(incl, off, 64);
+            if (lane >= (uint32_t)off && y > incl) incl = y;
+        }
+        if (lane == 63) wave_max[wave] = incl;
+        uint32_t carry = __shfl_up(incl, 1, 64);
+        if (lane == 0) carry = 0;
+        __syncthreads();
+        for (uint32_t k = 0; k < wave; ++k) carry = carry > wave_max[k] ? carry : wave_max[k];
+#pragma unroll
+        for (uint32_t k = 0; k < kPer; ++k) {
+            const uint32_t i = t * kPer + k;
+            if (i < n) aux[i] = m[k] > carry ? m[k] : carry;
+        }
+    }
+    __syncthreads();
+    bool changed = false;
+#pragma unroll
+    for (int r = 0; r < kRowsRounds; ++r) {
+        const uint32_t i = (uint32_t)r * kRunThreads + t;
+        if (i >= n) continue;
+        const uint32_t mark = aux[i];
+        if (mark == 0 || mark - 1 > r_hi - r_lo) {
+            changed = true;
+            continue;
+        }
+        const uint32_t off = delta[r_lo + (mark - 1)] + before_cs + poss[r];
+        if ((uint64_t)off + lens[r] > total) {
+            changed = true;
+            continue;
+        }
+        uint8_t* o = job.dst + off;
+        uint64_t v = vals[r];
+        if (varints) {
+            for (uint32_t k = 0; k < lens[r]; ++k) {
+                o[k] = (uint8_t)((v & 0x7f) | (k + 1 < lens[r] ? 0x80 : 0));
+                v >>= 7;
+            }
+        } else {
+            for (uint32_t k = 0; k < w; ++k) {
+                o[k] = (uint8_t)v;
+                v >>= 8;
+            }
+        }
+    }
+    if (changed) res[j].err = 4;
+}
+
 }  // namespace
+
+int LaunchPbRowsBuild(const PbRowsTables& t, hipStream_t s) {
+    if (t.njobs <= 0) return 0;
+    if (!t.jobs || !t.jobs_dev || !t.row_size || !t.row_pay || !t.row_delta || !t.block_off || !t.first_bad || !t.res ||
+        t.nrblocks == 0 || (t.ngroups > 0 && !t.groups) || t.ngroups > 0x7FFFFFFFu) {
+        return -1;
+    }
+    hipLaunchKernelGGL(pb_rows_init_kernel, dim3((unsigned)(t.njobs + 63) / 64), dim3(64), 0, s, t.jobs, t.njobs,
+                       t.jobs_dev, t.groups, t.first_bad);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (t.ngroups > 0) {
+        if (t.nchunks > 0) {
+            hipLaunchKernelGGL(pb_rows_size_kernel, dim3(t.nchunks), dim3(kRunThreads), 0, s, t.jobs_dev, t.njobs,
+                               t.groups);
+            if (hipGetLastError() != hipSuccess) return -1;
+        }
+        if (LaunchPbRunPrefix(t.groups, (int)t.ngroups, s) != 0) return -1;
+    }
+    hipLaunchKernelGGL(pb_rows_measure_kernel, dim3(t.nrblocks), dim3(kPbRowsBlockRows), 0, s, t.jobs_dev, t.njobs,
+                       t.groups, t.row_size, t.row_pay, t.row_delta, t.block_off, t.first_bad);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (LaunchPbRunPrefix(t.block_off, (int)(t.nrblocks + (uint32_t)t.njobs), s) != 0) return -1;
+    hipLaunchKernelGGL(pb_rows_heads_kernel, dim3(t.nrblocks), dim3(kPbRowsBlockRows), 0, s, t.jobs_dev, t.njobs,
+                       t.row_size, t.row_pay, t.row_delta, t.block_off, t.first_bad, t.res);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (t.nchunks == 0) return 0;
+    hipLaunchKernelGGL(pb_rows_place_kernel, dim3(t.nchunks), dim3(kRunThreads), 0, s, t.jobs_dev, t.njobs, t.groups,
+                       t.block_off, t.row_delta, t.first_bad, t.res);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 int LaunchPbMsgEncode(const PbMsgTables& t, hipStream_t s) {
     if (t.nmsgs <= 0) return 0;

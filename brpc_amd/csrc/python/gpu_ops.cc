@@ -78,6 +78,8 @@ struct DevBuf {
 
 // (number, kind, device pointer, count) rows of device_build_message
 typedef std::tuple<uint32_t, uint32_t, uintptr_t, uint64_t> MessageFieldRow;
+// (number, inner, kind, src, count, row_ends, rows, dst, cap) rows of device_build_rows
+typedef std::tuple<uint32_t, uint32_t, uint32_t, uintptr_t, uint64_t, uintptr_t, uint64_t, uintptr_t, uint64_t> RowsJobRow;
 std::vector<gpu::DeviceMessageField> message_fields(const std::vector<MessageFieldRow>& rows) {
     std::vector<gpu::DeviceMessageField> fs(rows.size());
     for (size_t i = 0; i < rows.size(); ++i) {
@@ -264,6 +266,41 @@ void bind_gpu_ops(py::module_& g) {
         std::vector<gpu::DeviceMessageField> fs = message_fields(fields);
         return gpu::DeviceMessageWorstCaseBytes(fs.data(), (int)fs.size());
     });
+    // Ragged batches: jobs = [(number, inner, kind, src, count, row_ends,
+    // rows, dst, cap)], src / row_ends / dst device pointers -> [(len, err,
+    // first_bad)] (gpu::DeviceBuildRows; all jobs share one launch sequence).
+    g.def("device_build_rows", [](const std::vector<RowsJobRow>& jobs, int device) {
+        std::vector<gpu::DeviceRowsJob> js(jobs.size());
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            js[i].number = std::get<0>(jobs[i]);
+            js[i].inner = std::get<1>(jobs[i]);
+            js[i].kind = std::get<2>(jobs[i]);
+            js[i].src = (const void*)std::get<3>(jobs[i]);
+            js[i].count = std::get<4>(jobs[i]);
+            js[i].row_ends = (const uint32_t*)std::get<5>(jobs[i]);
+            js[i].rows = std::get<6>(jobs[i]);
+            js[i].dst = (void*)std::get<7>(jobs[i]);
+            js[i].cap = std::get<8>(jobs[i]);
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceBuildRows(js.data(), (int)js.size(), device);
+        }
+        check(rc, "device_build_rows");
+        py::list out;
+        for (const gpu::DeviceRowsJob& j : js) out.append(py::make_tuple(j.len, j.err, j.first_bad));
+        return out;
+    }, py::arg("jobs"), py::arg("device") = 0);
+    g.def("device_rows_worst_case", [](uint32_t number, uint32_t inner, uint32_t kind, uint64_t count, uint64_t rows) {
+        gpu::DeviceRowsJob j;
+        j.number = number;
+        j.inner = inner;
+        j.kind = kind;
+        j.count = count;
+        j.rows = rows;
+        return gpu::DeviceRowsWorstCaseBytes(j);
+    }, py::arg("number"), py::arg("inner"), py::arg("kind"), py::arg("count"), py::arg("rows"));
     // Bare packed runs (no tag, no length), the mirror of device_decode_packed:
     // [(bytes, err)] per array.
     g.def("device_encode_packed", [](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& counts,

@@ -27,6 +27,7 @@
 #include "json/json2pb.h"
 #include "pb/descriptor.h"
 #include "pb/parser.h"
+#include "pb/rows.h"
 #include "gpu/xgmi.h"
 #include "policy/device_payload.h"
 #include "gpu/rccl_plane.h"
@@ -131,6 +132,52 @@ public:
             throw std::runtime_error("[E" + std::to_string(cntl.ErrorCode()) + "] " + cntl.ErrorText());
         }
         return py::make_tuple(res.message(), py::bytes(cntl.response_attachment().to_string()), cntl.latency_us());
+    }
+    // A Batch composed on the device and sent as a device attachment: the
+    // block gpu::BuildDeviceMessage makes of `fields` [(number, kind, ptr,
+    // count)], then the block gpu::BuildDeviceRows makes of `rows` (number,
+    // inner, kind, src, count, row_ends, nrows), appended to one Buf (protobuf
+    // concatenation is merge). Returns the echoed attachment's bytes.
+    py::bytes echo_device_rows(const std::vector<std::tuple<uint32_t, uint32_t, uintptr_t, uint64_t>>& fields,
+                               const std::tuple<uint32_t, uint32_t, uint32_t, uintptr_t, uint64_t, uintptr_t, uint64_t>& rows,
+                               int device) {
+        example::EchoRequest req;
+        example::EchoResponse res;
+        Controller cntl;
+        req.set_message("rows");
+        std::vector<gpu::DeviceMessageField> fs(fields.size());
+        for (size_t i = 0; i < fields.size(); ++i) {
+            fs[i].number = std::get<0>(fields[i]);
+            fs[i].kind = std::get<1>(fields[i]);
+            fs[i].src = (const void*)std::get<2>(fields[i]);
+            fs[i].count = std::get<3>(fields[i]);
+        }
+        gpu::DeviceRowsJob job;
+        job.number = std::get<0>(rows);
+        job.inner = std::get<1>(rows);
+        job.kind = std::get<2>(rows);
+        job.src = (const void*)std::get<3>(rows);
+        job.count = std::get<4>(rows);
+        job.row_ends = (const uint32_t*)std::get<5>(rows);
+        job.rows = std::get<6>(rows);
+        std::string got;
+        int rc = 0, copy_rc = 0;
+        {
+            py::gil_scoped_release nogil;
+            if (!fs.empty()) rc = gpu::BuildDeviceMessage(fs.data(), (int)fs.size(), &cntl.request_attachment(), device);
+            if (rc == 0) rc = gpu::BuildDeviceRows(job, &cntl.request_attachment(), device);
+            if (rc == 0) {
+                example::EchoService_Stub stub(&_ch);
+                stub.Echo(&cntl, &req, &res, nullptr);
+                if (!cntl.Failed()) copy_rc = gpu::CopyBufToHost(cntl.response_attachment(), &got);
+            }
+        }
+        if (rc != 0) throw std::runtime_error("building the attachment on the device failed (code " + std::to_string(rc) + ")");
+        if (cntl.Failed()) {
+            throw std::runtime_error("[E" + std::to_string(cntl.ErrorCode()) + "] " + cntl.ErrorText());
+        }
+        if (copy_rc != 0) throw std::runtime_error("copying the echoed attachment to the host failed");
+        return py::bytes(got);
     }
 
 private:
@@ -540,6 +587,35 @@ PYBIND11_MODULE(_native, m) {
         return py::make_tuple(r.err, r.depth, r.count, r.rows, r.first_bad, py::bytes(r.out), py::bytes(r.classes),
                               r.row_ends);
     }, py::arg("text"), py::arg("mode"), py::arg("exact") = true, py::arg("nested") = true);
+    // The host twin of gpu::DeviceBuildRows (pb::SerializeRows): `values`
+    // holds the elements of all rows in the kind's vector layout, row_ends[r]
+    // the elements in rows 0..r (a list, or the memory image of a uint32
+    // array as bytes) -> (err, first_bad, wire bytes).
+    m.def("pb_serialize_rows", [](uint32_t number, uint32_t inner, uint32_t kind, py::bytes values,
+                                  py::object row_ends_obj) {
+        std::vector<uint32_t> row_ends;
+        if (py::isinstance<py::bytes>(row_ends_obj)) {
+            const std::string image = row_ends_obj.cast<std::string>();
+            if (image.size() % 4) throw std::invalid_argument("row_ends must hold whole uint32 entries");
+            row_ends.resize(image.size() / 4);
+            if (!image.empty()) memcpy(row_ends.data(), image.data(), image.size());
+        } else {
+            row_ends = row_ends_obj.cast<std::vector<uint32_t>>();
+        }
+        const std::string data = values;
+        if (kind > pb_rows::kKindFixed64) throw std::invalid_argument("kind must be 0..9");
+        const size_t eb = pb_rows::SourceBytes(kind);
+        if (data.size() % eb) throw std::invalid_argument("values must hold whole elements");
+        std::vector<uint64_t> aligned((data.size() + 7) / 8);
+        if (!data.empty()) memcpy(aligned.data(), data.data(), data.size());
+        std::string out;
+        uint32_t first_bad = 0xFFFFFFFFu;
+        static const uint32_t kNoRows = 0;
+        const int err = pb::SerializeRows(number, inner, kind, data.empty() ? nullptr : aligned.data(),
+                                          data.size() / eb, row_ends.empty() ? &kNoRows : row_ends.data(),
+                                          row_ends.size(), &out, &first_bad);
+        return py::make_tuple(err, first_bad, py::bytes(out));
+    }, py::arg("number"), py::arg("inner"), py::arg("kind"), py::arg("values"), py::arg("row_ends"));
     // The host base64 coder (base/util.h over base/base64.h), reading the
     // bytes object in place: the text pb2json gives a bytes field, and what
     // json2pb makes of one (None where base64_decode refuses the text).
@@ -641,7 +717,9 @@ PYBIND11_MODULE(_native, m) {
              py::arg("server"), py::arg("lb") = "", py::arg("protocol") = "baidu_std",
              py::arg("connection_type") = "", py::arg("timeout_ms") = 1000, py::arg("max_retry") = 3)
         .def("echo", &PyChannel::echo, py::arg("message"), py::arg("attachment") = py::bytes(),
-             py::arg("sleep_us") = 0);
+             py::arg("sleep_us") = 0)
+        .def("echo_device_rows", &PyChannel::echo_device_rows, py::arg("fields"), py::arg("rows"),
+             py::arg("device") = 0);
 
     py::class_<PyStreamPress>(m, "StreamPress")
         .def(py::init<const py::dict&>())
@@ -841,6 +919,9 @@ PYBIND11_MODULE(_native, m) {
         d["packed_elems"] = s.packed_elems;
         d["packed_errors"] = s.packed_errors;
         d["built_messages"] = s.built_messages;
+        d["built_row_jobs"] = s.built_row_jobs;
+        d["built_rows"] = s.built_rows;
+        d["built_row_bytes"] = s.built_row_bytes;
         d["built_fields"] = s.built_fields;
         d["built_bytes"] = s.built_bytes;
         d["build_errors"] = s.build_errors;

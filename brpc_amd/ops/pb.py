@@ -102,6 +102,82 @@ def pb_build_message(fields):
     return out[:n], [tuple(p) for p in pos]
 
 
+# the kinds of pb_build_rows: those above plus the fixed widths (8: 4-byte
+# elements, 9: 8-byte elements)
+_ROW_KINDS = dict(_KINDS)
+_ROW_KINDS.update({
+    "float32": (8, (torch.float32,)),
+    "fixed32": (8, (torch.int32, getattr(torch, "uint32", torch.int32))),
+    "float64": (9, (torch.float64,)),
+    "fixed64": (9, (torch.int64, getattr(torch, "uint64", torch.int64))),
+})
+ROWS_ERRORS = dict(BUILD_ERRORS)
+ROWS_ERRORS[1] = "row_ends decreases or does not end at the number of values"
+ROWS_ERRORS[2] = "refused (field number, inner, kind, alignment, rows or size)"
+
+
+def pb_build_rows(number, values, row_ends, kind_name, inner=None):
+    """Serialize a ragged batch in device memory as the occurrences of one
+    repeated field (``gpu::DeviceBuildRows``): row r holds the elements
+    ``values[row_ends[r-1]:row_ends[r]]`` (equal neighbours: an empty row).
+
+    With ``inner`` each row is a sub-message whose packed field ``inner``
+    holds the row (``repeated Row rows = number`` with ``message Row
+    {repeated T v = inner [packed = true];}``); without it (kind bytes only)
+    each row is one ``repeated bytes`` / ``repeated string`` element.
+    kind_name: a kind of ``pb_build_message``, or float32, float64, fixed32,
+    fixed64. row_ends: an int32 or uint32 device tensor, or the int64 one
+    ``json_parse_float_rows(..., ragged=True)`` returns next to values. A
+    2-D values tensor with ``row_ends=None`` means equal rows.
+
+    Returns a uint8 device tensor trimmed to the serialized length: a valid
+    message by itself, and (protobuf concatenation being merge) a part of a
+    larger one when concatenated with a ``pb_build_message`` result.
+
+    The builder runs on its own stream: the caller's current stream is
+    synchronized before the call, as in ``pb_build_message``."""
+    if kind_name not in _ROW_KINDS:
+        raise ValueError("unknown kind %r (one of %s)" % (kind_name, ", ".join(_ROW_KINDS)))
+    kind, dtypes = _ROW_KINDS[kind_name]
+    require_gpu_tensor(values, "values")
+    dev = values.device
+    if dtypes is not None and values.dtype not in dtypes:
+        raise TypeError("kind %s takes a tensor of %s, not %s" % (kind_name, dtypes[0], values.dtype))
+    if row_ends is None:
+        if values.dim() != 2:
+            raise ValueError("row_ends=None needs a 2-D values tensor (equal rows)")
+        per = values.shape[1] * (values.element_size() if kind == 7 else 1)
+        row_ends = torch.arange(per, per * values.shape[0] + 1, max(per, 1), dtype=torch.int32, device=dev) \
+            if per else torch.zeros(values.shape[0], dtype=torch.int32, device=dev)
+    require_gpu_tensor(row_ends, "row_ends")
+    if row_ends.device != dev:
+        raise ValueError("row_ends must live on the same device as values (%s vs %s)" % (row_ends.device, dev))
+    if row_ends.dtype == torch.int64:
+        # what json_parse_float_rows(ragged=True) returns: narrowed on the device
+        row_ends = row_ends.to(torch.int32)
+    if row_ends.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or row_ends.dim() != 1:
+        raise TypeError("row_ends must be a 1-D int32, uint32 or int64 tensor, not %s" % row_ends.dtype)
+    values = values.contiguous()
+    row_ends = row_ends.contiguous()
+    count = values.numel() * values.element_size() if kind == 7 else values.numel()
+    rows = row_ends.numel()
+    inner = int(inner or 0)
+    cap = native.gpu.device_rows_worst_case(int(number), inner, kind, count, rows)
+    if cap == 0:
+        raise ValueError("pb_build_rows: " + ROWS_ERRORS[2])
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (n, err, first_bad), = native.gpu.device_build_rows(
+            [(int(number), inner, kind, values.data_ptr() if count else 0, count, row_ends.data_ptr(), rows,
+              out.data_ptr(), cap)], dev.index or 0)
+    if err == 1:
+        raise ValueError("pb_build_rows: %s (row %d)" % (ROWS_ERRORS[1], first_bad))
+    if err:
+        raise ValueError("pb_build_rows: " + ROWS_ERRORS.get(err, "code %d" % err))
+    return out[:n]
+
+
 def pb_scan_host(msg, max_fields=16):
     """Pure-python reference of one message's scan (tests)."""
     out, p = [], 0
