@@ -132,5 +132,157 @@ MRPC_ROWS_FN uint64_t WorstCaseBytes(uint32_t number, uint32_t inner, uint32_t k
     return total > 0xFFFFFFFFull ? 0 : total;
 }
 
+// ---- the way back: a message that holds such rows, split into the flat array
+// and the row ends again (pb::SplitRows in pb/rows.h, gpu::DeviceSplitRows).
+
+// Elements that are varints on the wire. Unlike IsVarintKind this includes
+// bool: a peer may send a true as any nonzero varint.
+MRPC_ROWS_FN bool WireIsVarint(uint32_t kind) { return kind <= kKindBool; }
+
+// A varint of at most ten bytes, the tenth at most 1, at w[0, avail);
+// over-long encodings are accepted (gpu/device_pb.h read_varint). Reads
+// w[0, min(avail, 10)) at most.
+MRPC_ROWS_FN bool GetVarint(const uint8_t* w, uint64_t avail, uint32_t* used, uint64_t* v) {
+    uint64_t x = 0;
+    for (uint32_t i = 0; i < 10; ++i) {
+        if (i >= avail) return false;
+        const uint64_t c = w[i];
+        x |= (c & 0x7f) << (7 * i);
+        if (!(c & 0x80)) {
+            *used = i + 1;
+            *v = x;
+            return i < 9 || c <= 1;
+        }
+    }
+    return false;
+}
+
+constexpr uint32_t kSpecReadBytes = 20;  // a tag and a value or length, ten bytes each
+struct Field {
+    uint64_t next = 0;            // the offset just past the field
+    uint64_t vpos = 0, vlen = 0;  // wire type 2: the value
+    uint32_t tag = 0;
+    bool valid = false;
+};
+
+// The speculative parse of a top-level field at ANY byte offset p of a message
+// of n bytes, w pointing at byte p: what devpb::scan_message decides when it
+// arrives at p (a tag is a varint of at most 2^32-1, field number 0 and wire
+// types 3, 4, 6, 7 are invalid, so is a field that ends beyond n or a length
+// above 2^32-1). The device calls it at every offset, garbage ones included,
+// and follows the chains of `next`, so two things hold for any bytes:
+//   1. it reads w[0, min(n - p, kSpecReadBytes)) at most, never a byte at or
+//      beyond n (a canonical tag has five bytes, but scan_message takes an
+//      over-long one of ten, hence 20 and not 15);
+//   2. a valid field has p < next <= n: every chain of `next` increases
+//      strictly and ends.
+MRPC_ROWS_FN Field SpecFieldAt(const uint8_t* w, uint64_t p, uint64_t n) {
+    Field f;
+    if (p >= n) return f;
+    const uint64_t avail = n - p;
+    uint32_t tn = 0, vn = 0;
+    uint64_t tag = 0, v = 0;
+    if (!GetVarint(w, avail, &tn, &tag) || tag > 0xFFFFFFFFull || (tag >> 3) == 0) return f;
+    const uint32_t wire = (uint32_t)(tag & 7);
+    uint64_t size;  // bytes after the tag
+    if (wire == 0) {
+        if (!GetVarint(w + tn, avail - tn, &vn, &v)) return f;
+        size = vn;
+    } else if (wire == 1 || wire == 5) {
+        size = wire == 1 ? 8 : 4;
+    } else if (wire == 2) {
+        if (!GetVarint(w + tn, avail - tn, &vn, &v) || v > 0xFFFFFFFFull) return f;
+        size = vn + v;
+        f.vpos = p + tn + vn;
+        f.vlen = v;
+    } else {
+        return f;
+    }
+    if (size > avail - tn) return f;
+    f.tag = (uint32_t)tag;
+    f.next = p + tn + size;
+    f.valid = true;
+    return f;
+}
+MRPC_ROWS_FN Field SpecField(const uint8_t* b, uint64_t p, uint64_t n) { return SpecFieldAt(b + p, p, n); }
+
+// Codes of a split: 0 done, 1 malformed wire, 2 refused arguments, 5 more
+// elements or rows than the outputs hold, 6 well-formed wire of a shape that
+// is not split (the host parser takes it).
+constexpr int kSplitMalformed = 1, kSplitRefused = 2, kSplitShort = 5, kSplitUnsupported = 6;
+
+// The verdict on one occurrence of the rows field (wire type 2) whose value
+// is b[v, v + s): 0 and the payload's place, 1 or 6. With inner == 0 the
+// payload is the value. With inner != 0 the value is empty (a row of no
+// element, for every kind) or exactly one field `inner` of wire type 2 that
+// fills it; any other sub-message is walked to its end and is 6 when all of
+// it is wire (a second field, the inner field unpacked or twice), 1 when not.
+// Then the payload: the fixed kinds need whole elements, the varint kinds a
+// last byte without a continuation bit. Whether every varint is one the
+// packed-run decoder takes (at most ten bytes, the tenth at most 1) is
+// VarintsOk below on the host, and the place pass's twin on the device.
+// The walk reads only b[v, v + s) and takes at most s / 2 steps.
+MRPC_ROWS_FN int RowShape(const uint8_t* b, uint64_t v, uint64_t s, uint32_t inner, uint32_t kind, uint64_t* poff,
+                          uint64_t* plen) {
+    uint64_t po = v, pl = s;
+    if (inner != 0 && s > 0) {
+        const uint64_t end = v + s;
+        const Field f = SpecField(b, v, end);
+        if (!f.valid) return kSplitMalformed;
+        if (f.tag != ((inner << 3) | 2) || f.next != end) {
+            uint64_t p = f.next;
+            while (p < end) {
+                const Field g = SpecField(b, p, end);
+                if (!g.valid) return kSplitMalformed;
+                p = g.next;
+            }
+            return kSplitUnsupported;
+        }
+        po = f.vpos;
+        pl = f.vlen;
+    }
+    if (WireIsVarint(kind)) {
+        if (pl > 0 && (b[po + pl - 1] & 0x80)) return kSplitMalformed;
+    } else if (pl % SourceBytes(kind)) {
+        return kSplitMalformed;
+    }
+    *poff = po;
+    *plen = pl;
+    return 0;
+}
+
+// A payload of varints that ends without a continuation bit: false when the
+// packed-run decoder refuses one of them, else their number.
+MRPC_ROWS_FN bool VarintsOk(const uint8_t* p, uint64_t len, uint64_t* count) {
+    uint64_t n = 0, start = 0;
+    for (uint64_t i = 0; i < len; ++i) {
+        if (p[i] & 0x80) continue;
+        const uint64_t bytes = i - start + 1;
+        if (bytes > 10 || (bytes == 10 && p[i] > 1)) return false;
+        ++n;
+        start = i + 1;
+    }
+    *count = n;
+    return true;
+}
+
+// The element a varint of `raw` is in the kind's vector layout, as the
+// packed-run decoder stores it: truncated to 32 bits, zigzag undone, a bool
+// 0 or 1.
+MRPC_ROWS_FN void StoreVarintElem(void* dst, uint64_t i, uint32_t kind, uint64_t raw) {
+    switch (kind) {
+    case 0:
+    case 1: static_cast<uint32_t*>(dst)[i] = (uint32_t)raw; break;
+    case 2: {
+        const uint32_t u = (uint32_t)raw;
+        static_cast<uint32_t*>(dst)[i] = (u >> 1) ^ (0u - (u & 1));
+        break;
+    }
+    case 5: static_cast<uint64_t*>(dst)[i] = (raw >> 1) ^ (0ull - (raw & 1)); break;
+    case kKindBool: static_cast<uint8_t*>(dst)[i] = raw ? 1 : 0; break;
+    default: static_cast<uint64_t*>(dst)[i] = raw; break;
+    }
+}
+
 }  // namespace pb_rows
 }  // namespace mrpc

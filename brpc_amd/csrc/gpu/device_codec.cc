@@ -20,6 +20,11 @@ DEFINE_int32(device_payload_block_kb, 2,
              "Smaller blocks spread a payload over more waves: on MI355X the 64 KiB text leg runs 121k QPS at 2 KiB "
              "(ratio 1.96) against 80k at 4 KiB (ratio 2.24)");
 
+DEFINE_int32(device_split_skip, 8,
+             "chunks of 4 KiB a serial hop of DeviceSplitRows' chase spans at least (1..64; 1: no skip table, one hop "
+             "per chunk). A hop costs 260 ns on MI355X whatever it spans; the skip table costs a pass of gathers and "
+             "4 bytes of scratch per byte of message");
+
 namespace mrpc {
 namespace gpu {
 
@@ -29,6 +34,7 @@ std::atomic<int64_t> g_encodes{0}, g_enc_bytes{0}, g_enc_out{0}, g_decodes{0}, g
     g_dec_err{0}, g_scans{0}, g_runs{0}, g_run_bytes{0}, g_run_elems{0}, g_run_err{0};
 std::atomic<int64_t> g_built{0}, g_built_fields{0}, g_built_bytes{0}, g_build_err{0};
 std::atomic<int64_t> g_built_row_jobs{0}, g_built_rows{0}, g_built_row_bytes{0};
+std::atomic<int64_t> g_split_row_jobs{0}, g_split_rows{0};
 
 uint32_t varint_len(uint64_t v) {
     uint32_t n = 1;
@@ -576,8 +582,132 @@ int BuildDeviceRows(const DeviceRowsJob& job, Buf* out, int device) {
     return 0;
 }
 
+namespace {
+
+static_assert(kDeviceSplitMaxBytes < (1ull << 28), "the splitter's offender word and row table hold 28-bit offsets");
+
+bool split_job_ok(const DeviceRowsSplitJob& j) {
+    if (!pb_rows::FieldsOk(j.number, j.inner, j.kind) || j.n > kDeviceSplitMaxBytes) return false;
+    if ((j.n > 0 && !j.msg) || (j.cap > 0 && !j.values) || (j.row_cap > 0 && !j.row_ends)) return false;
+    return ((uintptr_t)j.values & (pb_rows::SourceBytes(j.kind) - 1)) == 0 && ((uintptr_t)j.row_ends & 3) == 0;
+}
+
+}  // namespace
+
+// On a pool stream of its own, as DeviceBuildRows and for its reason: the
+// scratch is sized by the message.
+int DeviceSplitRows(DeviceRowsSplitJob* jobs, int n, int device) {
+    if (n <= 0) return 0;
+    if (!jobs || device < 0) return -1;
+    std::vector<int> live;
+    uint64_t nchunks = 0, nrblocks = 0, nochunks = 0, nrows = 0;
+    for (int i = 0; i < n; ++i) {
+        DeviceRowsSplitJob& j = jobs[i];
+        j.count = j.rows = j.others = 0;
+        j.first_bad = ~0ull;
+        j.err = 0;
+        if (!split_job_ok(j)) {
+            j.err = pb_rows::kSplitRefused;
+            continue;
+        }
+        if (j.n == 0) {  // no field: no row, nothing to launch
+            g_split_row_jobs.fetch_add(1, std::memory_order_relaxed);
+            continue;
+        }
+        live.push_back(i);
+    }
+    if (live.empty()) return 0;
+    const size_t nlive = live.size();
+    PinnedBlock tables(nlive * (sizeof(PbSplitJob) + sizeof(PbSplitResult)));
+    if (!tables) return -1;
+    PbSplitJob* tj = tables.as<PbSplitJob>();
+    PbSplitResult* tr = reinterpret_cast<PbSplitResult*>(tj + nlive);
+    PbSplitTables t;
+    for (size_t k = 0; k < nlive; ++k) {
+        const DeviceRowsSplitJob& j = jobs[live[k]];
+        PbSplitJob& o = tj[k];
+        o.msg = static_cast<const uint8_t*>(j.msg);
+        o.values = j.values;
+        o.row_ends = j.row_ends;
+        o.cap = j.cap;
+        o.row_cap = j.row_cap;
+        o.n = (uint32_t)j.n;
+        o.number = j.number;
+        o.inner = j.inner;
+        o.kind = j.kind;
+        const bool varints = pb_rows::WireIsVarint(j.kind);
+        const uint64_t most_rows = j.n / 2;  // a row has a tag and a length
+        o.first_chunk = (uint32_t)nchunks;
+        o.nchunks = (uint32_t)((j.n + kPbSplitChunk - 1) / kPbSplitChunk);
+        o.first_rblock = (uint32_t)nrblocks;
+        o.nrblocks = (uint32_t)std::max<uint64_t>(1, (most_rows + kPbSplitBlockRows - 1) / kPbSplitBlockRows);
+        o.first_ochunk = (uint32_t)nochunks;
+        o.nochunks = varints ? 0
+                             : (uint32_t)((std::min(j.cap, j.n / pb_rows::SourceBytes(j.kind)) + kPbSplitOutChunk - 1) /
+                                          kPbSplitOutChunk);
+        o.first_row = (uint32_t)nrows;
+        nchunks += o.nchunks;
+        nrblocks += o.nrblocks;
+        nochunks += o.nochunks;
+        if (varints) {
+            nrows += std::min(j.row_cap, most_rows);
+            t.any_varint = true;
+        }
+        tr[k] = PbSplitResult{0, 0, 0, kPbSplitNone, 0};
+    }
+    // exit[] (later the row table) by itself; then the 8-byte tables, then the words
+    const size_t exit_bytes = (size_t)nchunks * kPbSplitChunk * sizeof(uint32_t);
+    const size_t jobs_bytes = (nlive * sizeof(PbSplitJob) + 7) & ~(size_t)7;
+    const size_t masks = 2 * (size_t)nchunks * 64;
+    const size_t words = (size_t)nchunks * 64 + 3 * ((size_t)nchunks + 1) + (size_t)nrblocks + 1 + (size_t)nrows +
+                         3 * nlive;
+    t.skip_hops = (uint32_t)std::max(1, std::min(64, FLAGS_device_split_skip));
+    const bool skips = t.skip_hops > 1 && nchunks > t.skip_hops;  // a short message is chased directly
+    if (!skips) t.skip_hops = 1;
+    HbmBlock exit_block(exit_bytes, device), skip_block(skips ? exit_bytes : 0, device);
+    HbmBlock scratch(jobs_bytes + masks * sizeof(uint64_t) + (words + (skips ? nchunks : 0)) * sizeof(uint32_t), device);
+    if (!exit_block || !scratch || (skips && !skip_block)) return -1;
+    t.skip = skip_block.as<uint32_t>();
+    t.jobs = tj;
+    t.njobs = (int)nlive;
+    t.nchunks = (uint32_t)nchunks;
+    t.nrblocks = (uint32_t)nrblocks;
+    t.nochunks = (uint32_t)nochunks;
+    t.nrows = (uint32_t)nrows;
+    t.exit = exit_block.as<uint32_t>();
+    t.jobs_dev = scratch.as<PbSplitJob>();
+    t.term_mask = reinterpret_cast<uint64_t*>(static_cast<char*>(scratch.p) + jobs_bytes);
+    t.row_mask = t.term_mask + nchunks * 64;
+    t.term_group = reinterpret_cast<uint32_t*>(t.row_mask + nchunks * 64);
+    t.term_chunk = t.term_group + nchunks * 64;
+    t.row_chunk = t.term_chunk + nchunks + 1;
+    t.entry = t.row_chunk + nchunks + 1;
+    t.block_sum = t.entry + nchunks + 1;
+    t.row_bias = t.block_sum + nrblocks + 1;
+    t.bad = t.row_bias + nrows;
+    t.others = t.bad + nlive;
+    t.ok = reinterpret_cast<int32_t*>(t.others + nlive);
+    t.land = skips ? reinterpret_cast<uint32_t*>(t.ok + nlive) : nullptr;
+    t.res = tr;
+    if (RunOnPoolStream(device, [&](hipStream_t s) { return LaunchPbRowsSplit(t, s); }) != 0) return -1;
+    for (size_t k = 0; k < nlive; ++k) {
+        DeviceRowsSplitJob& j = jobs[live[k]];
+        j.err = tr[k].err;
+        j.count = tr[k].count;
+        j.rows = tr[k].rows;
+        j.others = tr[k].others;
+        if (j.err == pb_rows::kSplitMalformed || j.err == pb_rows::kSplitUnsupported) j.first_bad = tr[k].first_bad;
+        if (j.err) continue;
+        g_split_row_jobs.fetch_add(1, std::memory_order_relaxed);
+        g_split_rows.fetch_add((int64_t)j.rows, std::memory_order_relaxed);
+    }
+    return 0;
+}
+
 DeviceCodecStats GetDeviceCodecStats() {
     DeviceCodecStats s;
+    s.split_row_jobs = g_split_row_jobs.load();
+    s.split_rows = g_split_rows.load();
     s.built_row_jobs = g_built_row_jobs.load();
     s.built_rows = g_built_rows.load();
     s.built_row_bytes = g_built_row_bytes.load();

@@ -189,6 +189,45 @@ int DeviceBuildRows(DeviceRowsJob* jobs, int n, int device);
 // block, as BuildDeviceMessage does. 0, a DeviceRowsJob::err code, or -1.
 int BuildDeviceRows(const DeviceRowsJob& job, Buf* out, int device);
 
+// ---- and back: a message in device memory that holds such rows (what
+// DeviceBuildRows wrote, or any sender's `repeated Row rows = N`, other
+// top-level fields around and between the rows included) -> the flat array
+// and the row ends, without a copy of the message to the host. DevicePbScan
+// walks a message with one lane and stops at its field table's size; here
+// the top-level field starts are found in parallel (gpu/kernels.h
+// LaunchPbRowsSplit), with one serial hop per 4 KiB. pb::SplitRows
+// (pb/rows.h) is the host twin: same codes, same outputs.
+// The scratch is 10.5 bytes per byte of message in three blocks (6.5 in two
+// with -device_split_skip 1), the largest of 4 bytes per byte: the arena's
+// largest block (256 MiB) bounds a message.
+constexpr uint64_t kDeviceSplitMaxBytes = 64ull << 20;
+struct DeviceRowsSplitJob {
+    uint32_t number = 0;  // the repeated field, 1 .. 2^29-1
+    uint32_t inner = 0;   // the packed field inside each row; 0: the row is the payload (kind bytes only)
+    uint32_t kind = 0;    // as DeviceRowsJob
+    const void* msg = nullptr;  // device, any byte alignment
+    uint64_t n = 0;
+    void* values = nullptr;  // device, cap elements, naturally aligned for the kind
+    uint64_t cap = 0;
+    uint32_t* row_ends = nullptr;  // device, 4-byte aligned, row_cap entries
+    uint64_t row_cap = 0;
+    // out
+    uint64_t count = 0, rows = 0;  // elements and rows (with err 5: what the outputs need)
+    uint64_t others = 0;           // top-level fields other than `number`, skipped
+    uint64_t first_bad = ~0ull;    // with err 1 and 6: the offset of the top-level field that offends
+    // 0 split; 1 malformed wire; 2 refused before any launch (bad number /
+    // inner / kind, a null pointer with a nonzero size, misaligned values or
+    // row_ends, n above kDeviceSplitMaxBytes); 5 more than cap elements or
+    // row_cap rows; 6 well-formed wire of a shape that is not split (see
+    // pb_rows::RowShape): the host parser takes it. With 1, 5 and 6 values
+    // and row_ends are untouched; no store ever goes beyond cap or row_cap.
+    int err = 0;
+};
+// All jobs share one sequence of launches on a pool stream and one wait; the
+// host reads nothing but the result words. Returns -1 only on a device error
+// (a failed scratch allocation is one); per-job codes in jobs[i].err.
+int DeviceSplitRows(DeviceRowsSplitJob* jobs, int n, int device);
+
 struct DeviceCodecStats {
     int64_t encodes = 0, encoded_bytes = 0, encoded_out_bytes = 0;
     int64_t decodes = 0, decoded_bytes = 0, bad_tables = 0, decode_errors = 0;
@@ -196,6 +235,7 @@ struct DeviceCodecStats {
     int64_t packed_runs = 0, packed_bytes = 0, packed_elems = 0, packed_errors = 0;
     int64_t built_messages = 0, built_fields = 0, built_bytes = 0, build_errors = 0;
     int64_t built_row_jobs = 0, built_rows = 0, built_row_bytes = 0;  // failed row jobs count in build_errors
+    int64_t split_row_jobs = 0, split_rows = 0;                       // DeviceSplitRows jobs that ended with code 0
 };
 DeviceCodecStats GetDeviceCodecStats();
 

@@ -404,6 +404,117 @@ struct PbRowsTables {
 };
 int LaunchPbRowsBuild(const PbRowsTables& t, hipStream_t s);
 
+// Row splitter, the inverse: a message in device memory whose field `number`
+// repeats once per row becomes the flat array and the row ends again
+// (base/pb_rows.h has the rules, pb::SplitRows is the host twin). Finding the
+// top-level fields of a message is a walk of length-prefixed fields; here
+// only one hop per chunk of kPbSplitChunk bytes of it stays serial. All jobs
+// share one sequence of launches on one stream, ordered by the launches alone:
+// no workgroup waits for another, and every loop is bounded by n or by the
+// two invariants of pb_rows::SpecField (it never reads beyond n, and `next`
+// grows strictly).
+//   spec    a workgroup per chunk parses a field at EVERY byte offset of the
+//           chunk (staged in LDS with the bytes a parse may read behind it)
+//           and resolves, by pointer doubling in LDS, exit[p]: the first
+//           offset at or beyond the chunk's end on p's chain of `next`, or
+//           invalid. Also the chunk's terminator mask (bytes without a
+//           continuation bit, a bit per byte), the terminators before each of
+//           its 64-byte groups and their total, and entry[chunk] = none
+//   prefix  LaunchPbRunPrefix over the chunks' terminator totals
+//   skip    skip[p] = exit applied skip_hops times to p, for every offset:
+//           a pass of gathers that mostly meet (chains merge within a few
+//           fields), which makes every serial hop below skip_hops chunks long
+//   chase   a lane per job hops pos = skip[pos] from 0 and writes land[c],
+//           the first true field start of every chunk it lands in: one
+//           dependent load per skip_hops chunks, the serial remainder (260 ns
+//           a hop on MI355X: the table was written by other XCDs a moment ago)
+//   fill    a lane per landing writes entry[] of the chunks up to the next
+//           landing, skip_hops - 1 hops of exit[] further. With skip_hops 1
+//           there is neither skip nor fill: the chase follows exit[] and
+//           writes entry[] itself
+//   mark    a workgroup per chunk parses every offset again and finds the
+//           true starts from entry[c] in two levels: exits of the 64-byte
+//           sub-chunks by doubling, one lane across the 64 sub-chunks, then a
+//           lane per sub-chunk walks its own. A true start that is no field
+//           reports its offset (code 1), field `number` with another wire
+//           type too (code 6); rows are marked in the row mask and counted
+//           per chunk, other fields counted per job
+//   prefix  over the chunks' row counts: every row has its rank
+//   table   the lane that owns a row's tag applies pb_rows::RowShape (from
+//           device memory: a row's sub-header may lie in the next chunk) and
+//           writes {tag offset, header bytes, payload bytes} into the row
+//           table, which takes the place of exit[] (two bytes of message at
+//           least per row, eight bytes per entry)
+//   check   varint kinds: a workgroup per chunk looks for varints of more
+//           than ten bytes (or ten with a last byte above 1) and reports those
+//           inside a row's payload (code 1). The byte in front of a payload
+//           ends a length, so a varint's extent needs no row bounds
+//   count   a lane per row: elements of the row (payload bytes over the
+//           element size, or the difference of two terminator counts), summed
+//           per 256 rows
+//   prefix  over those sums
+//   publish a lane per job combines the lowest offender, the counts and the
+//           capacities into the result; everything below runs only for jobs
+//           whose code is 0, read from device memory
+//   ends    a lane per row: row_ends, by a scan inside each block of 256 rows,
+//           and for varint kinds the row's first element index less the
+//           terminators in front of its payload
+//   place   fixed-width kinds and bytes: a workgroup per 2048 elements of the
+//           output; every element finds its row in row_ends by binary search
+//           between the rows of the chunk's first and last element. Varint
+//           kinds: a workgroup per message chunk; every terminator inside a
+//           payload is the end of one element, whose row is found in the
+//           slice of the row table that meets the chunk
+// The offender word of a job is (offset << 3 | code), lowered with atomicMin.
+constexpr uint32_t kPbSplitChunk = 4096;
+constexpr uint32_t kPbSplitBlockRows = 256;
+constexpr uint32_t kPbSplitOutChunk = 2048;  // elements
+constexpr uint32_t kPbSplitNone = 0xFFFFFFFFu;
+struct PbSplitJob {
+    const uint8_t* msg;  // n bytes, any alignment
+    void* values;        // cap elements, naturally aligned
+    uint32_t* row_ends;  // row_cap entries
+    uint64_t cap, row_cap;
+    uint32_t n;  // 1 .. kDeviceSplitMaxBytes
+    uint32_t number, inner, kind;
+    // the job's part of the tables: chunk c of the job is entry first_chunk + c of entry, term_chunk and
+    // row_chunk, its 64 groups those from there times 64 of the masks and term_group, its bytes those from
+    // there times kPbSplitChunk of exit
+    uint32_t first_chunk, nchunks;    // ceil(n / kPbSplitChunk)
+    uint32_t first_rblock, nrblocks;  // blocks of 256 rows in block_sum: ceil((n / 2) / 256), at least 1
+    uint32_t first_ochunk, nochunks;  // fixed-width kinds and bytes: ceil(min(cap, n / width) / 2048) output chunks
+    uint32_t first_row;               // in row_bias: min(row_cap, n / 2) entries (varint kinds)
+};
+struct PbSplitResult {
+    uint64_t count, rows, others;
+    uint32_t first_bad;
+    int32_t err;  // 0, 1, 5, 6
+};
+struct PbSplitTables {
+    const PbSplitJob* jobs = nullptr;  // pinned host
+    int njobs = 0;
+    PbSplitJob* jobs_dev = nullptr;
+    uint32_t nchunks = 0, nrblocks = 0, nochunks = 0, nrows = 0;
+    bool any_varint = false;
+    uint32_t* exit = nullptr;       // nchunks * kPbSplitChunk; later the row table (uint64 per row)
+    uint32_t skip_hops = 1;         // chunks a serial hop of the chase spans at least; above 1 with skip and land
+    uint32_t* skip = nullptr;       // nchunks * kPbSplitChunk
+    uint32_t* land = nullptr;       // nchunks
+    uint64_t* term_mask = nullptr;  // nchunks * 64
+    uint64_t* row_mask = nullptr;   // nchunks * 64
+    uint32_t* term_group = nullptr; // nchunks * 64
+    uint32_t* term_chunk = nullptr; // nchunks + 1, scanned
+    uint32_t* row_chunk = nullptr;  // nchunks + 1, scanned
+    uint32_t* entry = nullptr;      // nchunks
+    uint32_t* block_sum = nullptr;  // nrblocks + 1, scanned
+    uint32_t* row_bias = nullptr;   // nrows
+    uint32_t* bad = nullptr;        // njobs
+    uint32_t* others = nullptr;     // njobs
+    int32_t* ok = nullptr;          // njobs
+    PbSplitResult* res = nullptr;   // njobs, pinned host
+};
+int LaunchPbRowsSplit(const PbSplitTables& t, hipStream_t s);
+
 // JSON float / double arrays (gpu/json_kernels.hip): arrays in device (or
 // pinned host) memory become "v,v,...,v" in device memory, every element
 // exactly as json::Value prints a double (base/shortest_double.h; a float is

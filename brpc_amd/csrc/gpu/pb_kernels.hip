@@ -1178,7 +1178,645 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
     if (changed) res[j].err = 4;
 }
 
+// ------------------------------------------------------------ row splitter
+// A message of rows -> the flat array and the row ends (kernels.h: init,
+// spec, prefix, skip, chase, fill, mark, prefix, table, check, count, prefix,
+// publish, ends, place; the wire rules are base/pb_rows.h).
+constexpr uint32_t kSplitPer = kPbSplitChunk / kRunThreads;  // offsets per lane
+constexpr uint32_t kSplitAhead = 32;                         // staged behind a chunk: >= pb_rows::kSpecReadBytes
+constexpr uint32_t kSplitBack = 16;                          // staged in front of one: a varint's nine earlier bytes
+constexpr int kSplitStage16 = (kSplitBack + kPbSplitChunk + kSplitAhead + 16 + 15) / 16;
+static_assert(kPbSplitChunk == 64 * 64 && kRunThreads == 256 && kSplitAhead >= pb_rows::kSpecReadBytes, "split layout");
+static_assert(2 * kRunThreads * 16 >= kSplitStage16 * 16, "stage_aligned covers a staged chunk");
+
+// which: 0 message chunks, 1 row blocks, 2 output chunks
+__device__ __forceinline__ int split_job_of(const PbSplitJob* jobs, int njobs, uint32_t x, int which) {
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        const uint32_t first = which == 0 ? jobs[mid].first_chunk : (which == 1 ? jobs[mid].first_rblock : jobs[mid].first_ochunk);
+        if (first <= x) {
+            lo = mid;
+        } else {
+            hi = mid - 1;
+        }
+    }
+    return lo;
+}
+
+__device__ __forceinline__ uint64_t* split_row_table(const PbSplitJob& job, uint32_t* exit) {
+    return reinterpret_cast<uint64_t*>(exit + (size_t)job.first_chunk * kPbSplitChunk);
+}
+// A row table entry: the tag's offset (28 bits), the bytes from there to the
+// payload (6 bits: two tags and two lengths of ten bytes at most), the
+// payload's bytes (28 bits).
+__device__ __forceinline__ uint64_t split_row_pack(uint32_t tag_off, uint32_t head, uint32_t len) {
+    return (uint64_t)tag_off | ((uint64_t)head << 28) | ((uint64_t)len << 34);
+}
+__device__ __forceinline__ uint32_t split_row_tag(uint64_t e) { return (uint32_t)e & 0x0FFFFFFFu; }
+__device__ __forceinline__ uint32_t split_row_pay(uint64_t e) { return split_row_tag(e) + ((uint32_t)(e >> 28) & 63u); }
+__device__ __forceinline__ uint32_t split_row_len(uint64_t e) { return (uint32_t)(e >> 34) & 0x0FFFFFFFu; }
+
+__device__ __forceinline__ uint32_t split_total(const uint32_t* scanned, uint32_t first, uint32_t n) {
+    return scanned[first + n] - scanned[first];
+}
+
+// Bytes without a continuation bit in [0, x) of the job's message, x <= n.
+__device__ __forceinline__ uint32_t split_terms_before(const PbSplitJob& job, const uint64_t* term_mask,
+                                                       const uint32_t* term_group, const uint32_t* term_chunk,
+                                                       uint32_t x) {
+    const uint32_t c = x / kPbSplitChunk;
+    if (c >= job.nchunks) return split_total(term_chunk, job.first_chunk, job.nchunks);
+    const size_t g = (size_t)(job.first_chunk + c) * 64 + ((x >> 6) & 63);
+    return term_chunk[job.first_chunk + c] - term_chunk[job.first_chunk] + term_group[g] +
+           (uint32_t)__popcll(term_mask[g] & ((1ull << (x & 63)) - 1));
+}
+
+__global__ void __launch_bounds__(64) pb_split_init_kernel(const PbSplitJob* __restrict__ jobs, int njobs,
+                                                           PbSplitJob* __restrict__ jobs_dev,
+                                                           uint32_t* __restrict__ term_chunk,
+                                                           uint32_t* __restrict__ row_chunk,
+                                                           uint32_t* __restrict__ block_sum, uint32_t nchunks,
+                                                           uint32_t nrblocks, uint32_t* __restrict__ bad,
+                                                           uint32_t* __restrict__ others, int32_t* __restrict__ ok) {
+    const int j = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (j == 0) {
+        // the entries behind the last job's, whose prefix is its total
+        term_chunk[nchunks] = 0;
+        row_chunk[nchunks] = 0;
+        block_sum[nrblocks] = 0;
+    }
+    if (j >= njobs) return;
+    jobs_dev[j] = jobs[j];
+    bad[j] = kPbSplitNone;
+    others[j] = 0;
+    ok[j] = 0;
+}
+
+// Stages chunk bytes [-back, len + ahead) that lie inside the message and
+// returns the LDS address of chunk byte 0.
+__device__ __forceinline__ const uint8_t* split_stage(const PbSplitJob& job, uint32_t cs, uint32_t len, uint32_t back,
+                                                      u32x4* lds) {
+    back = back < cs ? back : cs;
+    const uint32_t rest = job.n - cs;
+    const uint32_t fwd = rest < len + kSplitAhead ? rest : len + kSplitAhead;
+    const uint32_t a = stage_aligned(job.msg + cs - back, back + fwd, lds);
+    return reinterpret_cast<const uint8_t*>(lds) + a + back;
+}
+
+// next[] of every offset of the chunk: where the field that would start
+// there ends, or none.
+__device__ __forceinline__ void split_parse(const PbSplitJob& job, const uint8_t* bytes, uint32_t cs, uint32_t len,
+                                            uint32_t* nxt) {
+#pragma unroll 4
+    for (uint32_t r = 0; r < kSplitPer; ++r) {
+        const uint32_t i = r * kRunThreads + threadIdx.x;
+        if (i >= len) continue;
+        const pb_rows::Field f = pb_rows::SpecFieldAt(bytes + i, cs + i, job.n);
+        nxt[i] = f.valid ? (uint32_t)f.next : kPbSplitNone;
+    }
+}
+
+// Pointer doubling over the chunk's offsets: afterwards at[i] is the first
+// offset on i's chain that is at or beyond the end of i's span (the chunk
+// when span_shift is 12, its 64-byte sub-chunk when 6), or none. A chain
+// grows by two bytes a hop at least, so a span of 2^k bytes is resolved
+// after k - 1 rounds and the round that sees nothing move; reading an entry
+// another lane has already advanced only gets there sooner.
+__device__ __forceinline__ void split_resolve(uint32_t* at, uint32_t cs, uint32_t len, uint32_t span_shift) {
+    for (uint32_t round = 0; round <= span_shift; ++round) {
+        int moved = 0;
+        for (uint32_t r = 0; r < kSplitPer; ++r) {
+            const uint32_t i = r * kRunThreads + threadIdx.x;
+            if (i >= len) continue;
+            const uint32_t e = at[i];
+            if (e == kPbSplitNone) continue;
+            const uint32_t k = e - cs;  // > i
+            if (k < len && (k >> span_shift) == (i >> span_shift)) {
+                at[i] = at[k];
+                moved = 1;
+            }
+        }
+        if (!__syncthreads_or(moved)) break;
+    }
+}
+
+__global__ void __launch_bounds__(kRunThreads) pb_split_spec_kernel(const PbSplitJob* __restrict__ jobs, int njobs,
+                                                                    uint32_t* __restrict__ exit,
+                                                                    uint64_t* __restrict__ term_mask,
+                                                                    uint32_t* __restrict__ term_group,
+                                                                    uint32_t* __restrict__ term_chunk,
+                                                                    uint32_t* __restrict__ entry,
+                                                                    uint32_t* __restrict__ land) {
+    __shared__ u32x4 raw[kSplitStage16];
+    __shared__ uint32_t nxt[kPbSplitChunk];
+    __shared__ uint64_t groups[64];
+    const PbSplitJob job = jobs[split_job_of(jobs, njobs, blockIdx.x, 0)];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbSplitChunk;
+    const uint32_t len = job.n - cs < kPbSplitChunk ? job.n - cs : kPbSplitChunk;
+    const uint8_t* bytes = split_stage(job, cs, len, 0, raw);
+    if (t == 0) {
+        entry[blockIdx.x] = kPbSplitNone;
+        if (land) land[blockIdx.x] = kPbSplitNone;
+    }
+    __syncthreads();
+    split_parse(job, bytes, cs, len, nxt);
+    // a wave's 64 bytes of a round are one group of the terminator mask
+    for (uint32_t r = 0; r < kSplitPer; ++r) {
+        const uint32_t i = r * kRunThreads + t;
+        const uint64_t m = __ballot(i < len && !(bytes[i] & 0x80));
+        if (lane == 0) groups[r * (kRunThreads / 64) + wave] = m;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const uint64_t m = groups[lane];
+        const uint32_t mine = (uint32_t)__popcll(m);
+        uint32_t incl = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t y = __shfl_up(incl, off, 64);
+            if (lane >= (uint32_t)off) incl += y;
+        }
+        const size_t g = (size_t)blockIdx.x * 64 + lane;
+        term_mask[g] = m;
+        term_group[g] = incl - mine;
+        if (lane == 63) term_chunk[blockIdx.x] = incl;
+    }
+    split_resolve(nxt, cs, len, 12);
+    uint32_t* out = exit + (size_t)blockIdx.x * kPbSplitChunk;
+    for (uint32_t r = 0; r < kSplitPer; ++r) {
+        const uint32_t i = r * kRunThreads + t;
+        if (i < len) out[i] = nxt[i];
+    }
+}
+
+// skip[p] = exit applied `hops` times to p (none and n stay): what the chase
+// follows, so that its serial hops are `hops` chunks long at least. Chains
+// merge within a few fields, so the lanes of a wave mostly ask for the same
+// few entries.
+__global__ void __launch_bounds__(kRunThreads) pb_split_skip_kernel(const PbSplitJob* __restrict__ jobs, int njobs,
+                                                                    const uint32_t* __restrict__ exit,
+                                                                    uint32_t* __restrict__ skip, uint32_t hops) {
+    const PbSplitJob job = jobs[split_job_of(jobs, njobs, blockIdx.x, 0)];
+    const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbSplitChunk;
+    const uint32_t len = job.n - cs < kPbSplitChunk ? job.n - cs : kPbSplitChunk;
+    const uint32_t* ex = exit + (size_t)job.first_chunk * kPbSplitChunk;
+    uint32_t e[kSplitPer];
+#pragma unroll
+    for (uint32_t r = 0; r < kSplitPer; ++r) {
+        const uint32_t i = r * kRunThreads + threadIdx.x;
+        e[r] = i < len ? ex[cs + i] : kPbSplitNone;
+    }
+    for (uint32_t h = 1; h < hops; ++h) {
+#pragma unroll
+        for (uint32_t r = 0; r < kSplitPer; ++r) {
+            if (e[r] < job.n) e[r] = ex[e[r]];  // none is above every n
+        }
+    }
+    uint32_t* out = skip + (size_t)blockIdx.x * kPbSplitChunk;
+#pragma unroll
+    for (uint32_t r = 0; r < kSplitPer; ++r) {
+        const uint32_t i = r * kRunThreads + threadIdx.x;
+        if (i < len) out[i] = e[r];
+    }
+}
+
+// `table` is exit[] (then `first` is entry[]) or skip[] (then `first` is
+// land[], which the fill pass spreads into entry[]).
+__global__ void __launch_bounds__(64) pb_split_chase_kernel(const PbSplitJob* __restrict__ jobs, int njobs,
+                                                            const uint32_t* __restrict__ table,
+                                                            uint32_t* __restrict__ first) {
+    const int j = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (j >= njobs) return;
+    const PbSplitJob job = jobs[j];
+    const uint32_t* hop_to = table + (size_t)job.first_chunk * kPbSplitChunk;
+    uint32_t pos = 0;
+    // every hop lands in a later chunk
+    for (uint32_t hop = 0; hop < job.nchunks && pos < job.n; ++hop) {
+        first[job.first_chunk + pos / kPbSplitChunk] = pos;
+        pos = hop_to[pos];  // none is above every n
+    }
+}
+
+// A lane per chunk the chase landed in: the entries of the chunks between
+// this landing and the next, `hops` - 1 hops of exit[] further.
+__global__ void __launch_bounds__(64) pb_split_fill_kernel(const PbSplitJob* __restrict__ jobs, int njobs,
+                                                           const uint32_t* __restrict__ exit,
+                                                           const uint32_t* __restrict__ land,
+                                                           uint32_t* __restrict__ entry, uint32_t hops,
+                                                           uint32_t nchunks) {
+    const uint32_t c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= nchunks) return;
+    const PbSplitJob job = jobs[split_job_of(jobs, njobs, c, 0)];
+    const uint32_t* ex = exit + (size_t)job.first_chunk * kPbSplitChunk;
+    uint32_t pos = land[c];
+    for (uint32_t h = 0; h < hops && pos < job.n; ++h) {
+        entry[job.first_chunk + pos / kPbSplitChunk] = pos;
+        pos = ex[pos];
+    }
+}
+
+__global__ void __launch_bounds__(kRunThreads) pb_split_mark_kernel(const PbSplitJob* __restrict__ jobs, int njobs,
+                                                                    const uint32_t* __restrict__ entry,
+                                                                    uint64_t* __restrict__ row_mask,
+                                                                    uint32_t* __restrict__ row_chunk,
+                                                                    uint32_t* __restrict__ bad,
+                                                                    uint32_t* __restrict__ others) {
+    __shared__ u32x4 raw[kSplitStage16];
+    __shared__ uint32_t nxt[kPbSplitChunk];
+    __shared__ uint32_t sub[kPbSplitChunk];
+    __shared__ uint32_t sub_entry[64];
+    __shared__ uint64_t starts[64];
+    __shared__ uint16_t row_bits[kRunThreads];  // lane t: its 16 offsets; four lanes make a group's mask
+    __shared__ uint32_t tally[2];
+    const int j = split_job_of(jobs, njobs, blockIdx.x, 0);
+    const PbSplitJob job = jobs[j];
+    const uint32_t t = threadIdx.x;
+    const uint32_t ent = entry[blockIdx.x];
+    if (ent == kPbSplitNone) {  // the walk jumped over this chunk, or ended before it
+        if (t < 64) row_mask[(size_t)blockIdx.x * 64 + t] = 0;
+        if (t == 0) row_chunk[blockIdx.x] = 0;
+        return;
+    }
+    const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbSplitChunk;
+    const uint32_t len = job.n - cs < kPbSplitChunk ? job.n - cs : kPbSplitChunk;
+    const uint8_t* bytes = split_stage(job, cs, len, 0, raw);
+    if (t < 64) sub_entry[t] = kPbSplitNone;
+    if (t < 2) tally[t] = 0;
+    __syncthreads();
+    split_parse(job, bytes, cs, len, nxt);
+    for (uint32_t r = 0; r < kSplitPer; ++r) {
+        const uint32_t i = r * kRunThreads + t;
+        if (i < len) sub[i] = nxt[i];
+    }
+    __syncthreads();
+    split_resolve(sub, cs, len, 6);
+    if (t == 0) {
+        // across the sub-chunks: every hop lands in a later one
+        uint32_t pos = ent;
+        for (uint32_t hop = 0; hop < 64 && pos != kPbSplitNone && pos - cs < len; ++hop) {
+            sub_entry[(pos - cs) >> 6] = pos;
+            pos = sub[pos - cs];
+        }
+    }
+    __syncthreads();
+    if (t < 64) {
+        // inside one: at most 32 fields; an offset that is no field is still a
+        // true start (the offender), and ends the walk
+        uint64_t m = 0;
+        uint32_t pos = sub_entry[t];
+        for (uint32_t hop = 0; hop < 32 && pos != kPbSplitNone && pos - cs < len && ((pos - cs) >> 6) == t; ++hop) {
+            m |= 1ull << ((pos - cs) & 63);
+            pos = nxt[pos - cs];
+        }
+        starts[t] = m;
+    }
+    __syncthreads();
+    uint32_t mine = (uint32_t)(starts[t >> 2] >> ((t & 3) * 16)) & 0xFFFFu, rows = 0, nrows = 0, nothers = 0;
+    while (mine) {
+        const uint32_t bit = (uint32_t)__ffs((int)mine) - 1;
+        mine &= mine - 1;
+        const uint32_t i = t * 16 + bit;
+        const pb_rows::Field f = pb_rows::SpecFieldAt(bytes + i, cs + i, job.n);
+        if (!f.valid) {
+            atomicMin(&bad[j], ((cs + i) << 3) | (uint32_t)pb_rows::kSplitMalformed);
+        } else if ((f.tag >> 3) != job.number) {
+            ++nothers;
+        } else if ((f.tag & 7) != 2) {
+            atomicMin(&bad[j], ((cs + i) << 3) | (uint32_t)pb_rows::kSplitUnsupported);
+        } else {
+            rows |= 1u << bit;
+            ++nrows;
+        }
+    }
+    row_bits[t] = (uint16_t)rows;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        nrows += __shfl_xor(nrows, off, 64);
+        nothers += __shfl_xor(nothers, off, 64);
+    }
+    if ((t & 63) == 0) {
+        atomicAdd(&tally[0], nrows);
+        atomicAdd(&tally[1], nothers);
+    }
+    __syncthreads();
+    if (t < 64) {
+        const uint64_t m = (uint64_t)row_bits[4 * t] | ((uint64_t)row_bits[4 * t + 1] << 16) |
+                           ((uint64_t)row_bits[4 * t + 2] << 32) | ((uint64_t)row_bits[4 * t + 3] << 48);
+        row_mask[(size_t)blockIdx.x * 64 + t] = m;
+    }
+    if (t == 0) {
+        row_chunk[blockIdx.x] = tally[0];
+        if (tally[1]) atomicAdd(&others[j], tally[1]);
+    }
+}
+
+__global__ void __launch_bounds__(kRunThreads) pb_split_table_kernel(const PbSplitJob* __restrict__ jobs, int njobs,
+                                                                     const uint64_t* __restrict__ row_mask,
+                                                                     const uint32_t* __restrict__ row_chunk,
+                                                                     uint32_t* __restrict__ exit,
+                                                                     uint32_t* __restrict__ bad) {
+    __shared__ uint32_t before[64];
+    const int j = split_job_of(jobs, njobs, blockIdx.x, 0);
+    const PbSplitJob job = jobs[j];
+    if (row_chunk[blockIdx.x + 1] == row_chunk[blockIdx.x]) return;
+    const uint32_t t = threadIdx.x, lane = t & 63;
+    const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbSplitChunk;
+    if (t < 64) {
+        const uint32_t mine = (uint32_t)__popcll(row_mask[(size_t)blockIdx.x * 64 + t]);
+        uint32_t incl = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t y = __shfl_up(incl, off, 64);
+            if (lane >= (uint32_t)off) incl += y;
+        }
+        before[t] = incl - mine;
+    }
+    __syncthreads();
+    const uint64_t m = row_mask[(size_t)blockIdx.x * 64 + (t >> 2)];
+    const uint32_t sh = (t & 3) * 16;
+    uint32_t mine = (uint32_t)(m >> sh) & 0xFFFFu;
+    // rows of the job in front of this lane's: at most n / 2 rows, so the
+    // table stays inside the job's part of exit[]
+    uint32_t rank = row_chunk[blockIdx.x] - row_chunk[job.first_chunk] + before[t >> 2] +
+                    (uint32_t)__popcll(m & ((1ull << sh) - 1));
+    uint64_t* table = split_row_table(job, exit);
+    while (mine) {
+        const uint32_t bit = (uint32_t)__ffs((int)mine) - 1;
+        mine &= mine - 1;
+        const uint32_t p = cs + t * 16 + bit;
+        const pb_rows::Field f = pb_rows::SpecField(job.msg, p, job.n);  // a row: the mark pass parsed it
+        uint64_t po = 0, pl = 0;
+        const int code = f.valid ? pb_rows::RowShape(job.msg, f.vpos, f.vlen, job.inner, job.kind, &po, &pl)
+                                 : pb_rows::kSplitMalformed;
+        if (code != 0) {
+            atomicMin(&bad[j], (p << 3) | (uint32_t)code);
+            po = p;
+            pl = 0;
+        }
+        if ((uint64_t)rank < job.n / 2 + 1) table[rank] = split_row_pack(p, (uint32_t)(po - p), (uint32_t)pl);
+        ++rank;
+    }
+}
+
+// The row whose payload holds byte q, among rows [lo, hi) of the table, or
+// none: the last one whose payload starts at or before q, if q is inside it.
+__device__ __forceinline__ uint32_t split_row_of(const uint64_t* table, uint32_t lo, uint32_t hi, uint32_t q,
+                                                 uint64_t* entry) {
+    if (lo >= hi || split_row_pay(table[lo]) > q) return kPbSplitNone;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (split_row_pay(table[mid]) <= q) {
+            lo = mid;
+        } else {
+            hi = mid;
+        }
+    }
+    const uint64_t e = table[lo];
+    *entry = e;
+    return q - split_row_pay(e) < split_row_len(e) ? lo : kPbSplitNone;
+}
+
+// Varint kinds, a workgroup per message chunk. kPlace false: the check pass
+// (a varint the packed-run decoder refuses, inside a payload, is reported).
+// kPlace true: the place pass (every terminator inside a payload ends one
+// element). A varint's extent needs no row bounds: the byte in front of a
+// payload is the last of a length, so it has no continuation bit.
+template <bool kPlace>
+__global__ void __launch_bounds__(kRunThreads) pb_split_varint_kernel(const PbSplitJob* __restrict__ jobs, int njobs,
+                                                                      const uint32_t* __restrict__ exit,
+                                                                      const uint64_t* __restrict__ term_mask,
+                                                                      const uint32_t* __restrict__ term_group,
+                                                                      const uint32_t* __restrict__ term_chunk,
+                                                                      const uint32_t* __restrict__ row_chunk,
+                                                                      const uint32_t* __restrict__ row_bias,
+                                                                      uint32_t* __restrict__ bad,
+                                                                      const int32_t* __restrict__ ok) {
+    __shared__ u32x4 raw[kSplitStage16];
+    const int j = split_job_of(jobs, njobs, blockIdx.x, 0);
+    const PbSplitJob job = jobs[j];
+    if (!pb_rows::WireIsVarint(job.kind) || (kPlace && !ok[j])) return;
+    // the rows that start in this chunk, and the one before them that may reach into it
+    const uint32_t first = row_chunk[job.first_chunk];
+    const uint32_t hi = row_chunk[blockIdx.x + 1] - first;
+    uint32_t lo = row_chunk[blockIdx.x] - first;
+    lo = lo ? lo - 1 : 0;
+    if (lo >= hi) return;
+    const uint32_t t = threadIdx.x;
+    const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbSplitChunk;
+    const uint32_t len = job.n - cs < kPbSplitChunk ? job.n - cs : kPbSplitChunk;
+    const uint8_t* bytes = split_stage(job, cs, len, kSplitBack, raw);
+    const uint64_t* table = split_row_table(job, const_cast<uint32_t*>(exit));
+    const size_t g = (size_t)blockIdx.x * 64 + (t >> 2);
+    const uint64_t m = term_mask[g];
+    uint32_t terms = 0;  // terminators in front of this lane's bytes
+    if (kPlace) {
+        terms = term_chunk[blockIdx.x] - term_chunk[job.first_chunk] + term_group[g] +
+                (uint32_t)__popcll(m & ((1ull << ((t & 3) * 16)) - 1));
+    }
+    __syncthreads();
+    uint32_t mine = (uint32_t)(m >> ((t & 3) * 16)) & 0xFFFFu;
+    while (mine) {
+        const uint32_t bit = (uint32_t)__ffs((int)mine) - 1;
+        mine &= mine - 1;
+        const int i = (int)(t * 16 + bit);  // bytes[i - 10 ..] is staged when it is in the message
+        const uint32_t q = cs + (uint32_t)i;
+        uint32_t nb = 1;  // bytes of the varint that ends at q; 11: more than ten
+        uint64_t v = bytes[i] & 0x7f;
+        while (nb <= 10 && nb <= q && (bytes[i - (int)nb] & 0x80)) {
+            v = (v << 7) | (bytes[i - (int)nb] & 0x7f);
+            ++nb;
+        }
+        const bool refused = nb > 10 || (nb == 10 && bytes[i] > 1);
+        if (kPlace || refused) {
+            uint64_t e = 0;
+            const uint32_t r = split_row_of(table, lo, hi, q, &e);
+            if (r != kPbSplitNone) {
+                if (!kPlace) {
+                    atomicMin(&bad[j], (split_row_tag(e) << 3) | (uint32_t)pb_rows::kSplitMalformed);
+                } else {
+                    const uint32_t at = row_bias[job.first_row + r] + terms;
+                    if ((uint64_t)at < job.cap) pb_rows::StoreVarintElem(job.values, at, job.kind, v);
+                }
+            }
+        }
+        ++terms;
+    }
+}
+
+// A lane per row, 256 rows to a workgroup. kEnds false: the count pass (the
+// elements of each block of rows). kEnds true: row_ends, and for varint
+// kinds row_bias, of the jobs that passed.
+template <bool kEnds>
+__global__ void __launch_bounds__(kPbSplitBlockRows) pb_split_rows_kernel(const PbSplitJob* __restrict__ jobs,
+                                                                          int njobs,
+                                                                          const uint32_t* __restrict__ exit,
+                                                                          const uint64_t* __restrict__ term_mask,
+                                                                          const uint32_t* __restrict__ term_group,
+                                                                          const uint32_t* __restrict__ term_chunk,
+                                                                          const uint32_t* __restrict__ row_chunk,
+                                                                          uint32_t* __restrict__ block_sum,
+                                                                          uint32_t* __restrict__ row_bias,
+                                                                          const int32_t* __restrict__ ok) {
+    __shared__ uint32_t wave_tot[kPbSplitBlockRows / 64];
+    const int j = split_job_of(jobs, njobs, blockIdx.x, 1);
+    const PbSplitJob job = jobs[j];
+    if (kEnds && !ok[j]) return;
+    const uint32_t rows = split_total(row_chunk, job.first_chunk, job.nchunks);
+    const uint32_t r = (blockIdx.x - job.first_rblock) * kPbSplitBlockRows + threadIdx.x;
+    const bool varints = pb_rows::WireIsVarint(job.kind);
+    uint32_t ne = 0, front = 0;
+    if (r < rows) {
+        const uint64_t e = split_row_table(job, const_cast<uint32_t*>(exit))[r];
+        const uint32_t po = split_row_pay(e), pl = split_row_len(e);
+        if (varints) {
+            front = split_terms_before(job, term_mask, term_group, term_chunk, po);
+            ne = split_terms_before(job, term_mask, term_group, term_chunk, po + pl) - front;
+        } else {
+            ne = pl / pb_rows::SourceBytes(job.kind);
+        }
+    }
+    uint32_t before;
+    const uint32_t sum = rows_block_scan(ne, wave_tot, &before);
+    if (!kEnds) {
+        if (threadIdx.x == 0) block_sum[blockIdx.x] = sum;
+        return;
+    }
+    if (r >= rows) return;  // rows <= row_cap, count <= cap: the job passed
+    before += block_sum[blockIdx.x] - block_sum[job.first_rblock];
+    job.row_ends[r] = before + ne;
+    if (varints) row_bias[job.first_row + r] = before - front;
+}
+
+__global__ void __launch_bounds__(64) pb_split_publish_kernel(const PbSplitJob* __restrict__ jobs, int njobs,
+                                                              const uint32_t* __restrict__ row_chunk,
+                                                              const uint32_t* __restrict__ block_sum,
+                                                              const uint32_t* __restrict__ bad,
+                                                              const uint32_t* __restrict__ others,
+                                                              int32_t* __restrict__ ok,
+                                                              PbSplitResult* __restrict__ res) {
+    const int j = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (j >= njobs) return;
+    const PbSplitJob job = jobs[j];
+    const uint32_t key = bad[j];
+    PbSplitResult out = {0, 0, 0, kPbSplitNone, 0};
+    if (key != kPbSplitNone) {
+        out.first_bad = key >> 3;
+        out.err = (int32_t)(key & 7);
+    } else {
+        out.count = split_total(block_sum, job.first_rblock, job.nrblocks);
+        out.rows = split_total(row_chunk, job.first_chunk, job.nchunks);
+        out.others = others[j];
+        if (out.count > job.cap || out.rows > job.row_cap) out.err = pb_rows::kSplitShort;
+    }
+    ok[j] = out.err == 0;
+    res[j] = out;
+}
+
+// Fixed-width kinds and bytes: a workgroup per 2048 elements of the output.
+__global__ void __launch_bounds__(kRunThreads) pb_split_place_kernel(const PbSplitJob* __restrict__ jobs, int njobs,
+                                                                     const uint32_t* __restrict__ exit,
+                                                                     const uint32_t* __restrict__ row_chunk,
+                                                                     const uint32_t* __restrict__ block_sum,
+                                                                     const int32_t* __restrict__ ok) {
+    const int j = split_job_of(jobs, njobs, blockIdx.x, 2);
+    const PbSplitJob job = jobs[j];
+    if (!ok[j]) return;
+    const uint32_t count = split_total(block_sum, job.first_rblock, job.nrblocks);
+    const uint32_t rows = split_total(row_chunk, job.first_chunk, job.nchunks);
+    const uint32_t i0 = (blockIdx.x - job.first_ochunk) * kPbSplitOutChunk;
+    if (i0 >= count || rows == 0) return;
+    const uint32_t i1 = count - i0 < kPbSplitOutChunk ? count - 1 : i0 + kPbSplitOutChunk - 1;
+    const uint32_t* ends = job.row_ends;
+    // the first row whose end lies beyond element i, among rows [lo, hi]
+    auto row_of = [ends](uint32_t lo, uint32_t hi, uint32_t i) {
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (ends[mid] > i) {
+                hi = mid;
+            } else {
+                lo = mid + 1;
+            }
+        }
+        return lo;
+    };
+    const uint32_t r_lo = row_of(0, rows - 1, i0), r_hi = row_of(r_lo, rows - 1, i1);
+    const uint64_t* table = split_row_table(job, const_cast<uint32_t*>(exit));
+    const uint32_t w = pb_rows::SourceBytes(job.kind);
+    for (uint32_t k = 0; k < kPbSplitOutChunk / kRunThreads; ++k) {
+        const uint32_t i = i0 + k * kRunThreads + threadIdx.x;
+        if (i > i1) break;
+        const uint32_t r = row_of(r_lo, r_hi, i);
+        const uint32_t start = r ? ends[r - 1] : 0;
+        const uint64_t e = table[r];
+        const uint32_t off = (i - start) * w;
+        if (i < start || off + w > split_row_len(e)) continue;  // never: row_ends are sums of these lengths
+        const uint8_t* s = job.msg + split_row_pay(e) + off;
+        uint64_t v = 0;
+        for (uint32_t b = 0; b < w; ++b) v |= (uint64_t)s[b] << (8 * b);
+        if (w == 1) {
+            static_cast<uint8_t*>(job.values)[i] = (uint8_t)v;
+        } else if (w == 4) {
+            static_cast<uint32_t*>(job.values)[i] = (uint32_t)v;
+        } else {
+            static_cast<uint64_t*>(job.values)[i] = v;
+        }
+    }
+}
+
 }  // namespace
+
+int LaunchPbRowsSplit(const PbSplitTables& t, hipStream_t s) {
+    if (t.njobs <= 0) return 0;
+    if (!t.jobs || !t.jobs_dev || !t.exit || !t.term_mask || !t.row_mask || !t.term_group || !t.term_chunk ||
+        !t.row_chunk || !t.entry || !t.block_sum || !t.bad || !t.others || !t.ok || !t.res || t.nchunks == 0 ||
+        t.nrblocks == 0 || t.nchunks > 0x7FFFFFFEu || t.nrblocks > 0x7FFFFFFEu || (t.nrows > 0 && !t.row_bias) ||
+        t.skip_hops == 0 || (t.skip_hops > 1 && (!t.skip || !t.land))) {
+        return -1;
+    }
+    const bool skips = t.skip_hops > 1;
+    const dim3 per_job((unsigned)(t.njobs + 63) / 64), wave(64), wg(kRunThreads);
+#define SPLIT_LAUNCH(kernel, grid, block, ...)                          \
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, t.jobs_dev, t.njobs, __VA_ARGS__); \
+    if (hipGetLastError() != hipSuccess) return -1
+    hipLaunchKernelGGL(pb_split_init_kernel, per_job, wave, 0, s, t.jobs, t.njobs, t.jobs_dev, t.term_chunk,
+                       t.row_chunk, t.block_sum, t.nchunks, t.nrblocks, t.bad, t.others, t.ok);
+    if (hipGetLastError() != hipSuccess) return -1;
+    SPLIT_LAUNCH(pb_split_spec_kernel, dim3(t.nchunks), wg, t.exit, t.term_mask, t.term_group, t.term_chunk, t.entry,
+                 skips ? t.land : nullptr);
+    if (t.any_varint && LaunchPbRunPrefix(t.term_chunk, (int)t.nchunks + 1, s) != 0) return -1;
+    if (skips) {
+        SPLIT_LAUNCH(pb_split_skip_kernel, dim3(t.nchunks), wg, t.exit, t.skip, t.skip_hops);
+        SPLIT_LAUNCH(pb_split_chase_kernel, per_job, wave, t.skip, t.land);
+        SPLIT_LAUNCH(pb_split_fill_kernel, dim3((t.nchunks + 63) / 64), wave, t.exit, t.land, t.entry, t.skip_hops,
+                     t.nchunks);
+    } else {
+        SPLIT_LAUNCH(pb_split_chase_kernel, per_job, wave, t.exit, t.entry);
+    }
+    SPLIT_LAUNCH(pb_split_mark_kernel, dim3(t.nchunks), wg, t.entry, t.row_mask, t.row_chunk, t.bad, t.others);
+    if (LaunchPbRunPrefix(t.row_chunk, (int)t.nchunks + 1, s) != 0) return -1;
+    SPLIT_LAUNCH(pb_split_table_kernel, dim3(t.nchunks), wg, t.row_mask, t.row_chunk, t.exit, t.bad);
+    if (t.any_varint) {
+        SPLIT_LAUNCH(pb_split_varint_kernel<false>, dim3(t.nchunks), wg, t.exit, t.term_mask, t.term_group,
+                     t.term_chunk, t.row_chunk, t.row_bias, t.bad, t.ok);
+    }
+    SPLIT_LAUNCH(pb_split_rows_kernel<false>, dim3(t.nrblocks), dim3(kPbSplitBlockRows), t.exit, t.term_mask,
+                 t.term_group, t.term_chunk, t.row_chunk, t.block_sum, t.row_bias, t.ok);
+    if (LaunchPbRunPrefix(t.block_sum, (int)t.nrblocks + 1, s) != 0) return -1;
+    SPLIT_LAUNCH(pb_split_publish_kernel, per_job, wave, t.row_chunk, t.block_sum, t.bad, t.others, t.ok, t.res);
+    SPLIT_LAUNCH(pb_split_rows_kernel<true>, dim3(t.nrblocks), dim3(kPbSplitBlockRows), t.exit, t.term_mask,
+                 t.term_group, t.term_chunk, t.row_chunk, t.block_sum, t.row_bias, t.ok);
+    if (t.any_varint) {
+        SPLIT_LAUNCH(pb_split_varint_kernel<true>, dim3(t.nchunks), wg, t.exit, t.term_mask, t.term_group,
+                     t.term_chunk, t.row_chunk, t.row_bias, t.bad, t.ok);
+    }
+    if (t.nochunks > 0) {
+        SPLIT_LAUNCH(pb_split_place_kernel, dim3(t.nochunks), wg, t.exit, t.row_chunk, t.block_sum, t.ok);
+    }
+#undef SPLIT_LAUNCH
+    return 0;
+}
 
 int LaunchPbRowsBuild(const PbRowsTables& t, hipStream_t s) {
     if (t.njobs <= 0) return 0;

@@ -292,6 +292,36 @@ void bind_gpu_ops(py::module_& g) {
         for (const gpu::DeviceRowsJob& j : js) out.append(py::make_tuple(j.len, j.err, j.first_bad));
         return out;
     }, py::arg("jobs"), py::arg("device") = 0);
+    // The way back: jobs = [(number, inner, kind, msg, n, values, cap,
+    // row_ends, row_cap)], msg / values / row_ends device pointers ->
+    // [(count, rows, others, err, first_bad)] (gpu::DeviceSplitRows; all jobs
+    // share one launch sequence).
+    g.def("device_split_rows", [](const std::vector<RowsJobRow>& jobs, int device) {
+        std::vector<gpu::DeviceRowsSplitJob> js(jobs.size());
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            js[i].number = std::get<0>(jobs[i]);
+            js[i].inner = std::get<1>(jobs[i]);
+            js[i].kind = std::get<2>(jobs[i]);
+            js[i].msg = (const void*)std::get<3>(jobs[i]);
+            js[i].n = std::get<4>(jobs[i]);
+            js[i].values = (void*)std::get<5>(jobs[i]);
+            js[i].cap = std::get<6>(jobs[i]);
+            js[i].row_ends = (uint32_t*)std::get<7>(jobs[i]);
+            js[i].row_cap = std::get<8>(jobs[i]);
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceSplitRows(js.data(), (int)js.size(), device);
+        }
+        check(rc, "device_split_rows");
+        py::list out;
+        for (const gpu::DeviceRowsSplitJob& j : js) {
+            out.append(py::make_tuple(j.count, j.rows, j.others, j.err, j.first_bad));
+        }
+        return out;
+    }, py::arg("jobs"), py::arg("device") = 0);
+    g.def("device_split_max_bytes", []() { return gpu::kDeviceSplitMaxBytes; });
     g.def("device_rows_worst_case", [](uint32_t number, uint32_t inner, uint32_t kind, uint64_t count, uint64_t rows) {
         gpu::DeviceRowsJob j;
         j.number = number;

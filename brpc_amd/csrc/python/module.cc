@@ -19,6 +19,7 @@
 #include "gpu/copy_engine.h"
 #include "rpc/compress.h"
 #include "gpu/hbm_pool.h"
+#include "gpu/scoped.h"
 #include "gpu/snappy_offload.h"
 #include "gpu/json_offload.h"
 #include "gpu/codec_batch.h"
@@ -103,6 +104,8 @@ private:
 
 class PyChannel {
 public:
+    typedef std::vector<std::tuple<uint32_t, uint32_t, uintptr_t, uint64_t>> MessageFields;
+    typedef std::tuple<uint32_t, uint32_t, uint32_t, uintptr_t, uint64_t, uintptr_t, uint64_t> RowsSource;
     PyChannel(const std::string& server, const std::string& lb, const std::string& protocol,
               const std::string& connection_type, int timeout_ms, int max_retry) {
         GlobalInitializeOrDie();
@@ -138,12 +141,74 @@ public:
     // count)], then the block gpu::BuildDeviceRows makes of `rows` (number,
     // inner, kind, src, count, row_ends, nrows), appended to one Buf (protobuf
     // concatenation is merge). Returns the echoed attachment's bytes.
-    py::bytes echo_device_rows(const std::vector<std::tuple<uint32_t, uint32_t, uintptr_t, uint64_t>>& fields,
-                               const std::tuple<uint32_t, uint32_t, uint32_t, uintptr_t, uint64_t, uintptr_t, uint64_t>& rows,
-                               int device) {
+    py::bytes echo_device_rows(const MessageFields& fields, const RowsSource& rows, int device) {
+        Controller cntl;
+        std::string got;
+        int copy_rc = 0;
+        echo_rows(fields, rows, device, &cntl, [&]() { copy_rc = gpu::CopyBufToHost(cntl.response_attachment(), &got); });
+        if (copy_rc != 0) throw std::runtime_error("copying the echoed attachment to the host failed");
+        return py::bytes(got);
+    }
+    // The same round trip, then the echoed attachment is split where it
+    // arrived (gpu::DeviceSplitRows on its device block; blocks that arrived
+    // apart are gathered into one in HBM first): only the split's outputs come
+    // to the host. Returns (values bytes, row_ends list, others).
+    py::tuple echo_device_rows_split(const MessageFields& fields, const RowsSource& rows, int device) {
+        Controller cntl;
+        gpu::DeviceRowsSplitJob job;
+        job.number = std::get<0>(rows);
+        job.inner = std::get<1>(rows);
+        job.kind = std::get<2>(rows);
+        if (!pb_rows::FieldsOk(job.number, job.inner, job.kind)) throw std::invalid_argument("rows job refused");
+        std::string values;
+        std::vector<uint32_t> row_ends;
+        int rc = 0;
+        echo_rows(fields, rows, device, &cntl, [&]() {
+            const Buf& got = cntl.response_attachment();
+            Buf gathered;
+            const Buf* one = &got;
+            if (got.backing_block_num() != 1 || got.ref_at(0).block->kind != MemKind::DEVICE ||
+                got.ref_at(0).block->device != device) {
+                if (gpu::GatherToDevice(got, &gathered, device) != 0 || gathered.backing_block_num() != 1) {
+                    rc = -1;
+                    return;
+                }
+                one = &gathered;
+            }
+            job.msg = one->block_data(0);
+            job.n = one->block_len(0);
+            const size_t eb = pb_rows::SourceBytes(job.kind);
+            job.cap = job.n / (pb_rows::WireIsVarint(job.kind) ? 1 : eb);
+            job.row_cap = job.n / 2;
+            gpu::HbmBlock vals(std::max<size_t>(job.cap * eb, 16), device), ends(std::max<size_t>(job.row_cap * 4, 16), device);
+            if (!vals || !ends) {
+                rc = -1;
+                return;
+            }
+            job.values = vals.p;
+            job.row_ends = ends.as<uint32_t>();
+            rc = gpu::DeviceSplitRows(&job, 1, device);
+            if (rc != 0 || job.err != 0) return;
+            values.resize((size_t)job.count * eb);
+            row_ends.resize((size_t)job.rows);
+            if (!values.empty()) rc = gpu::CopyDeviceToHost(&values[0], vals.p, values.size(), device);
+            if (rc == 0 && !row_ends.empty()) rc = gpu::CopyDeviceToHost(row_ends.data(), ends.p, row_ends.size() * 4, device);
+        });
+        if (rc != 0) throw std::runtime_error("splitting the echoed attachment on the device failed");
+        if (job.err != 0) {
+            throw std::runtime_error("the echoed attachment does not split (code " + std::to_string(job.err) + ", offset " +
+                                     std::to_string(job.first_bad) + ")");
+        }
+        return py::make_tuple(py::bytes(values), row_ends, job.others);
+    }
+
+private:
+    // Builds the two blocks, echoes them and runs `then` on the response
+    // (without the GIL); throws what the build or the RPC reports.
+    template <typename F>
+    void echo_rows(const MessageFields& fields, const RowsSource& rows, int device, Controller* cntl, F&& then) {
         example::EchoRequest req;
         example::EchoResponse res;
-        Controller cntl;
         req.set_message("rows");
         std::vector<gpu::DeviceMessageField> fs(fields.size());
         for (size_t i = 0; i < fields.size(); ++i) {
@@ -160,27 +225,23 @@ public:
         job.count = std::get<4>(rows);
         job.row_ends = (const uint32_t*)std::get<5>(rows);
         job.rows = std::get<6>(rows);
-        std::string got;
-        int rc = 0, copy_rc = 0;
+        int rc = 0;
         {
             py::gil_scoped_release nogil;
-            if (!fs.empty()) rc = gpu::BuildDeviceMessage(fs.data(), (int)fs.size(), &cntl.request_attachment(), device);
-            if (rc == 0) rc = gpu::BuildDeviceRows(job, &cntl.request_attachment(), device);
+            if (!fs.empty()) rc = gpu::BuildDeviceMessage(fs.data(), (int)fs.size(), &cntl->request_attachment(), device);
+            if (rc == 0) rc = gpu::BuildDeviceRows(job, &cntl->request_attachment(), device);
             if (rc == 0) {
                 example::EchoService_Stub stub(&_ch);
-                stub.Echo(&cntl, &req, &res, nullptr);
-                if (!cntl.Failed()) copy_rc = gpu::CopyBufToHost(cntl.response_attachment(), &got);
+                stub.Echo(cntl, &req, &res, nullptr);
+                if (!cntl->Failed()) then();
             }
         }
         if (rc != 0) throw std::runtime_error("building the attachment on the device failed (code " + std::to_string(rc) + ")");
-        if (cntl.Failed()) {
-            throw std::runtime_error("[E" + std::to_string(cntl.ErrorCode()) + "] " + cntl.ErrorText());
+        if (cntl->Failed()) {
+            throw std::runtime_error("[E" + std::to_string(cntl->ErrorCode()) + "] " + cntl->ErrorText());
         }
-        if (copy_rc != 0) throw std::runtime_error("copying the echoed attachment to the host failed");
-        return py::bytes(got);
     }
 
-private:
     Channel _ch;
 };
 
@@ -519,6 +580,23 @@ PYBIND11_MODULE(_native, m) {
         return py::make_tuple(ok, err, out);
     }, py::arg("proto_dir"), py::arg("proto_file"), py::arg("type_name"), py::arg("wire"),
        py::arg("bytes_to_base64") = false, py::arg("pretty") = false);
+    // wire bytes -> message, nothing else: whether the dynamic host parser
+    // (the type imported from a .proto at run time) takes them. The host
+    // baseline of benchmarks/device_rows_split_bw.py.
+    m.def("pb_dynamic_parse", [](const std::string& proto_dir, const std::string& proto_file,
+                                 const std::string& type_name, py::bytes wire) {
+        pb::Importer imp({proto_dir});
+        std::string err;
+        if (!imp.Import(proto_file, &err)) throw std::runtime_error("import " + proto_file + ": " + err);
+        const pb::Descriptor* d = imp.FindMessageTypeByName(type_name);
+        if (!d || !d->prototype) throw std::invalid_argument("unknown message type " + type_name);
+        std::unique_ptr<pb::Message> msg(d->prototype->New());
+        char* data = nullptr;
+        Py_ssize_t size = 0;
+        if (PyBytes_AsStringAndSize(wire.ptr(), &data, &size) != 0) throw py::error_already_set();
+        py::gil_scoped_release nogil;
+        return msg->ParsePartialFromArray(data, (size_t)size);
+    }, py::arg("proto_dir"), py::arg("proto_file"), py::arg("type_name"), py::arg("wire"));
     // the text json::Value prints for a double (json::AppendShortestDouble;
     // non-finite values as quoted strings): the oracle of the array printers
     m.def("json_shortest_double", [](double x) { return py::bytes(json::Value(x).ToString()); });
@@ -616,6 +694,30 @@ PYBIND11_MODULE(_native, m) {
                                           row_ends.size(), &out, &first_bad);
         return py::make_tuple(err, first_bad, py::bytes(out));
     }, py::arg("number"), py::arg("inner"), py::arg("kind"), py::arg("values"), py::arg("row_ends"));
+    // The host twin of gpu::DeviceSplitRows (pb::SplitRows): the message's
+    // rows of field `number` -> (err, count, rows, others, first_bad, values
+    // bytes, row_ends list). max_elems / max_rows are the outputs' capacities
+    // (default: what any message of this size can hold); values and row_ends
+    // are empty unless err is 0.
+    m.def("pb_split_rows", [](uint32_t number, uint32_t inner, uint32_t kind, py::bytes message, py::object max_elems,
+                              py::object max_rows) {
+        if (kind > pb_rows::kKindFixed64) throw std::invalid_argument("kind must be 0..9");
+        const std::string msg = message;
+        const size_t eb = pb_rows::SourceBytes(kind);
+        const uint64_t cap = max_elems.is_none() ? msg.size() / (pb_rows::WireIsVarint(kind) ? 1 : eb)
+                                                 : max_elems.cast<uint64_t>();
+        const uint64_t row_cap = max_rows.is_none() ? msg.size() / 2 : max_rows.cast<uint64_t>();
+        std::vector<uint64_t> values((size_t)(cap * eb + 7) / 8 + 1);
+        std::vector<uint32_t> row_ends((size_t)row_cap + 1);
+        uint64_t count = 0, rows = 0, others = 0, first_bad = 0;
+        const int err = pb::SplitRows(number, inner, kind, msg.data(), msg.size(), values.data(), cap, row_ends.data(),
+                                      row_cap, &count, &rows, &others, &first_bad);
+        row_ends.resize(err == 0 ? (size_t)rows : 0);
+        return py::make_tuple(err, count, rows, others, first_bad,
+                              py::bytes(reinterpret_cast<const char*>(values.data()), err == 0 ? (size_t)count * eb : 0),
+                              row_ends);
+    }, py::arg("number"), py::arg("inner"), py::arg("kind"), py::arg("message"), py::arg("max_elems") = py::none(),
+       py::arg("max_rows") = py::none());
     // The host base64 coder (base/util.h over base/base64.h), reading the
     // bytes object in place: the text pb2json gives a bytes field, and what
     // json2pb makes of one (None where base64_decode refuses the text).
@@ -719,6 +821,8 @@ PYBIND11_MODULE(_native, m) {
         .def("echo", &PyChannel::echo, py::arg("message"), py::arg("attachment") = py::bytes(),
              py::arg("sleep_us") = 0)
         .def("echo_device_rows", &PyChannel::echo_device_rows, py::arg("fields"), py::arg("rows"),
+             py::arg("device") = 0)
+        .def("echo_device_rows_split", &PyChannel::echo_device_rows_split, py::arg("fields"), py::arg("rows"),
              py::arg("device") = 0);
 
     py::class_<PyStreamPress>(m, "StreamPress")
@@ -922,6 +1026,8 @@ PYBIND11_MODULE(_native, m) {
         d["built_row_jobs"] = s.built_row_jobs;
         d["built_rows"] = s.built_rows;
         d["built_row_bytes"] = s.built_row_bytes;
+        d["split_row_jobs"] = s.split_row_jobs;
+        d["split_rows"] = s.split_rows;
         d["built_fields"] = s.built_fields;
         d["built_bytes"] = s.built_bytes;
         d["build_errors"] = s.build_errors;

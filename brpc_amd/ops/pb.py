@@ -178,6 +178,61 @@ def pb_build_rows(number, values, row_ends, kind_name, inner=None):
     return out[:n]
 
 
+SPLIT_ERRORS = {
+    1: "malformed wire",
+    2: "refused (field number, inner, kind or size)",
+    5: "more elements or rows than max_elems / max_rows",
+    6: "well-formed, but a row is not one packed field (or the field is no sub-message): use the host parser",
+}
+
+
+def pb_split_rows(message, number, kind_name, inner=None, max_elems=None, max_rows=None):
+    """The inverse of ``pb_build_rows`` (``gpu::DeviceSplitRows``): every
+    occurrence of field ``number`` in ``message`` (a uint8 device tensor) is a
+    row; other top-level fields are skipped, so a whole ``Batch { string
+    model = 1; repeated Row rows = 4; }`` splits as it is.
+
+    Returns ``(values, row_ends)``, both trimmed: values holds the elements
+    of all rows in the dtype of the kind (the first one ``pb_build_rows``
+    takes for it; uint8 for bytes), row_ends is int32 with ``row_ends[r]`` the
+    elements in rows 0..r. ``pb_build_rows(number, values, row_ends, ...)``
+    gives a canonical message of rows alone back byte for byte.
+
+    max_elems / max_rows size the outputs; without them they hold what any
+    message of this size can: ``n // wire-minimum`` elements, ``n // 2`` rows.
+    The splitter runs on its own stream: the caller's current stream is
+    synchronized first, as in ``pb_build_rows``."""
+    if kind_name not in _ROW_KINDS:
+        raise ValueError("unknown kind %r (one of %s)" % (kind_name, ", ".join(_ROW_KINDS)))
+    kind, dtypes = _ROW_KINDS[kind_name]
+    dtype = dtypes[0] if dtypes else torch.uint8
+    require_gpu_tensor(message, "message")
+    if message.dtype != torch.uint8 or message.dim() != 1:
+        raise TypeError("message must be a 1-D uint8 tensor")
+    message = message.contiguous()
+    dev = message.device
+    n = message.numel()
+    if n > native.gpu.device_split_max_bytes():
+        raise ValueError("pb_split_rows: a message of %d bytes is above device_split_max_bytes()" % n)
+    eb = torch.empty(0, dtype=dtype).element_size()
+    cap = n // (eb if kind >= 8 else 1) if max_elems is None else int(max_elems)
+    row_cap = n // 2 if max_rows is None else int(max_rows)
+    values = torch.empty(max(cap, 1), dtype=dtype, device=dev)
+    row_ends = torch.empty(max(row_cap, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (count, rows, _, err, first_bad), = native.gpu.device_split_rows(
+            [(int(number), int(inner or 0), kind, message.data_ptr() if n else 0, n, values.data_ptr(), cap,
+              row_ends.data_ptr(), row_cap)], dev.index or 0)
+    if err in (1, 6):
+        raise ValueError("pb_split_rows: %s (offset %d)" % (SPLIT_ERRORS[err], first_bad))
+    if err == 5:
+        raise ValueError("pb_split_rows: %s (%d elements, %d rows)" % (SPLIT_ERRORS[5], count, rows))
+    if err:
+        raise ValueError("pb_split_rows: " + SPLIT_ERRORS.get(err, "code %d" % err))
+    return values[:count], row_ends[:rows]
+
+
 def pb_scan_host(msg, max_fields=16):
     """Pure-python reference of one message's scan (tests)."""
     out, p = [], 0
