@@ -1,0 +1,752 @@
+// JSON string bodies in device memory on gfx950: escape, unescape and the
+// UTF-8 verdict (kernels.h JsonStringJob has the passes; the reference does
+// all three on the host, through rapidjson's Writer and Reader). The rules
+// are base/json_string.h, the code the host twins in json/json.cc run.
+//
+// A workgroup of 256 lanes takes one chunk of kJsonStringChunkBytes of one
+// job, a lane 16 bytes. Global loads are aligned 16-byte loads from the
+// aligned-down address (they stay inside 16-byte units that hold a byte of the
+// job) into an LDS stage; what leaves goes through jstr_copy_out: bytes up to
+// the first 16-byte boundary of dst, 16-byte stores, bytes for the rest. The
+// shift between the two alignments happens on chip.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "base/json_string.h"
+#include "gpu/kernels.h"
+
+namespace mrpc {
+namespace gpu {
+
+namespace {
+
+namespace js = ::mrpc::json_string;
+typedef uint32_t jstr_u32x4 __attribute__((ext_vector_type(4)));
+constexpr int kJstrThreads = 256;
+constexpr uint32_t kC = kJsonStringChunkBytes;
+constexpr uint32_t kNone = kJsonStringNone;
+static_assert(kJstrThreads * 16 == kC, "a lane per 16 bytes");
+static_assert(kC / kJsonStringGroupBytes == 64, "64 groups per chunk");
+
+// the job that owns this chunk: the last whose first_chunk is not past it
+__device__ __forceinline__ int jstr_job_of_chunk(const JsonStringJob* __restrict__ jobs, int njobs, uint32_t chunk) {
+    int ja = 0, jb = njobs - 1;
+    while (ja < jb) {
+        const int mid = (ja + jb + 1) / 2;
+        if (jobs[mid].first_chunk <= chunk) ja = mid;
+        else jb = mid - 1;
+    }
+    return ja;
+}
+__device__ __forceinline__ int jstr_job_of_rblock(const JsonStringJob* __restrict__ jobs, int njobs, uint32_t rb) {
+    int ja = 0, jb = njobs - 1;
+    while (ja < jb) {
+        const int mid = (ja + jb + 1) / 2;
+        if (jobs[mid].first_rblock <= rb) ja = mid;
+        else jb = mid - 1;
+    }
+    return ja;
+}
+
+__device__ __forceinline__ uint32_t jstr_shift(uint32_t lo, uint32_t hi, uint32_t sh) {
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
+}
+
+// The staged span of a chunk: job bytes [at - back, at + len + fwd) cut to
+// [0, n), loaded as whole 16-byte units. stage[pos0 + (i - at)] is job byte i.
+struct JstrStage {
+    const uint8_t* bytes;  // LDS
+    int pos0;              // index of job byte `at`
+    __device__ __forceinline__ uint8_t at(int64_t rel) const { return bytes[pos0 + rel]; }
+};
+constexpr uint32_t kStageBack = 16, kStageFwd = 12;
+constexpr int kStage16 = (int)(kStageBack + 15 + kC + kStageFwd + 15) / 16 + 1;  // and a dword to spare
+
+__device__ __forceinline__ JstrStage jstr_stage(jstr_u32x4* stage16, const uint8_t* src, uint32_t n, uint32_t at,
+                                                uint32_t len, uint32_t back, uint32_t fwd) {
+    const uint32_t lo = at < back ? 0u : at - back;
+    const uint64_t want = (uint64_t)at + len + fwd;
+    const uint32_t hi = want > n ? n : (uint32_t)want;  // lo < hi: the chunk holds a byte
+    const uint8_t* first = src + lo;
+    const uint32_t a = (uint32_t)((uintptr_t)first & 15);
+    const jstr_u32x4* from = reinterpret_cast<const jstr_u32x4*>(first - a);
+    const uint32_t nstage = (a + (hi - lo) + 15) / 16;  // <= kStage16 - 1
+    for (uint32_t u = threadIdx.x; u < nstage; u += kJstrThreads) stage16[u] = from[u];
+    JstrStage st;
+    st.bytes = reinterpret_cast<const uint8_t*>(stage16);
+    st.pos0 = (int)(a + (at - lo));
+    return st;
+}
+
+// image bytes [ioff, ioff + total) (LDS dwords, readable 8 bytes past the
+// last one) -> dst at any alignment. The caller has synchronized the image.
+__device__ __forceinline__ void jstr_copy_out(const uint32_t* image, uint32_t ioff, uint8_t* __restrict__ dst,
+                                              uint32_t total) {
+    const uint32_t t = threadIdx.x;
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(image) + ioff;
+    uint32_t head = (16u - (uint32_t)((uintptr_t)dst & 15)) & 15;
+    if (head > total) head = total;
+    if (t < head) dst[t] = bytes[t];
+    const uint32_t nv = (total - head) / 16;
+    const uint32_t sh = ((ioff + head) & 3) * 8;  // uniform: where a unit starts inside an LDS dword
+    jstr_u32x4* body = reinterpret_cast<jstr_u32x4*>(dst + head);
+    for (uint32_t v = t; v < nv; v += kJstrThreads) {
+        const uint32_t w = (ioff + head + 16 * v) >> 2;
+        jstr_u32x4 x;
+        if (sh == 0) {
+            x.x = image[w];
+            x.y = image[w + 1];
+            x.z = image[w + 2];
+            x.w = image[w + 3];
+        } else {
+            const uint32_t d0 = image[w], d1 = image[w + 1], d2 = image[w + 2], d3 = image[w + 3], d4 = image[w + 4];
+            x.x = jstr_shift(d0, d1, sh);
+            x.y = jstr_shift(d1, d2, sh);
+            x.z = jstr_shift(d2, d3, sh);
+            x.w = jstr_shift(d3, d4, sh);
+        }
+        body[v] = x;
+    }
+    for (uint32_t j = head + 16 * nv + t; j < total; j += kJstrThreads) dst[j] = bytes[j];
+}
+
+// The lane's 16 bytes of the chunk as two words; what lies past `mine` bytes
+// reads as '0' (plain, no backslash, ASCII).
+__device__ __forceinline__ void jstr_words_at(const JstrStage& st, uint32_t p, uint32_t mine, uint64_t* w0,
+                                              uint64_t* w1) {
+    const uint32_t* dw = reinterpret_cast<const uint32_t*>(st.bytes);
+    uint64_t a = 0x3030303030303030ull, b = 0x3030303030303030ull;
+    if (mine != 0) {
+        const uint32_t w = p >> 2, sh = (p & 3) * 8;
+        const uint32_t d0 = dw[w], d1 = dw[w + 1], d2 = dw[w + 2], d3 = dw[w + 3], d4 = dw[w + 4];
+        a = (uint64_t)jstr_shift(d0, d1, sh) | (uint64_t)jstr_shift(d1, d2, sh) << 32;
+        b = (uint64_t)jstr_shift(d2, d3, sh) | (uint64_t)jstr_shift(d3, d4, sh) << 32;
+        if (mine < 16) {
+            const uint64_t keep_a = mine >= 8 ? ~0ull : (1ull << (8 * mine)) - 1;
+            const uint64_t keep_b = mine <= 8 ? 0ull : (1ull << (8 * (mine - 8))) - 1;
+            a = (a & keep_a) | (0x3030303030303030ull & ~keep_a);
+            b = (b & keep_b) | (0x3030303030303030ull & ~keep_b);
+        }
+    }
+    *w0 = a;
+    *w1 = b;
+}
+__device__ __forceinline__ void jstr_lane_words(const JstrStage& st, uint32_t mine, uint64_t* w0, uint64_t* w1) {
+    jstr_words_at(st, (uint32_t)st.pos0 + 16 * threadIdx.x, mine, w0, w1);
+}
+// a bit per byte of the two words that equals c
+__device__ __forceinline__ uint32_t jstr_bits_of(uint64_t w0, uint64_t w1, uint8_t c) {
+    const uint64_t spread = 0x0102040810204080ull;
+    return (uint32_t)(((js::EqMask8(w0, c) >> 7) * spread) >> 56) | (uint32_t)(((js::EqMask8(w1, c) >> 7) * spread) >> 56) << 8;
+}
+
+// Exclusive scan of v over the workgroup; *total its sum. part: 5 words of LDS.
+__device__ __forceinline__ uint32_t jstr_block_scan(uint32_t v, uint32_t* part, uint32_t* total) {
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(incl, off, 64);
+        if (lane >= (uint32_t)off) incl += y;
+    }
+    __syncthreads();  // part may still be read from an earlier scan
+    if (lane == 63) part[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, sum = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kJstrThreads / 64; ++k) {
+        const uint32_t x = part[k];
+        if (k < wave) before += x;
+        sum += x;
+    }
+    *total = sum;
+    return before + incl - v;
+}
+
+__device__ __forceinline__ uint32_t jstr_mine(uint32_t len) {
+    const uint32_t o = 16 * threadIdx.x;
+    return o < len ? (len - o < 16 ? len - o : 16u) : 0u;
+}
+
+// ------------------------------------------------------------------ escape
+
+__global__ void __launch_bounds__(kJstrThreads) jstr_escape_size_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
+                                                                        uint32_t* __restrict__ prefix,
+                                                                        uint32_t* __restrict__ groups) {
+    __shared__ jstr_u32x4 stage16[kStage16];
+    __shared__ uint32_t part[8];
+    const uint32_t t = threadIdx.x;
+    const int ji = jstr_job_of_chunk(jobs, njobs, blockIdx.x);
+    const JsonStringJob job = jobs[ji];
+    const uint32_t c = blockIdx.x - job.first_chunk;
+    if (c >= job.nchunks) return;  // uniform
+    const uint32_t at = c * kC, left = job.n - at, len = left < kC ? left : kC;
+    const JstrStage st = jstr_stage(stage16, job.src, job.n, at, len, 0, 0);
+    __syncthreads();
+    const uint32_t mine = jstr_mine(len);
+    uint64_t w0, w1;
+    jstr_lane_words(st, mine, &w0, &w1);
+    const uint32_t size = js::EscapedSize8(w0) + js::EscapedSize8(w1) - (16 - mine);
+    uint32_t total;
+    const uint32_t before = jstr_block_scan(size, part, &total);
+    if (job.row_ends && (t & 3) == 0) groups[job.first_group + c * 64 + (t >> 2)] = before;
+    if (t == 0) prefix[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(kJstrThreads) jstr_rows_check_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
+                                                                       uint32_t* __restrict__ bad) {
+    const int ji = jstr_job_of_rblock(jobs, njobs, blockIdx.x);
+    const JsonStringJob job = jobs[ji];
+    if (!job.row_ends) return;
+    const uint64_t r = (uint64_t)(blockIdx.x - job.first_rblock) * kJsonStringBlockRows + threadIdx.x;
+    if (r >= job.rows) return;
+    const uint32_t end = job.row_ends[r], prev = r ? job.row_ends[r - 1] : 0u;
+    if (end < prev || (r == job.rows - 1 && end != job.n)) atomicMin(&bad[ji], (uint32_t)r);
+}
+
+// a lane per job, after the prefix scan: shared by escape and unescape
+__global__ void jstr_verdict_kernel(const JsonStringJob* __restrict__ jobs, int njobs, const uint32_t* __restrict__ prefix,
+                                    const uint32_t* __restrict__ bad, int32_t* __restrict__ ok,
+                                    JsonStringResult* __restrict__ res) {
+    const int ji = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (ji >= njobs) return;
+    const JsonStringJob job = jobs[ji];
+    const uint64_t body = (uint32_t)(prefix[job.first_chunk + job.nchunks] - prefix[job.first_chunk]);
+    uint64_t len = body;
+    if (job.row_ends) len += 3ull * job.rows - 1;
+    else if (job.quote) len += 2;
+    JsonStringResult r;
+    r.len = len;
+    r.first_bad = 0;
+    r.err = 0;
+    const uint32_t b = bad[ji];
+    if (b != kNone) {
+        r.err = 1;
+        r.first_bad = b;
+        r.len = 0;
+    } else if (len > job.cap) {
+        r.err = 3;
+    } else if (!job.row_ends && job.quote) {
+        job.dst[0] = '"';
+        job.dst[len - 1] = '"';
+    }
+    ok[ji] = r.err == 0;
+    res[ji] = r;
+}
+
+// escaped bytes in front of source byte x of the job (x <= n)
+__device__ __forceinline__ uint32_t jstr_escaped_before(const JsonStringJob& job, const uint32_t* __restrict__ prefix,
+                                                        const uint32_t* __restrict__ groups, uint32_t x) {
+    if (x >= job.n) return prefix[job.first_chunk + job.nchunks] - prefix[job.first_chunk];
+    const uint32_t c = x / kC, g = (x % kC) / kJsonStringGroupBytes;
+    uint32_t e = prefix[job.first_chunk + c] - prefix[job.first_chunk] + groups[job.first_group + c * 64 + g];
+    for (uint32_t i = c * kC + g * kJsonStringGroupBytes; i < x; ++i) e += js::EscapedSize(job.src[i]);
+    return e;
+}
+
+__global__ void __launch_bounds__(kJstrThreads) jstr_rows_punct_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
+                                                                       const uint32_t* __restrict__ prefix,
+                                                                       const uint32_t* __restrict__ groups,
+                                                                       const int32_t* __restrict__ ok) {
+    const int ji = jstr_job_of_rblock(jobs, njobs, blockIdx.x);
+    const JsonStringJob job = jobs[ji];
+    if (!job.row_ends || !ok[ji]) return;
+    const uint64_t r = (uint64_t)(blockIdx.x - job.first_rblock) * kJsonStringBlockRows + threadIdx.x;
+    if (r >= job.rows) return;
+    // ok: the ends ascend to n, so both lie inside the source
+    const uint32_t start = r ? job.row_ends[r - 1] : 0u, end = job.row_ends[r];
+    const uint32_t es = jstr_escaped_before(job, prefix, groups, start);
+    const uint32_t ee = end == start ? es : jstr_escaped_before(job, prefix, groups, end);
+    uint8_t* o = job.dst + (uint64_t)es + 3 * r;  // below cap: the verdict compared the whole length
+    o[0] = '"';
+    o[1 + (ee - es)] = '"';
+    if (r + 1 < job.rows) o[2 + (ee - es)] = ',';
+}
+
+constexpr int kEscImage16 = (int)(6 * kC) / 16 + 1;  // copy_out reads past the last byte
+
+__global__ void __launch_bounds__(kJstrThreads) jstr_escape_place_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
+                                                                         const uint32_t* __restrict__ prefix,
+                                                                         const int32_t* __restrict__ ok,
+                                                                         JsonStringResult* __restrict__ res) {
+    __shared__ jstr_u32x4 stage16[kStage16];
+    __shared__ jstr_u32x4 image16[kEscImage16];
+    __shared__ uint32_t lane_before[kJstrThreads + 1];
+    __shared__ uint32_t part[8];
+    const uint32_t t = threadIdx.x;
+    const int ji = jstr_job_of_chunk(jobs, njobs, blockIdx.x);
+    const JsonStringJob job = jobs[ji];
+    const uint32_t c = blockIdx.x - job.first_chunk;
+    if (c >= job.nchunks || !ok[ji]) return;  // uniform
+    const uint32_t at = c * kC, left = job.n - at, len = left < kC ? left : kC;
+    const JstrStage st = jstr_stage(stage16, job.src, job.n, at, len, 0, 0);
+    __syncthreads();
+    const uint32_t mine = jstr_mine(len);
+    uint64_t w0, w1;
+    jstr_lane_words(st, mine, &w0, &w1);
+    const uint32_t size = js::EscapedSize8(w0) + js::EscapedSize8(w1) - (16 - mine);
+    uint32_t total;
+    const uint32_t before = jstr_block_scan(size, part, &total);
+    if (total != prefix[blockIdx.x + 1] - prefix[blockIdx.x]) {  // uniform: the source changed since the size pass
+        if (t == 0) res[ji].err = 4;
+        return;
+    }
+    const uint32_t out0 = prefix[blockIdx.x] - prefix[job.first_chunk];  // escaped bytes of the job before this chunk
+    const uint32_t* image = reinterpret_cast<const uint32_t*>(stage16);
+    uint32_t ioff = (uint32_t)st.pos0;
+    if (total != len) {  // some byte expands: build the escaped image
+        char* img = reinterpret_cast<char*>(image16);
+        if (size == mine) {
+            for (uint32_t k = 0; k < mine; ++k) img[before + k] = (char)st.at(16 * t + k);
+        } else {
+            uint32_t o = before;
+            for (uint32_t k = 0; k < mine; ++k) o += js::EscapeByte(st.at(16 * t + k), img + o);
+        }
+        image = reinterpret_cast<const uint32_t*>(image16);
+        ioff = 0;
+    }
+    if (!job.row_ends) {
+        __syncthreads();
+        jstr_copy_out(image, ioff, job.dst + (job.quote ? 1 : 0) + out0, total);
+        return;
+    }
+    lane_before[t] = before;
+    if (t == 0) lane_before[kJstrThreads] = total;
+    __syncthreads();
+    // the rows of the chunk's first and last byte: the first row whose end lies beyond the byte
+    const uint32_t* __restrict__ ends = job.row_ends;
+    uint32_t ra = 0, rb = job.rows - 1;
+    while (ra < rb) {
+        const uint32_t mid = (ra + rb) / 2;
+        if (ends[mid] > at) rb = mid;
+        else ra = mid + 1;
+    }
+    const uint32_t r0 = ra;
+    rb = job.rows - 1;
+    while (ra < rb) {
+        const uint32_t mid = (ra + rb) / 2;
+        if (ends[mid] > at + len - 1) rb = mid;
+        else ra = mid + 1;
+    }
+    const uint32_t r1 = ra;
+    if (r1 - r0 < 8) {  // few rows: a segment of the image per row
+        for (uint32_t r = r0; r <= r1; ++r) {
+            const uint32_t start = r ? ends[r - 1] : 0u, end = ends[r];
+            const uint32_t lo = (start > at ? start : at) - at, hi = (end < at + len ? end : at + len) - at;
+            if (hi <= lo) continue;
+            uint32_t xlo = lane_before[lo >> 4], xhi = lane_before[hi >> 4];
+            for (uint32_t i = lo & ~15u; i < lo; ++i) xlo += js::EscapedSize(st.at(i));
+            for (uint32_t i = hi & ~15u; i < hi; ++i) xhi += js::EscapedSize(st.at(i));
+            jstr_copy_out(image, ioff + xlo, job.dst + (uint64_t)out0 + xlo + 3ull * r + 1, xhi - xlo);
+        }
+        return;
+    }
+    // many rows: every lane stores its own bytes
+    if (mine == 0) return;
+    const uint32_t i0 = at + 16 * t;
+    ra = r0, rb = r1;
+    while (ra < rb) {
+        const uint32_t mid = (ra + rb) / 2;
+        if (ends[mid] > i0) rb = mid;
+        else ra = mid + 1;
+    }
+    uint32_t r = ra, o = before;
+    for (uint32_t k = 0; k < mine; ++k) {
+        while (r < r1 && ends[r] <= i0 + k) ++r;
+        char b[6];
+        const uint32_t nb = js::EscapeByte(st.at(16 * t + k), b);
+        uint8_t* d = job.dst + (uint64_t)out0 + o + 3ull * r + 1;
+        for (uint32_t q = 0; q < nb; ++q) d[q] = (uint8_t)b[q];
+        o += nb;
+    }
+}
+
+// ---------------------------------------------------------------- unescape
+
+// A chunk's staged text, addressed by job offset; bytes outside the job read as 0.
+struct JstrText {
+    JstrStage st;
+    uint32_t at, n;
+    __device__ __forceinline__ uint8_t byte(int64_t i) const {  // job offset, anywhere
+        return i >= 0 && i < (int64_t)n ? st.at(i - (int64_t)at) : (uint8_t)0;
+    }
+};
+
+// Which bytes of the lane's window are unescaped backslashes, from a bit per
+// backslash. The window is the 32 bytes [at - 16 + 16 t, at + 16 + 16 t): the
+// 16 bytes in front of the lane's own, then its own. `run` is the parity of
+// the backslashes right in front of the window; *mid gets the parity in front
+// of the lane's own bytes.
+__device__ __forceinline__ uint32_t jstr_starters(uint32_t backslashes, uint32_t run, uint32_t* mid) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        if (j == 16) *mid = run;
+        if ((backslashes >> j) & 1) {
+            if (!(run & 1)) m |= 1u << j;
+            run ^= 1;
+        } else {
+            run = 0;
+        }
+    }
+    return m;
+}
+
+// The bytes the lane's own 16 bytes give, with starter mask m of its window:
+// returns their number, lowers *bad to the first offender; writes them at out
+// when it is not null.
+__device__ __forceinline__ uint32_t jstr_emit(const JstrText& x, int64_t i0, uint32_t mine, uint64_t w0, uint64_t w1,
+                                              uint32_t m, uint32_t* bad, char* out) {
+    uint32_t count = 0;
+    for (uint32_t j = 0; j < mine; ++j) {
+        const int64_t i = i0 + j;
+        const uint32_t before = m >> (10 + j);  // bit 6 - k: whether byte i - k starts an escape, k = 1..6
+        if (before & 32u) continue;            // the letter of an escape
+        if (((before & 16u) && x.byte(i - 1) == 'u') || ((before & 8u) && x.byte(i - 2) == 'u') ||
+            ((before & 4u) && x.byte(i - 3) == 'u') || ((before & 2u) && x.byte(i - 4) == 'u'))
+            continue;  // a hex digit of one
+        const uint8_t b = (uint8_t)((j < 8 ? w0 : w1) >> (8 * (j & 7)));  // the lane's own byte j
+        if (b == '\\') {
+            char got[4];
+            uint32_t span;
+            const int k = js::DecodeEscape([&](int d) { return x.byte(i + d); }, (uint64_t)i, (uint64_t)x.n - (uint64_t)i,
+                                           [&] { return (before & 1u) != 0; }, got, &span);
+            if (k < 0) {
+                if ((uint32_t)i < *bad) *bad = (uint32_t)i;
+                continue;
+            }
+            if (out) {
+                for (int q = 0; q < k; ++q) out[count + q] = got[q];
+            }
+            count += (uint32_t)k;
+        } else if (b == '"') {
+            if ((uint32_t)i < *bad) *bad = (uint32_t)i;
+        } else {
+            if (out) out[count] = (char)b;
+            ++count;
+        }
+    }
+    return count;
+}
+
+// A bit per backslash of the lane's window: bits 0..15 the 16 bytes in front
+// of its own (bytes outside the job are none), bits 16..31 its own.
+__device__ __forceinline__ uint32_t jstr_window_backslashes(const JstrText& x, uint32_t own) {
+    const int64_t win = (int64_t)x.at - 16 + 16 * (int64_t)threadIdx.x;
+    uint32_t valid = 0;  // bytes of the front 16 inside the job
+    if (win >= 0 && win < (int64_t)x.n) valid = x.n - (uint32_t)win < 16 ? x.n - (uint32_t)win : 16u;
+    uint64_t f0, f1;
+    jstr_words_at(x.st, (uint32_t)(x.st.pos0 - 16 + 16 * (int)threadIdx.x), valid, &f0, &f1);
+    return jstr_bits_of(f0, f1, '\\') | own << 16;
+}
+
+// The parity in front of each lane's window for carry-in c of the chunk, c
+// the parity in front of byte at - 16. *depends: no byte other than a
+// backslash lies between there and the window, so the answer is c itself
+// (16 backslashes keep a parity); else it is the returned value.
+__device__ __forceinline__ uint32_t jstr_window_parity(uint32_t front, uint64_t* wave_np, uint64_t* wave_odd,
+                                                       bool* depends) {
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    // the 16 bytes in front of the lane's own (a bit per backslash): all backslashes, or how many at their end
+    const bool all = front == 0xFFFFu;
+    const uint32_t trail = (uint32_t)__builtin_clz(~(front << 16));
+    const uint64_t np = __ballot(!all), odd = __ballot(!all && (trail & 1));
+    if (lane == 0) {
+        wave_np[wave] = np;
+        wave_odd[wave] = odd;
+    }
+    __syncthreads();
+    // the nearest lane below this one whose front 16 bytes are not all backslashes: their trailing run decides,
+    // the lanes between (16 backslashes each) only pass the parity on
+    uint64_t mask = np & ((1ull << lane) - 1), odds = odd;
+    int w = (int)wave;
+    while (mask == 0 && w > 0) {
+        --w;
+        mask = wave_np[w];
+        odds = wave_odd[w];
+    }
+    if (mask == 0) {
+        *depends = true;
+        return 0;
+    }
+    *depends = false;
+    const int p = 63 - __builtin_clzll(mask);
+    return (uint32_t)((odds >> p) & 1);
+}
+
+constexpr int kUnImage16 = (int)(kC + 16) / 16 + 1;
+
+__global__ void __launch_bounds__(kJstrThreads) jstr_unescape_scan_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
+                                                                          uint32_t* __restrict__ info) {
+    __shared__ jstr_u32x4 stage16[kStage16];
+    __shared__ uint64_t wave_np[4], wave_odd[4];
+    __shared__ uint32_t acc[6];  // size 0 / 1, bad 0 / 1, the map, whether any lane met a backslash or a quote
+    const uint32_t t = threadIdx.x;
+    const int ji = jstr_job_of_chunk(jobs, njobs, blockIdx.x);
+    const JsonStringJob job = jobs[ji];
+    const uint32_t c = blockIdx.x - job.first_chunk;
+    if (c >= job.nchunks) return;  // uniform
+    const uint32_t at = c * kC, left = job.n - at, len = left < kC ? left : kC;
+    JstrText x;
+    x.st = jstr_stage(stage16, job.src, job.n, at, len, kStageBack, kStageFwd);
+    x.at = at;
+    x.n = job.n;
+    if (t < 6) acc[t] = t == 2 || t == 3 ? kNone : 0u;
+    __syncthreads();
+    const uint32_t mine = jstr_mine(len);
+    uint32_t* out = info + (uint64_t)blockIdx.x * kJsonStringInfoWords;
+    // a chunk with neither backslash nor quote, in the 16 bytes before it either, is copied whatever came before
+    uint64_t w0, w1;
+    jstr_lane_words(x.st, mine, &w0, &w1);
+    uint64_t special = js::EqMask8(w0, '\\') | js::EqMask8(w0, '"') | js::EqMask8(w1, '\\') | js::EqMask8(w1, '"');
+    if (t < 16 && x.byte((int64_t)at - 16 + t) == '\\') special = 1;
+    if (!__syncthreads_or(special != 0)) {
+        if (t == 0) {
+            out[0] = out[1] = len;
+            out[2] = out[3] = kNone;
+            out[4] = 0;  // both carries end at 0
+        }
+        return;
+    }
+    const int64_t i0 = (int64_t)at + 16 * t;
+    const uint32_t bs = jstr_window_backslashes(x, jstr_bits_of(w0, w1, '\\'));
+    bool depends;
+    const uint32_t par = jstr_window_parity(bs & 0xFFFFu, wave_np, wave_odd, &depends);
+    uint32_t size[2], bad[2] = {kNone, kNone}, mid[2];
+    const uint32_t m0 = jstr_starters(bs, depends ? 0u : par, &mid[0]);
+    size[0] = jstr_emit(x, i0, mine, w0, w1, m0, &bad[0], nullptr);
+    if (depends) {
+        const uint32_t m1 = jstr_starters(bs, 1u, &mid[1]);
+        size[1] = jstr_emit(x, i0, mine, w0, w1, m1, &bad[1], nullptr);
+    } else {
+        size[1] = size[0], bad[1] = bad[0], mid[1] = mid[0];
+    }
+    atomicAdd(&acc[0], size[0]);
+    atomicAdd(&acc[1], size[1]);
+    if (bad[0] != kNone) atomicMin(&acc[2], bad[0]);
+    if (bad[1] != kNone) atomicMin(&acc[3], bad[1]);
+    // the parity in front of the last lane's own bytes is the one in front of byte at + kC - 16: the carry
+    if (t == kJstrThreads - 1) acc[4] = (mid[0] & 1) | (mid[1] & 1) << 1;
+    __syncthreads();
+    if (t < 5) out[t] = acc[t];
+}
+
+// maps of {0, 1} to itself in two bits: bit c = the image of c
+__device__ __forceinline__ uint32_t jstr_then(uint32_t f, uint32_t g) {  // first f, then g
+    return ((g >> (f & 1)) & 1) | ((g >> ((f >> 1) & 1)) & 1) << 1;
+}
+constexpr uint32_t kMapIdentity = 2;
+
+__global__ void __launch_bounds__(kJstrThreads) jstr_unescape_carry_kernel(const JsonStringJob* __restrict__ jobs,
+                                                                           uint32_t* __restrict__ info,
+                                                                           uint32_t* __restrict__ prefix,
+                                                                           uint32_t* __restrict__ bad) {
+    __shared__ uint32_t wave_map[kJstrThreads / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const JsonStringJob job = jobs[blockIdx.x];
+    uint32_t carry = 0, lowest = kNone;
+    for (uint32_t base = 0; base < job.nchunks; base += kJstrThreads) {
+        const uint32_t c = base + t;
+        uint32_t* mine = info + (uint64_t)(job.first_chunk + c) * kJsonStringInfoWords;
+        const uint32_t map = c < job.nchunks ? mine[4] : kMapIdentity;
+        uint32_t incl = map;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t y = __shfl_up(incl, off, 64);
+            if (lane >= (uint32_t)off) incl = jstr_then(y, incl);
+        }
+        if (lane == 63) wave_map[wave] = incl;
+        __syncthreads();
+        uint32_t excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = kMapIdentity;
+        uint32_t front = kMapIdentity, tile = kMapIdentity;
+        for (uint32_t k = 0; k < kJstrThreads / 64; ++k) {
+            if (k < wave) front = jstr_then(front, wave_map[k]);
+            tile = jstr_then(tile, wave_map[k]);
+        }
+        const uint32_t cin = (jstr_then(front, excl) >> carry) & 1;
+        if (c < job.nchunks) {
+            prefix[job.first_chunk + c] = mine[cin];
+            mine[5] = cin;
+            const uint32_t b = mine[2 + cin];
+            if (b < lowest) lowest = b;
+        }
+        carry = (tile >> carry) & 1;
+        __syncthreads();  // wave_map is rewritten by the next tile
+    }
+    if (lowest != kNone) atomicMin(&bad[blockIdx.x], lowest);
+}
+
+__global__ void __launch_bounds__(kJstrThreads) jstr_unescape_place_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
+                                                                           const uint32_t* __restrict__ info,
+                                                                           const uint32_t* __restrict__ prefix,
+                                                                           const int32_t* __restrict__ ok,
+                                                                           JsonStringResult* __restrict__ res) {
+    __shared__ jstr_u32x4 stage16[kStage16];
+    __shared__ jstr_u32x4 image16[kUnImage16];
+    __shared__ uint64_t wave_np[4], wave_odd[4];
+    __shared__ uint32_t part[8];
+    const uint32_t t = threadIdx.x;
+    const int ji = jstr_job_of_chunk(jobs, njobs, blockIdx.x);
+    const JsonStringJob job = jobs[ji];
+    const uint32_t c = blockIdx.x - job.first_chunk;
+    if (c >= job.nchunks || !ok[ji]) return;  // uniform
+    const uint32_t at = c * kC, left = job.n - at, len = left < kC ? left : kC;
+    JstrText x;
+    x.st = jstr_stage(stage16, job.src, job.n, at, len, kStageBack, kStageFwd);
+    x.at = at;
+    x.n = job.n;
+    __syncthreads();
+    const uint32_t want = prefix[blockIdx.x + 1] - prefix[blockIdx.x];
+    uint8_t* dst = job.dst + (uint32_t)(prefix[blockIdx.x] - prefix[job.first_chunk]);
+    const uint32_t mine = jstr_mine(len);
+    uint64_t w0, w1;
+    jstr_lane_words(x.st, mine, &w0, &w1);
+    uint64_t special = js::EqMask8(w0, '\\') | js::EqMask8(w0, '"') | js::EqMask8(w1, '\\') | js::EqMask8(w1, '"');
+    if (t < 16 && x.byte((int64_t)at - 16 + t) == '\\') special = 1;
+    if (!__syncthreads_or(special != 0)) {
+        if (want != len) {
+            if (t == 0) res[ji].err = 4;
+            return;
+        }
+        jstr_copy_out(reinterpret_cast<const uint32_t*>(stage16), (uint32_t)x.st.pos0, dst, len);
+        return;
+    }
+    const uint32_t cin = info[(uint64_t)blockIdx.x * kJsonStringInfoWords + 5] & 1;
+    const int64_t i0 = (int64_t)at + 16 * t;
+    const uint32_t bs = jstr_window_backslashes(x, jstr_bits_of(w0, w1, '\\'));
+    bool depends;
+    const uint32_t par = jstr_window_parity(bs & 0xFFFFu, wave_np, wave_odd, &depends);
+    uint32_t mid, bad = kNone;
+    const uint32_t m = jstr_starters(bs, depends ? cin : par, &mid);
+    const uint32_t count = jstr_emit(x, i0, mine, w0, w1, m, &bad, nullptr);
+    uint32_t total;
+    const uint32_t before = jstr_block_scan(count, part, &total);
+    if (total != want || __syncthreads_or(bad != kNone)) {  // uniform: the source changed since the scan
+        if (t == 0) res[ji].err = 4;
+        return;
+    }
+    jstr_emit(x, i0, mine, w0, w1, m, &bad, reinterpret_cast<char*>(image16) + before);
+    __syncthreads();
+    jstr_copy_out(reinterpret_cast<const uint32_t*>(image16), 0, dst, total);
+}
+
+// ------------------------------------------------------------------- UTF-8
+
+__global__ void __launch_bounds__(kJstrThreads) jstr_utf8_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
+                                                                 uint32_t* __restrict__ bad) {
+    __shared__ jstr_u32x4 stage16[kStage16];
+    const uint32_t t = threadIdx.x;
+    const int ji = jstr_job_of_chunk(jobs, njobs, blockIdx.x);
+    const JsonStringJob job = jobs[ji];
+    const uint32_t c = blockIdx.x - job.first_chunk;
+    if (c >= job.nchunks) return;  // uniform
+    const uint32_t at = c * kC, left = job.n - at, len = left < kC ? left : kC;
+    JstrText x;
+    x.st = jstr_stage(stage16, job.src, job.n, at, len, 3, 3);
+    x.at = at;
+    x.n = job.n;
+    __syncthreads();
+    const uint32_t mine = jstr_mine(len);
+    uint64_t w0, w1;
+    jstr_lane_words(x.st, mine, &w0, &w1);
+    if (((w0 | w1) & 0x8080808080808080ull) == 0) return;  // all ASCII
+    const int64_t i0 = (int64_t)at + 16 * t;
+    uint32_t lowest = kNone;
+    for (uint32_t j = 0; j < mine && lowest == kNone; ++j) {
+        const int64_t i = i0 + j;
+        const uint8_t b = x.byte(i);
+        if (b < 0x80) continue;
+        bool fine;
+        if (js::Utf8IsCont(b)) {
+            fine = js::Utf8ContCovered(x.byte(i - 1), x.byte(i - 2), x.byte(i - 3), (uint64_t)i);
+        } else {
+            fine = js::Utf8SequenceLen(b, x.byte(i + 1), x.byte(i + 2), x.byte(i + 3), (uint64_t)job.n - (uint64_t)i) != 0;
+        }
+        if (!fine) lowest = (uint32_t)i;
+    }
+    if (lowest != kNone) atomicMin(&bad[ji], lowest);
+}
+
+__global__ void jstr_utf8_publish_kernel(const uint32_t* __restrict__ bad, int njobs, JsonStringResult* __restrict__ res) {
+    const int ji = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (ji >= njobs) return;
+    JsonStringResult r;
+    r.len = 0;
+    r.first_bad = bad[ji] == kNone ? 0u : bad[ji];
+    r.err = bad[ji] != kNone;
+    res[ji] = r;
+}
+
+// the job table to device memory, the counters to their start values
+int jstr_begin(const JsonStringTables& t, hipStream_t s) {
+    if (!t.jobs || !t.jobs_dev || !t.bad || !t.res) return -1;
+    if (hipMemcpyAsync(t.jobs_dev, t.jobs, (size_t)t.njobs * sizeof(JsonStringJob), hipMemcpyHostToDevice, s) != hipSuccess)
+        return -1;
+    if (hipMemsetAsync(t.bad, 0xFF, (size_t)t.njobs * sizeof(uint32_t), s) != hipSuccess) return -1;
+    if (t.ok && hipMemsetAsync(t.ok, 0, (size_t)t.njobs * sizeof(int32_t), s) != hipSuccess) return -1;
+    // a job without chunks reads two equal entries, the last job the one past the end
+    if (t.prefix && hipMemsetAsync(t.prefix, 0, ((size_t)t.nchunks + 1) * sizeof(uint32_t), s) != hipSuccess) return -1;
+    return 0;
+}
+
+bool jstr_launched() { return hipGetLastError() == hipSuccess; }
+
+}  // namespace
+
+int LaunchJsonStringEscape(const JsonStringTables& t, hipStream_t s) {
+    if (t.njobs <= 0) return 0;
+    if (!t.prefix || !t.ok || (t.ngroups && !t.groups) || jstr_begin(t, s) != 0) return -1;
+    const dim3 threads(kJstrThreads), per_job((t.njobs + 63) / 64);
+    if (t.nchunks) {
+        hipLaunchKernelGGL(jstr_escape_size_kernel, dim3(t.nchunks), threads, 0, s, t.jobs_dev, t.njobs, t.prefix, t.groups);
+        if (!jstr_launched()) return -1;
+    }
+    if (t.nrblocks) {
+        hipLaunchKernelGGL(jstr_rows_check_kernel, dim3(t.nrblocks), threads, 0, s, t.jobs_dev, t.njobs, t.bad);
+        if (!jstr_launched()) return -1;
+    }
+    if (t.nchunks && LaunchPbRunPrefix(t.prefix, (int)t.nchunks + 1, s) != 0) return -1;
+    hipLaunchKernelGGL(jstr_verdict_kernel, per_job, dim3(64), 0, s, t.jobs_dev, t.njobs, t.prefix, t.bad, t.ok, t.res);
+    if (!jstr_launched()) return -1;
+    if (t.nrblocks) {
+        hipLaunchKernelGGL(jstr_rows_punct_kernel, dim3(t.nrblocks), threads, 0, s, t.jobs_dev, t.njobs, t.prefix, t.groups,
+                           t.ok);
+        if (!jstr_launched()) return -1;
+    }
+    if (t.nchunks) {
+        hipLaunchKernelGGL(jstr_escape_place_kernel, dim3(t.nchunks), threads, 0, s, t.jobs_dev, t.njobs, t.prefix, t.ok,
+                           t.res);
+        if (!jstr_launched()) return -1;
+    }
+    return 0;
+}
+
+int LaunchJsonStringUnescape(const JsonStringTables& t, hipStream_t s) {
+    if (t.njobs <= 0 || t.nchunks == 0) return 0;
+    if (!t.prefix || !t.ok || !t.info || jstr_begin(t, s) != 0) return -1;
+    const dim3 threads(kJstrThreads), chunks(t.nchunks);
+    hipLaunchKernelGGL(jstr_unescape_scan_kernel, chunks, threads, 0, s, t.jobs_dev, t.njobs, t.info);
+    if (!jstr_launched()) return -1;
+    hipLaunchKernelGGL(jstr_unescape_carry_kernel, dim3(t.njobs), threads, 0, s, t.jobs_dev, t.info, t.prefix, t.bad);
+    if (!jstr_launched()) return -1;
+    if (LaunchPbRunPrefix(t.prefix, (int)t.nchunks + 1, s) != 0) return -1;
+    hipLaunchKernelGGL(jstr_verdict_kernel, dim3((t.njobs + 63) / 64), dim3(64), 0, s, t.jobs_dev, t.njobs, t.prefix, t.bad,
+                       t.ok, t.res);
+    if (!jstr_launched()) return -1;
+    hipLaunchKernelGGL(jstr_unescape_place_kernel, chunks, threads, 0, s, t.jobs_dev, t.njobs, t.info, t.prefix, t.ok, t.res);
+    return jstr_launched() ? 0 : -1;
+}
+
+int LaunchJsonStringValidate(const JsonStringTables& t, hipStream_t s) {
+    if (t.njobs <= 0 || t.nchunks == 0) return 0;
+    if (jstr_begin(t, s) != 0) return -1;
+    hipLaunchKernelGGL(jstr_utf8_kernel, dim3(t.nchunks), dim3(kJstrThreads), 0, s, t.jobs_dev, t.njobs, t.bad);
+    if (!jstr_launched()) return -1;
+    hipLaunchKernelGGL(jstr_utf8_publish_kernel, dim3((t.njobs + 63) / 64), dim3(64), 0, s, t.bad, t.njobs, t.res);
+    return jstr_launched() ? 0 : -1;
+}
+
+}  // namespace gpu
+}  // namespace mrpc

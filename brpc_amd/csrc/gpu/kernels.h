@@ -707,6 +707,93 @@ struct Base64Job {
 int LaunchBase64Encode(const Base64Job* jobs, int njobs, uint32_t nblocks, hipStream_t s);
 int LaunchBase64Decode(const Base64Job* jobs, int njobs, uint32_t nblocks, JsonNumberResult* res_dev,
                        JsonNumberResult* res_out, hipStream_t s);
+
+// JSON string bodies and UTF-8 in device memory (gpu/json_string_kernels.hip;
+// the rules are base/json_string.h, the code json::EscapeStringBody,
+// UnescapeStringBody and Utf8FirstBad run on the host). A job's n bytes are
+// cut into chunks of kJsonStringChunkBytes, a workgroup of 256 lanes takes one
+// chunk, a lane 16 bytes. src and dst may have any byte alignment. All jobs of
+// a call share the launches, ordered by the stream alone; the job table is
+// copied to device memory first, and nothing is written to a dst before the
+// job's verdict (ok[job], device memory) is known.
+//   escape    size    a workgroup per chunk: the escaped size of the chunk into
+//                     prefix[], and for jobs with rows the escaped bytes in
+//                     front of each 64-byte group of the chunk into groups[]
+//             rows    a lane per row: a row end below its predecessor, or a
+//                     last end other than n, goes into bad[job] (atomicMin)
+//             prefix  LaunchPbRunPrefix over the chunk sizes
+//             verdict a lane per job: len, err 1 / 3, ok[job], the quotes of a
+//                     single string
+//             punct   a lane per row writes its two quotes and its comma: the
+//                     escaped bytes in front of a row end are its group's
+//                     prefix plus at most 63 sizes recomputed from the source
+//             place   a workgroup per chunk escapes it into an LDS image sized
+//                     for the worst case (6 x chunk; there is no direct-store
+//                     path for a chunk that expands) and copies it out with
+//                     16-byte stores; a chunk that needs no escape leaves
+//                     straight from the staged source. With rows, a chunk that
+//                     meets at most 8 rows copies one segment per row, one that
+//                     meets more lets every lane store its own bytes, each
+//                     finding its row in row_ends by binary search
+//   unescape  scan    a workgroup per chunk: whether a backslash starts an
+//                     escape depends on the parity of the backslashes before
+//                     it, so the chunk computes output size, lowest bad offset
+//                     and carry-out for carry-in 0 and 1. The parity span of
+//                     chunk k is [kC - 16, (k + 1)C - 16): with it a chunk
+//                     knows which of the 16 bytes before it start an escape,
+//                     which is all an escape's tail (at most 11 bytes) and the
+//                     low half of a surrogate pair need to know
+//             carry   a workgroup per job composes the chunks' two-state maps,
+//                     picks each chunk's result and lowers bad[job]
+//             prefix, verdict as above
+//             place   a workgroup per chunk, with its carry-in: an escape
+//                     belongs to the chunk that holds its backslash (it reads
+//                     up to 11 bytes beyond its end); bytes are compacted into
+//                     an LDS image by a scan of the lanes' counts and leave
+//                     with 16-byte stores
+//   validate          one launch: a lead byte is judged by the lane that holds
+//                     it (up to 3 bytes beyond), a continuation byte from up to
+//                     3 bytes before; lowest offender by atomicMin; then a
+//                     lane per job publishes
+// res is device-writable pinned host memory; everything else device memory.
+constexpr uint32_t kJsonStringChunkBytes = 4096;
+constexpr uint32_t kJsonStringNone = 0xFFFFFFFFu;
+constexpr uint32_t kJsonStringBlockRows = 256;
+constexpr uint32_t kJsonStringGroupBytes = 64;
+constexpr uint32_t kJsonStringInfoWords = 6;  // per chunk: size, bad for carry-in 0 / 1, the map, the carry-in
+struct JsonStringJob {
+    const uint8_t* src;
+    uint8_t* dst;              // null for validate
+    const uint32_t* row_ends;  // escape: null for a single string
+    uint64_t cap;
+    uint32_t n, rows;
+    uint32_t quote;                 // escape without rows: 1 = surrounding quotes
+    uint32_t first_chunk, nchunks;  // nchunks = ceil(n / kJsonStringChunkBytes), may be 0
+    uint32_t first_rblock;          // ceil(rows / kJsonStringBlockRows) row blocks
+    uint32_t first_group;           // in groups: nchunks * 64 entries (jobs with rows)
+    uint32_t pad;
+};
+struct JsonStringResult {
+    uint64_t len;        // bytes written (with err 3: the size needed)
+    uint32_t first_bad;  // with err 1
+    int32_t err;         // 0, 1, 3, 4 (the source changed between two passes; dst may be partly written)
+};
+struct JsonStringTables {
+    const JsonStringJob* jobs = nullptr;  // pinned host
+    int njobs = 0;
+    JsonStringJob* jobs_dev = nullptr;    // njobs
+    uint32_t nchunks = 0, nrblocks = 0, ngroups = 0;  // of all jobs
+    uint32_t* prefix = nullptr;  // nchunks + 1 (escape, unescape)
+    uint32_t* groups = nullptr;  // ngroups (escape with rows)
+    uint32_t* info = nullptr;    // nchunks * kJsonStringInfoWords (unescape)
+    uint32_t* bad = nullptr;     // njobs
+    int32_t* ok = nullptr;       // njobs (escape, unescape)
+    JsonStringResult* res = nullptr;  // njobs, pinned host
+};
+int LaunchJsonStringEscape(const JsonStringTables& t, hipStream_t s);
+int LaunchJsonStringUnescape(const JsonStringTables& t, hipStream_t s);
+int LaunchJsonStringValidate(const JsonStringTables& t, hipStream_t s);
+
 // scratch must hold JsonIndexScratchBytes(n).
 size_t JsonIndexScratchBytes(uint64_t n);
 int LaunchJsonIndex(const uint8_t* in, uint64_t n, uint32_t* out_pos, uint64_t max_out, uint64_t* count_dev,

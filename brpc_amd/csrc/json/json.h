@@ -233,6 +233,23 @@ bool Parse(const char* data, size_t n, Value* out, std::string* error = nullptr)
 bool ParseWithIndex(const char* data, size_t n, const uint32_t* index, size_t nindex, Value* out,
                     std::string* error = nullptr);
 void EscapeString(const std::string& s, std::string* out);
+// The host twins of the device string entries (gpu/json_string_offload.h);
+// the rules are base/json_string.h for both.
+// What EscapeString writes between its quotes, appended to *out.
+void EscapeStringBody(const char* s, size_t n, std::string* out);
+// "r0","r1",...,"r(rows-1)" appended to *out: row r is bytes[row_ends[r - 1],
+// row_ends[r]) (row_ends[-1] = 0), the pair pb::SplitRows gives a repeated
+// string. False, with nothing appended, when row_ends decreases.
+bool EscapeStringRows(const char* bytes, const uint32_t* row_ends, size_t rows, std::string* out);
+// The body between the quotes -> its bytes, appended to *out. 0: done, and the
+// bytes are what the reader makes of '"' + body + '"'. 1: not decided here
+// (the reader is looser there, or refuses): *first_bad (if given) is the offset
+// of the offending backslash or quote and *out is as it was.
+int UnescapeStringBody(const char* body, size_t n, std::string* out, uint64_t* first_bad = nullptr);
+// The first offset at which no well-formed UTF-8 sequence starts on the walk
+// from 0 (what Python reports as UnicodeDecodeError.start), n when the text
+// is well-formed.
+size_t Utf8FirstBad(const char* s, size_t n);
 // Shortest round-tripping form of d in the reference rapidjson layout ("2.0", "0.1", "1e22").
 void AppendShortestDouble(double d, std::string* out);
 

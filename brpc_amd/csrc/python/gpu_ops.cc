@@ -18,6 +18,7 @@
 #include "policy/device_payload.h"
 #include "gpu/gpu.h"
 #include "gpu/json_offload.h"
+#include "gpu/json_string_offload.h"
 #include "gpu/kernels.h"
 #include "json/json.h"
 
@@ -552,6 +553,84 @@ void bind_gpu_ops(py::module_& g) {
         return out;
     }, py::arg("srcs"), py::arg("ns"), py::arg("dsts"), py::arg("caps"), py::arg("device") = 0);
     g.def("base64_chunk_bytes", [] { return gpu::kBase64ChunkBytes; });
+    // JSON string bodies in device memory, all jobs sharing the launches
+    // (gpu/json_string_offload.h): escape returns [(len, err, first_bad)]
+    // (row_ends[i] 0: one string, else `rows[i]` uint32 in device memory),
+    // unescape [(len, err, first_bad)], validate [(err, first_bad)]. err 0
+    // done, 1 first_bad is set, 2 refused before any launch, 3 cap too small
+    // (len = the size needed).
+    g.def("device_json_escape", [](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& ns,
+                                   const std::vector<uintptr_t>& dsts, const std::vector<uint64_t>& caps,
+                                   const std::vector<uintptr_t>& row_ends, const std::vector<uint64_t>& rows,
+                                   bool quote, int device) {
+        if (srcs.size() != ns.size() || dsts.size() != ns.size() || caps.size() != ns.size() ||
+            (!row_ends.empty() && row_ends.size() != ns.size()) || rows.size() != row_ends.size())
+            throw std::invalid_argument("size mismatch");
+        std::vector<gpu::DeviceJsonEscapeJob> jobs(ns.size());
+        for (size_t i = 0; i < ns.size(); ++i) {
+            jobs[i].src = (const void*)srcs[i];
+            jobs[i].n = ns[i];
+            jobs[i].dst = (void*)dsts[i];
+            jobs[i].cap = caps[i];
+            jobs[i].quote = quote;
+            if (!row_ends.empty()) {
+                jobs[i].row_ends = (const void*)row_ends[i];
+                jobs[i].rows = rows[i];
+            }
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceEscapeJsonStrings(jobs.data(), (int)jobs.size(), device);
+        }
+        check(rc, "device_json_escape");
+        py::list out;
+        for (const gpu::DeviceJsonEscapeJob& j : jobs) out.append(py::make_tuple(j.len, j.err, j.first_bad));
+        return out;
+    }, py::arg("srcs"), py::arg("ns"), py::arg("dsts"), py::arg("caps"),
+       py::arg("row_ends") = std::vector<uintptr_t>(), py::arg("rows") = std::vector<uint64_t>(),
+       py::arg("quote") = true, py::arg("device") = 0);
+    g.def("device_json_unescape", [](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& ns,
+                                     const std::vector<uintptr_t>& dsts, const std::vector<uint64_t>& caps, int device) {
+        if (srcs.size() != ns.size() || dsts.size() != ns.size() || caps.size() != ns.size())
+            throw std::invalid_argument("size mismatch");
+        std::vector<gpu::DeviceJsonUnescapeJob> jobs(ns.size());
+        for (size_t i = 0; i < ns.size(); ++i) {
+            jobs[i].src = (const void*)srcs[i];
+            jobs[i].n = ns[i];
+            jobs[i].dst = (void*)dsts[i];
+            jobs[i].cap = caps[i];
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceUnescapeJsonStrings(jobs.data(), (int)jobs.size(), device);
+        }
+        check(rc, "device_json_unescape");
+        py::list out;
+        for (const gpu::DeviceJsonUnescapeJob& j : jobs) out.append(py::make_tuple(j.len, j.err, j.first_bad));
+        return out;
+    }, py::arg("srcs"), py::arg("ns"), py::arg("dsts"), py::arg("caps"), py::arg("device") = 0);
+    g.def("device_utf8_validate", [](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& ns, int device) {
+        if (srcs.size() != ns.size()) throw std::invalid_argument("size mismatch");
+        std::vector<gpu::DeviceUtf8Job> jobs(ns.size());
+        for (size_t i = 0; i < ns.size(); ++i) {
+            jobs[i].src = (const void*)srcs[i];
+            jobs[i].n = ns[i];
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceValidateUtf8(jobs.data(), (int)jobs.size(), device);
+        }
+        check(rc, "device_utf8_validate");
+        py::list out;
+        for (const gpu::DeviceUtf8Job& j : jobs) out.append(py::make_tuple(j.err, j.first_bad));
+        return out;
+    }, py::arg("srcs"), py::arg("ns"), py::arg("device") = 0);
+    g.def("json_escape_worst_case", [](uint64_t n, uint64_t rows) { return gpu::JsonEscapeWorstCaseBytes(n, rows); },
+          py::arg("n"), py::arg("rows") = 0);
+    g.def("json_string_chunk_bytes", [] { return gpu::kJsonStringChunkBytes; });
     // Field table of a message already in device memory -> (nfields, fields)
     g.def("device_pb_scan", [](uintptr_t buf, uint64_t len, int device) {
         const void* p = (const void*)buf;

@@ -739,7 +739,82 @@ PYBIND11_MODULE(_native, m) {
         if (!base64_decode(p, (size_t)n, &out)) return py::none();
         return py::bytes(out);
     });
-    m.def("narrow_double_bits", [](uint64_t bits) { return decimal_to_double::NarrowDoubleBits(bits); });
+    // The host twins of the device string entries (json/json.h over
+    // base/json_string.h), reading the bytes objects in place. json_escape:
+    // the quoted (quote=True) or bare escaped body, or with row_ends (uint32
+    // little-endian bytes, ascending to len(data)) "r0","r1",... .
+    // json_unescape: (bytes, 0), or (None, first_bad) where the twin leaves
+    // the body to json::Reader. utf8_first_bad: the offset, or len(data).
+    m.def("json_escape", [](py::bytes data, py::object row_ends, bool quote) {
+        char* p = nullptr;
+        Py_ssize_t n = 0;
+        if (PyBytes_AsStringAndSize(data.ptr(), &p, &n) != 0) throw py::error_already_set();
+        std::string out;
+        if (row_ends.is_none()) {
+            if (quote) out.push_back('"');
+            json::EscapeStringBody(p, (size_t)n, &out);
+            if (quote) out.push_back('"');
+            return py::bytes(out);
+        }
+        const std::string ends = py::cast<py::bytes>(row_ends);
+        if (ends.size() % 4 != 0) throw py::value_error("row_ends: a multiple of 4 bytes");
+        std::vector<uint32_t> e(ends.size() / 4);
+        if (!e.empty()) memcpy(e.data(), ends.data(), ends.size());
+        if ((e.empty() ? 0u : e.back()) != (uint64_t)n) throw py::value_error("row_ends does not end at len(data)");
+        if (!json::EscapeStringRows(p, e.data(), e.size(), &out)) throw py::value_error("row_ends decreases");
+        return py::bytes(out);
+    }, py::arg("data"), py::arg("row_ends") = py::none(), py::arg("quote") = true);
+    m.def("json_unescape", [](py::bytes body) -> py::tuple {
+        char* p = nullptr;
+        Py_ssize_t n = 0;
+        if (PyBytes_AsStringAndSize(body.ptr(), &p, &n) != 0) throw py::error_already_set();
+        std::string out;
+        uint64_t first_bad = 0;
+        if (json::UnescapeStringBody(p, (size_t)n, &out, &first_bad) != 0)
+            return py::make_tuple(py::none(), first_bad);
+        return py::make_tuple(py::bytes(out), 0);
+    });
+    m.def("utf8_first_bad", [](py::bytes data) {
+        char* p = nullptr;
+        Py_ssize_t n = 0;
+        if (PyBytes_AsStringAndSize(data.ptr(), &p, &n) != 0) throw py::error_already_set();
+        return json::Utf8FirstBad(p, (size_t)n);
+    });
+    // The twins between raw buffers (pinned host memory of a benchmark), the
+    // GIL released: op 0 escape (quoted; with row_ends the rows form), 1
+    // unescape, 2 validate. Returns the bytes written at dst (validate: the
+    // first bad offset), -1 when the twin refuses or dst is too small.
+    m.def("json_string_twin", [](int op, uintptr_t src, size_t n, uintptr_t dst, size_t cap, uintptr_t row_ends,
+                                 size_t rows) -> int64_t {
+        py::gil_scoped_release nogil;
+        const char* s = reinterpret_cast<const char*>(src);
+        if (op == 2) return (int64_t)json::Utf8FirstBad(s, n);
+        std::string out;
+        if (op == 0 && row_ends) {
+            if (!json::EscapeStringRows(s, reinterpret_cast<const uint32_t*>(row_ends), rows, &out)) return -1;
+        } else if (op == 0) {
+            out.reserve(n + 2);
+            out.push_back('"');
+            json::EscapeStringBody(s, n, &out);
+            out.push_back('"');
+        } else if (json::UnescapeStringBody(s, n, &out) != 0) {
+            return -1;
+        }
+        if (out.size() > cap) return -1;
+        memcpy(reinterpret_cast<char*>(dst), out.data(), out.size());
+        return (int64_t)out.size();
+    }, py::arg("op"), py::arg("src"), py::arg("n"), py::arg("dst"), py::arg("cap"), py::arg("row_ends") = 0,
+       py::arg("rows") = 0);
+    // What json::Reader makes of '"' + body + '"': the bytes, or None where it refuses.
+    m.def("json_reader_string", [](py::bytes body) -> py::object {
+        std::string text = "\"";
+        text += (std::string)body;
+        text += '"';
+        json::Value v;
+        if (!json::Parse(text, &v) || !v.is_string()) return py::none();
+        return py::bytes(v.as_string());
+    });
+    m.def("narrow_double_bits",[](uint64_t bits) { return decimal_to_double::NarrowDoubleBits(bits); });
     m.def("json_max_device_number_chars", [] { return decimal_to_double::kMaxDeviceNumberChars; });
     // json::Parse alone (the DOM is dropped): (ok, error). packed=False parses
     // number arrays element by element, as before packed numbers.

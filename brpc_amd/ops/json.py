@@ -275,3 +275,132 @@ def base64_decode(text):
     if err:
         raise ValueError("base64_decode: refused (code %d)" % err)
     return out[:length]
+
+
+_STRING_ERRORS = {2: "refused (bad arguments)", 3: "longer than the output buffer",
+                  4: "the source changed during the call"}
+
+
+def _flat_bytes(t, name):
+    require_gpu_tensor(t, name)
+    if t.dtype != torch.uint8:
+        raise TypeError("%s must be uint8" % name)
+    t = t.contiguous().view(-1)
+    if t.numel() >= (1 << 32) - 1:
+        raise ValueError("%s must be below 4 GiB" % name)
+    return t
+
+
+def json_escape_string(data, row_ends=None, quote=True, max_bytes=None):
+    """uint8 device tensor of text -> uint8 device tensor of its JSON string:
+    exactly what the host's ``json::EscapeString`` writes (``\\"`` ``\\\\``
+    ``\\n`` ``\\r`` ``\\t`` ``\\b`` ``\\f``, ``\\u00xx`` for the other control
+    bytes, everything else copied), with the surrounding quotes unless
+    ``quote=False``. With ``row_ends`` (an integer device tensor, the bytes in
+    rows 0..r, as ``pb_split_rows`` returns it for a ``repeated string``) the
+    result is ``"r0","r1",...,"rk"``: a whole repeated field in one call. The
+    text never leaves HBM (``gpu::DeviceEscapeJsonStrings``).
+
+    The output is sized for the worst case (six bytes per byte) unless
+    ``max_bytes`` bounds it (ValueError naming the size needed when the text
+    is longer). ValueError names the first row whose end lies below its
+    predecessor's, or the last row when it does not end at ``len(data)``.
+
+    The escaper runs on a pool stream, not on torch's: the caller's current
+    stream is synchronized before the call, and the text is complete when
+    this returns."""
+    t = _flat_bytes(data, "data")
+    dev = t.device
+    n = t.numel()
+    rows, ends = 0, None
+    if row_ends is not None:
+        require_gpu_tensor(row_ends, "row_ends")
+        ends = row_ends.contiguous().view(-1).to(torch.int32)
+        rows = ends.numel()
+        if rows == 0:
+            if n:
+                raise ValueError("json_escape_string: bytes without rows")
+            return torch.empty(0, dtype=torch.uint8, device=dev)
+    worst = native.gpu.json_escape_worst_case(n, rows) if rows else n * 6 + (2 if quote else 0)
+    cap = worst if max_bytes is None else min(int(max_bytes), worst)
+    if cap >= 1 << 32:
+        raise ValueError("json_escape_string: the worst case must be below 4 GiB (pass max_bytes)")
+    out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+    if n == 0 and not rows and not quote:
+        return out[:0]
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (length, err, first_bad), = native.gpu.device_json_escape(
+            [t.data_ptr() if n else 0], [n], [out.data_ptr()], [cap], [ends.data_ptr()] if rows else [],
+            [rows] if rows else [], quote, dev.index or 0)
+    if err == 1:
+        raise ValueError("json_escape_string: row_ends is not ascending to len(data) (row %d)" % first_bad)
+    if err == 3:
+        raise ValueError("json_escape_string: max_bytes=%d is too small (the text takes %d)" % (cap, length))
+    if err:
+        raise ValueError("json_escape_string: " + _STRING_ERRORS.get(err, "code %d" % err))
+    return out[:length] if 2 * length >= out.numel() else out[:length].clone()
+
+
+def json_unescape_string(text):
+    """uint8 device tensor of a JSON string's body (what stands between the
+    quotes) -> uint8 device tensor of its bytes, the inverse of
+    ``json_escape_string(..., quote=False)``. Escapes are resolved in HBM
+    (``gpu::DeviceUnescapeJsonStrings``): the one-letter escapes, ``\\uXXXX``
+    to UTF-8, a surrogate pair to its four bytes. A body the device leaves to
+    the host (an unescaped quote, a bad or cut-off escape, a lone surrogate)
+    is fetched and given to ``native.json_unescape`` and then to the reader
+    itself (``native.json_reader_string``), which is looser about surrogates:
+    its result is returned, or ValueError raised naming the offset the device
+    reported.
+
+    The coder runs on a pool stream, not on torch's: the caller's current
+    stream is synchronized before the call, and the bytes are complete when
+    this returns."""
+    t = _flat_bytes(text, "text")
+    dev = t.device
+    n = t.numel()
+    out = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n == 0:
+        return out
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (length, err, first_bad), = native.gpu.device_json_unescape([t.data_ptr()], [n], [out.data_ptr()], [n],
+                                                                   dev.index or 0)
+    if err == 1:
+        body = bytes(t.cpu().numpy())
+        lax, _ = native.json_unescape(body)
+        if lax is None:
+            lax = native.json_reader_string(body)
+        if lax is None:
+            raise ValueError("json_unescape_string: not the body of a JSON string (offset %d)" % first_bad)
+        if not lax:
+            return out[:0]
+        return torch.frombuffer(bytearray(lax), dtype=torch.uint8).to(dev)
+    if err:
+        raise ValueError("json_unescape_string: " + _STRING_ERRORS.get(err, "code %d" % err))
+    return out[:length]
+
+
+def utf8_validate(data):
+    """uint8 device tensor -> None when it is well-formed UTF-8 (the rule a
+    protobuf ``string`` and a JSON text carry), else the first offset at which
+    no well-formed sequence starts: what ``bytes.decode`` reports as
+    ``UnicodeDecodeError.start``. The bytes never leave HBM
+    (``gpu::DeviceValidateUtf8``).
+
+    The check runs on a pool stream, not on torch's: the caller's current
+    stream is synchronized before the call."""
+    t = _flat_bytes(data, "data")
+    dev = t.device
+    n = t.numel()
+    if n == 0:
+        return None
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (err, first_bad), = native.gpu.device_utf8_validate([t.data_ptr()], [n], dev.index or 0)
+    if err == 1:
+        return first_bad
+    if err:
+        raise ValueError("utf8_validate: " + _STRING_ERRORS.get(err, "code %d" % err))
+    return None
