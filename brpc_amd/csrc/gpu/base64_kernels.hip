@@ -9,20 +9,18 @@
 // alignment: global loads and the stores of whole 16-byte units are aligned,
 // the shift happens on chip.
 //
-//  encode  the chunk's source span is staged in LDS with 16-byte loads from
-//          the aligned-down address (the loads stay inside 16-byte units that
-//          hold a source byte). A lane reads its 12 bytes as four dwords
-//          (stride 3 dwords: conflict-free) and funnel-shifts them, forms its
-//          16 symbols in registers and, when dst is 16-byte aligned and the
-//          chunk whole, stores them at once. Otherwise the symbols go through
-//          an LDS image and leave as bytes up to the first 16-byte boundary,
-//          16-byte stores, bytes again (copy_out). Only the job's last lane
-//          that holds data writes '='.
+//  encode  the chunk's source span is staged in LDS (wg::stage16). A lane
+//          reads its 12 bytes as four dwords (stride 3 dwords: conflict-free)
+//          and funnel-shifts them, forms its 16 symbols in registers and,
+//          when dst is 16-byte aligned and the chunk whole, stores them at
+//          once. Otherwise the symbols go through an LDS image and leave
+//          through wg::copy_out_shifted. Only the job's last lane that holds
+//          data writes '='.
 //  decode  a lane loads its 16 symbols (one aligned 16-byte load, or the two
 //          that cover them), converts them and puts its 12 bytes into the LDS
-//          image, which leaves through copy_out. Every workgroup reads the
-//          job's last two bytes to learn the padding p, so the body is
-//          [0, n - p) for all of them; a body byte outside the alphabet
+//          image, which leaves through wg::copy_out_shifted. Every workgroup
+//          reads the job's last two bytes to learn the padding p, so the body
+//          is [0, n - p) for all of them; a body byte outside the alphabet
 //          records its offset with atomicMin on the job's result in device
 //          memory, a body length the padding rule forbids records n there.
 //          The first workgroup of a job writes the decoded length.
@@ -32,6 +30,7 @@
 
 #include "base/base64.h"
 #include "gpu/kernels.h"
+#include "gpu/workgroup.h"
 
 namespace mrpc {
 namespace gpu {
@@ -39,71 +38,20 @@ namespace gpu {
 namespace {
 
 namespace b64 = ::mrpc::base64;
-typedef uint32_t b64_u32x4 __attribute__((ext_vector_type(4)));
+using wg::u32x4;
 constexpr int kB64Threads = 256;
 constexpr uint32_t kLaneBytes = 12, kLaneSymbols = 16;
 static_assert(kB64Threads * kLaneBytes == kBase64ChunkBytes, "a lane per 12 bytes");
 static_assert(kB64Threads * kLaneSymbols == kBase64ChunkSymbols, "a lane per 16 symbols");
 
-// the job that owns this block: the last whose first_block is not past it
-__device__ __forceinline__ int b64_job_of(const Base64Job* __restrict__ jobs, int njobs, uint32_t block) {
-    int ja = 0, jb = njobs - 1;
-    while (ja < jb) {
-        const int mid = (ja + jb + 1) / 2;
-        if (jobs[mid].first_block <= block) ja = mid;
-        else jb = mid - 1;
-    }
-    return ja;
-}
-
-// dwords lo, hi as they follow each other in memory -> the dword that starts
-// `sh` bits (0, 8, 16, 24) into lo
-__device__ __forceinline__ uint32_t b64_shift(uint32_t lo, uint32_t hi, uint32_t sh) {
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
-}
-
-// image[0, total) (LDS, readable one dword past total rounded up to 16) ->
-// dst at any alignment: bytes up to the first 16-byte boundary, 16-byte
-// stores, bytes for the rest. The caller has synchronized the image.
-__device__ __forceinline__ void b64_copy_out(const uint32_t* image, uint8_t* __restrict__ dst, uint32_t total) {
-    const uint32_t t = threadIdx.x;
-    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(image);
-    uint32_t head = (16u - (uint32_t)((uintptr_t)dst & 15)) & 15;
-    if (head > total) head = total;
-    if (t < head) dst[t] = bytes[t];
-    const uint32_t nv = (total - head) / 16;
-    const uint32_t sh = (head & 3) * 8;  // uniform: where a unit starts inside an LDS dword
-    b64_u32x4* body = reinterpret_cast<b64_u32x4*>(dst + head);
-    for (uint32_t v = t; v < nv; v += kB64Threads) {
-        const uint32_t w = (head + 16 * v) >> 2;
-        b64_u32x4 x;
-        if (head == 0) {  // dst is 16-byte aligned: one 16-byte LDS read
-            x = reinterpret_cast<const b64_u32x4*>(image)[v];
-        } else if (sh == 0) {
-            x.x = image[w];
-            x.y = image[w + 1];
-            x.z = image[w + 2];
-            x.w = image[w + 3];
-        } else {
-            const uint32_t d0 = image[w], d1 = image[w + 1], d2 = image[w + 2], d3 = image[w + 3], d4 = image[w + 4];
-            x.x = b64_shift(d0, d1, sh);
-            x.y = b64_shift(d1, d2, sh);
-            x.z = b64_shift(d2, d3, sh);
-            x.w = b64_shift(d3, d4, sh);
-        }
-        body[v] = x;
-    }
-    for (uint32_t j = head + 16 * nv + t; j < total; j += kB64Threads) dst[j] = bytes[j];
-}
-
 constexpr int kEncStage16 = (int)(kBase64ChunkBytes + 15 + 15) / 16 + 1;  // the span at any phase, and a dword to spare
-constexpr int kEncImage16 = (int)kBase64ChunkSymbols / 16 + 1;            // copy_out reads one dword past
+constexpr int kEncImage16 = (int)kBase64ChunkSymbols / 16 + 1;            // copy_out_shifted reads one dword past
 
 __global__ void __launch_bounds__(kB64Threads) base64_encode_kernel(const Base64Job* __restrict__ jobs, int njobs) {
-    __shared__ b64_u32x4 stage16[kEncStage16];
-    __shared__ b64_u32x4 image16[kEncImage16];
+    __shared__ u32x4 staged[kEncStage16];
+    __shared__ u32x4 image16[kEncImage16];
     const uint32_t t = threadIdx.x;
-    const int ji = b64_job_of(jobs, njobs, blockIdx.x);
+    const int ji = wg::job_of<&Base64Job::first_block>(jobs, njobs, blockIdx.x);
     const Base64Job job = jobs[ji];
     const uint64_t at = (uint64_t)(blockIdx.x - job.first_block) * kBase64ChunkBytes;
     if (at >= job.n) return;  // uniform: a block the host did not mean for this job
@@ -111,24 +59,20 @@ __global__ void __launch_bounds__(kB64Threads) base64_encode_kernel(const Base64
     const uint32_t len = left < kBase64ChunkBytes ? left : kBase64ChunkBytes;  // data bytes of this chunk
     const uint8_t* src = job.src + at;
     uint8_t* dst = job.dst + (at / 3) * 4;
-    // stage [src - a, src + len) rounded up to 16: at most 193 units
-    const uint32_t a = (uint32_t)((uintptr_t)src & 15);
-    const b64_u32x4* from = reinterpret_cast<const b64_u32x4*>(src - a);
-    const uint32_t nstage = (a + len + 15) / 16;
-    if (t < nstage) stage16[t] = from[t];
+    const uint32_t a = wg::stage16<kB64Threads, 1>(src, len, staged);  // at most 193 units
     __syncthreads();
-    const uint32_t* stage = reinterpret_cast<const uint32_t*>(stage16);
+    const uint32_t* stage = reinterpret_cast<const uint32_t*>(staged);
     const uint32_t mine = 12 * t < len ? (len - 12 * t < 12 ? len - 12 * t : 12u) : 0u;  // data bytes of this lane
     const uint32_t w = (a + 12 * t) >> 2, sh = (a & 3) * 8;
     const uint32_t d0 = stage[w], d1 = stage[w + 1], d2 = stage[w + 2], d3 = stage[w + 3];
-    uint32_t b0 = b64_shift(d0, d1, sh), b1 = b64_shift(d1, d2, sh), b2 = b64_shift(d2, d3, sh);
+    uint32_t b0 = wg::funnel(d0, d1, sh), b1 = wg::funnel(d1, d2, sh), b2 = wg::funnel(d2, d3, sh);
     if (mine < 12) {  // what lies past the data counts as zero bits
         const uint64_t keep01 = mine >= 8 ? ~0ull : ((1ull << (8 * mine)) - 1);
         b0 &= (uint32_t)keep01;
         b1 &= (uint32_t)(keep01 >> 32);
         b2 &= mine > 8 ? (1u << (8 * (mine - 8))) - 1 : 0u;
     }
-    b64_u32x4 sym;
+    u32x4 sym;
     sym.x = b64::Encode3LE(b0);
     sym.y = b64::Encode3LE((b0 >> 24) | (b1 << 8));
     sym.z = b64::Encode3LE((b1 >> 16) | (b2 << 16));
@@ -144,21 +88,21 @@ __global__ void __launch_bounds__(kB64Threads) base64_encode_kernel(const Base64
     }
     const uint32_t total = (len + 2) / 3 * 4;  // symbols of this chunk
     if (((uintptr_t)dst & 15) == 0 && len == kBase64ChunkBytes) {
-        reinterpret_cast<b64_u32x4*>(dst)[t] = sym;
+        reinterpret_cast<u32x4*>(dst)[t] = sym;
         return;
     }
     image16[t] = sym;
     __syncthreads();
-    b64_copy_out(reinterpret_cast<const uint32_t*>(image16), dst, total);
+    wg::copy_out_shifted<kB64Threads>(reinterpret_cast<const uint32_t*>(image16), 0, dst, total);
 }
 
-constexpr int kDecImage16 = (int)kBase64ChunkBytes / 16 + 1;  // copy_out reads one dword past
+constexpr int kDecImage16 = (int)kBase64ChunkBytes / 16 + 1;  // copy_out_shifted reads one dword past
 
 __global__ void __launch_bounds__(kB64Threads) base64_decode_kernel(const Base64Job* __restrict__ jobs, int njobs,
                                                                     JsonNumberResult* __restrict__ res) {
-    __shared__ b64_u32x4 image16[kDecImage16];
+    __shared__ u32x4 image16[kDecImage16];
     const uint32_t t = threadIdx.x;
-    const int ji = b64_job_of(jobs, njobs, blockIdx.x);
+    const int ji = wg::job_of<&Base64Job::first_block>(jobs, njobs, blockIdx.x);
     const Base64Job job = jobs[ji];
     const uint32_t n = job.n;
     const uint64_t at = (uint64_t)(blockIdx.x - job.first_block) * kBase64ChunkSymbols;
@@ -180,13 +124,13 @@ __global__ void __launch_bounds__(kB64Threads) base64_decode_kernel(const Base64
     if (text_mine == 16) {
         const uint8_t* mp = src + 16 * t;
         const uint32_t a = (uint32_t)((uintptr_t)mp & 15);  // uniform
-        const b64_u32x4* lo = reinterpret_cast<const b64_u32x4*>(mp - a);
-        const b64_u32x4 x = lo[0];
+        const u32x4* lo = reinterpret_cast<const u32x4*>(mp - a);
+        const u32x4 x = lo[0];
         if (a == 0) {
             s[0] = x.x, s[1] = x.y, s[2] = x.z, s[3] = x.w;
         } else {
             // the second unit starts before this lane's last symbol: it holds text
-            const b64_u32x4 y = lo[1];
+            const u32x4 y = lo[1];
             const uint32_t d[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
             const uint32_t w = a >> 2, sh = (a & 3) * 8;
 #pragma unroll
@@ -199,7 +143,7 @@ __global__ void __launch_bounds__(kB64Threads) base64_decode_kernel(const Base64
                         hi32 = d[q + k + 1 < 8 ? q + k + 1 : 7];
                     }
                 }
-                s[k] = b64_shift(lo32, hi32, sh);
+                s[k] = wg::funnel(lo32, hi32, sh);
             }
         }
     } else if (text_mine != 0) {  // the text's last lane: byte by byte
@@ -245,7 +189,7 @@ __global__ void __launch_bounds__(kB64Threads) base64_decode_kernel(const Base64
     __syncthreads();
     const uint32_t chunk_syms = body < kBase64ChunkSymbols ? body : kBase64ChunkSymbols;
     const uint32_t total = chunk_syms / 4 * 3 + (chunk_syms % 4) * 3 / 4;
-    b64_copy_out(image, job.dst + (at / 4) * 3, total);
+    wg::copy_out_shifted<kB64Threads>(image, 0, job.dst + (at / 4) * 3, total);
 }
 
 }  // namespace

@@ -35,6 +35,7 @@
 #include "base/number_text.h"
 #include "base/shortest_double.h"
 #include "gpu/kernels.h"
+#include "gpu/workgroup.h"
 
 namespace mrpc {
 namespace gpu {
@@ -165,16 +166,12 @@ __device__ __forceinline__ uint64_t position_mask(uint64_t q, uint64_t structura
     return (structural & ~inside) | q;
 }
 
-// Block-wide scans: 64-lane shuffle scans, then the 4 wave totals through
-// LDS. `wtot` is a kJWaves-entry LDS array owned by the caller.
+// Block-wide scan of transfer tables, the shape of wg::block_excl_scan with
+// xf_compose in place of the sum: one barrier, between writing and reading
+// `wtot`, a kJWaves-entry LDS array owned by the caller.
 __device__ __forceinline__ uint32_t block_xf_scan(uint32_t v, uint32_t* wtot, uint32_t* total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(inc, off, 64);
-        if (lane >= off) inc = xf_compose(y, inc);
-    }
+    const uint32_t inc = wg::wave_incl_scan(v, [](uint32_t a, uint32_t b) { return xf_compose(a, b); });
     if (lane == 63) wtot[wave] = inc;
     __syncthreads();
     uint32_t before = kXfIdentity, all = kXfIdentity;
@@ -183,30 +180,10 @@ __device__ __forceinline__ uint32_t block_xf_scan(uint32_t v, uint32_t* wtot, ui
         if (w < wave) before = xf_compose(before, wtot[w]);
         all = xf_compose(all, wtot[w]);
     }
-    uint32_t ex = __shfl_up(inc, 1, 64);
+    uint32_t ex = wg::wave_prev(inc);
     if (lane == 0) ex = kXfIdentity;
     *total = all;
     return xf_compose(before, ex);
-}
-
-__device__ __forceinline__ uint64_t block_sum_scan(uint64_t v, uint64_t* wtot, uint64_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t y = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += y;
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kJWaves; ++w) {
-        if (w < wave) before += wtot[w];
-        all += wtot[w];
-    }
-    *total = all;
-    return before + inc - v;
 }
 
 // Scratch layout (lanes = tiles * 256):
@@ -267,7 +244,7 @@ __global__ void __launch_bounds__(kJThreads) json_tile_kernel(const uint8_t* __r
         packed |= (uint64_t)__popcll(pos) << (16 * k);
     }
     uint64_t tile_cnt;
-    const uint64_t off = block_sum_scan(packed, sum_wtot, &tile_cnt);  // no u16 field exceeds 16384
+    const uint64_t off = wg::block_excl_scan<kJThreads>(packed, sum_wtot, &tile_cnt);  // no u16 field exceeds 16384
     sc.q0[lane] = q0;
     sc.q1[lane] = q1;
     sc.st[lane] = m.structural;
@@ -485,13 +462,7 @@ __global__ void __launch_bounds__(256) json_number_array_kernel(const JsonNumber
                                                                 JsonNumberResult* __restrict__ res) {
     __shared__ char span[kIntSpan];
     __shared__ uint32_t lo_s, hi_s;
-    // the job that owns this block: the last whose first_block is not past it
-    int ja = 0, jb = njobs - 1;
-    while (ja < jb) {
-        const int mid = (ja + jb + 1) / 2;
-        if (jobs[mid].first_block <= blockIdx.x) ja = mid;
-        else jb = mid - 1;
-    }
+    const int ja = wg::job_of<&JsonNumberJob::first_block>(jobs, njobs, blockIdx.x);
     const JsonNumberJob job = jobs[ja];
     const char* __restrict__ text = job.text;
     const uint32_t* __restrict__ seps = job.seps;
@@ -561,7 +532,7 @@ __global__ void __launch_bounds__(256) json_number_array_kernel(const JsonNumber
 // passes, a lane per 16 bytes of it. The scanner and every rule of the shape
 // are base/number_text.h, the code json::ParseNumberText runs.
 namespace nt = ::mrpc::number_text;
-typedef uint32_t jt_u32x4 __attribute__((ext_vector_type(4)));
+using wg::u32x4;
 static_assert(sizeof(nt::TextState) == kJsonTextStateBytes, "kernels.h sizes the state table");
 constexpr uint32_t kJtChunk = kJsonTextChunkBytes;
 constexpr int kJtThreads = 256;
@@ -589,22 +560,11 @@ struct JtWindowAt {
 };
 static_assert(kJtWin % 16 == 0 && kJtWin / 16 <= 2 * kJtThreads, "the window is read in 8-byte words and staged in at most two 16-byte loads a lane");
 
-// the job that owns chunk ci: the last whose first_chunk is not past it
-__device__ __forceinline__ int jt_job_of(const JsonTextJob* __restrict__ jobs, int njobs, uint32_t ci) {
-    int ja = 0, jb = njobs - 1;
-    while (ja < jb) {
-        const int mid = (ja + jb + 1) / 2;
-        if (jobs[mid].first_chunk <= ci) ja = mid;
-        else jb = mid - 1;
-    }
-    return ja;
-}
-
 // commas in the low half, ']' bytes in the high half (a chunk has at most 4096 of each)
 __device__ __forceinline__ uint32_t jt_tally(char c) { return c == ',' ? 1u : c == ']' ? 0x10000u : 0u; }
 
 // how many of the 16 bytes equal the byte broadcast in pat
-__device__ __forceinline__ uint32_t jt_count_eq(jt_u32x4 q, uint32_t pat) {
+__device__ __forceinline__ uint32_t jt_count_eq(u32x4 q, uint32_t pat) {
     return (uint32_t)(__builtin_popcount(bytes_eq(q.x, pat)) + __builtin_popcount(bytes_eq(q.y, pat)) +
                       __builtin_popcount(bytes_eq(q.z, pat)) + __builtin_popcount(bytes_eq(q.w, pat)));
 }
@@ -622,7 +582,7 @@ __global__ void __launch_bounds__(kJtThreads) json_text_count_kernel(const JsonT
     // kernels find it in device memory (a field read where it is used would
     // cross the bus every time)
     if (t == 0) {
-        const int ja = jt_job_of(jobs, njobs, ci);
+        const int ja = wg::job_of<&JsonTextJob::first_chunk>(jobs, njobs, ci);
         job_s = jobs[ja];
         if (ci == 0) prefix[nchunks] = prefix[2 * nchunks + 1] = 0;  // become the totals under the scan
         if (ci == job_s.first_chunk) {
@@ -638,7 +598,7 @@ __global__ void __launch_bounds__(kJtThreads) json_text_count_kernel(const JsonT
     if (s64 < job.n) {
         const uint32_t s = (uint32_t)s64, len = job.n - s < kJtChunk ? job.n - s : kJtChunk;
         if (len == kJtChunk && ((uintptr_t)(job.text + s) & 15) == 0) {  // a whole chunk, aligned: one load a lane
-            const jt_u32x4 q = reinterpret_cast<const jt_u32x4*>(job.text + s)[t];
+            const u32x4 q = reinterpret_cast<const u32x4*>(job.text + s)[t];
             v = jt_count_eq(q, 0x2C2C2C2Cu) | jt_count_eq(q, 0x5D5D5D5Du) << 16;
         } else {
             char c[kJtPer];
@@ -651,14 +611,8 @@ __global__ void __launch_bounds__(kJtThreads) json_text_count_kernel(const JsonT
             for (uint32_t k = 0; k < kJtPer; ++k) v += jt_tally(c[k]);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((t & 63) == 0) wave_tot[t >> 6] = v;
-    __syncthreads();
+    const uint32_t total = wg::block_sum<kJtThreads>(v, wave_tot);
     if (t == 0) {
-        uint32_t total = 0;
-#pragma unroll
-        for (int w = 0; w < kJtThreads / 64; ++w) total += wave_tot[w];
         prefix[ci] = total & 0xFFFFu;
         prefix[nchunks + 1 + ci] = total >> 16;
     }
@@ -674,9 +628,9 @@ __global__ void __launch_bounds__(kJtThreads) json_text_parse_kernel(const JsonT
     __shared__ uint32_t wave_tot[kJtThreads / 64];
     __shared__ JsonTextJob job_s;
     __shared__ int ja_s;
-    const uint32_t ci = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint32_t ci = blockIdx.x, t = threadIdx.x;
     if (t == 0) {
-        ja_s = jt_job_of(jobs, njobs, ci);
+        ja_s = wg::job_of<&JsonTextJob::first_chunk>(jobs, njobs, ci);
         job_s = jobs[ja_s];
     }
     __syncthreads();
@@ -699,10 +653,10 @@ __global__ void __launch_bounds__(kJtThreads) json_text_parse_kernel(const JsonT
     const uint32_t wlo = s >= kJtPre ? s - kJtPre : 0, whi = n - e < kJtPost ? n : e + kJtPost;
     if (whi - wlo == kJtWin && ((uintptr_t)(text + wlo) & 15) == 0) {  // a whole window, aligned: 16 bytes a load
         constexpr uint32_t kWin16 = kJtWin / 16;
-        const jt_u32x4* from = reinterpret_cast<const jt_u32x4*>(text + wlo);
-        jt_u32x4* to = reinterpret_cast<jt_u32x4*>(win);
-        const jt_u32x4 a = from[t];
-        jt_u32x4 b = {0, 0, 0, 0};
+        const u32x4* from = reinterpret_cast<const u32x4*>(text + wlo);
+        u32x4* to = reinterpret_cast<u32x4*>(win);
+        const u32x4 a = from[t];
+        u32x4 b = {0, 0, 0, 0};
         if (t + kJtThreads < kWin16) b = from[t + kJtThreads];
         to[t] = a;
         if (t + kJtThreads < kWin16) to[t + kJtThreads] = b;
@@ -726,7 +680,7 @@ __global__ void __launch_bounds__(kJtThreads) json_text_parse_kernel(const JsonT
     // compares of the structural index), bytes past the chunk masked off.
     const uint32_t lo = s - wlo + t * kJtPer;  // index into win
     const uint32_t mine = s + t * kJtPer < e ? (e - (s + t * kJtPer) < kJtPer ? e - (s + t * kJtPer) : kJtPer) : 0;
-    const jt_u32x4 own = *reinterpret_cast<const jt_u32x4*>(win + lo);
+    const u32x4 own = *reinterpret_cast<const u32x4*>(win + lo);
     const uint32_t keep = mine >= kJtPer ? 0xFFFFu : (1u << mine) - 1u;
     uint32_t comma_bits = (gather4(bytes_eq(own.x, 0x2C2C2C2Cu)) | gather4(bytes_eq(own.y, 0x2C2C2C2Cu)) << 4 |
                            gather4(bytes_eq(own.z, 0x2C2C2C2Cu)) << 8 | gather4(bytes_eq(own.w, 0x2C2C2C2Cu)) << 12) & keep;
@@ -734,21 +688,8 @@ __global__ void __launch_bounds__(kJtThreads) json_text_parse_kernel(const JsonT
                            gather4(bytes_eq(own.z, 0x5D5D5D5Du)) << 8 | gather4(bytes_eq(own.w, 0x5D5D5D5Du)) << 12) & keep;
     const uint32_t own_commas = comma_bits;
     const uint32_t tally = (uint32_t)__builtin_popcount(comma_bits) | (uint32_t)__builtin_popcount(close_bits) << 16;
-    uint32_t incl = tally;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(incl, off, 64);
-        if (lane >= (uint32_t)off) incl += y;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    uint32_t before = incl - tally, total = 0;
-#pragma unroll
-    for (int w = 0; w < kJtThreads / 64; ++w) {
-        const uint32_t x = wave_tot[w];
-        if ((uint32_t)w < wave) before += x;
-        total += x;
-    }
+    uint32_t total;
+    const uint32_t before = wg::block_excl_scan<kJtThreads>(tally, wave_tot, &total);
     const uint32_t ncommas = total & 0xFFFFu;  // of this chunk
     {
         uint32_t c_at = before & 0xFFFFu;
@@ -847,7 +788,6 @@ __global__ void __launch_bounds__(256) json_text_publish_kernel(const JsonTextJo
 // Writer (src/json2pb/pb_to_json.cpp); here one lane formats one element
 // with base/shortest_double.h, the same code the host printer runs.
 namespace sd = ::mrpc::shortest_double;
-typedef uint32_t jf_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kJfThreads = (int)kJsonFloatChunkElems;  // a lane per element
 constexpr int kJfWaves = kJfThreads / 64;
 constexpr uint32_t kJfElemMax = (uint32_t)sd::kMaxJsonDoubleChars + 1;                // with its comma
@@ -882,16 +822,8 @@ __global__ void __launch_bounds__(kJfThreads) json_float_size_kernel(const JsonF
         n = jf_elem_len(d, c, t, count);
         digits[(uint64_t)ci * kJsonFloatChunkElems + t] = d;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
-    if ((t & 63) == 0) wave_tot[t >> 6] = n;
-    __syncthreads();
-    if (t == 0) {
-        uint32_t total = 0;
-#pragma unroll
-        for (int w = 0; w < kJfWaves; ++w) total += wave_tot[w];
-        sizes[ci] = total;
-    }
+    const uint32_t total = wg::block_sum<kJfThreads>(n, wave_tot);
+    if (t == 0) sizes[ci] = total;
 }
 
 __global__ void __launch_bounds__(kJfThreads) json_float_place_kernel(const JsonFloatJob* __restrict__ jobs,
@@ -899,10 +831,10 @@ __global__ void __launch_bounds__(kJfThreads) json_float_place_kernel(const Json
                                                                       const uint32_t* __restrict__ prefix,
                                                                       const sd::Decimal* __restrict__ digits,
                                                                       JsonFloatResult* __restrict__ res) {
-    __shared__ jf_u32x4 image16[kJfImage16];
+    __shared__ u32x4 image16[kJfImage16];
     __shared__ uint32_t wave_tot[kJfWaves];
     uint8_t* image = reinterpret_cast<uint8_t*>(image16);
-    const uint32_t ci = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint32_t ci = blockIdx.x, t = threadIdx.x;
     const JsonFloatChunk c = chunks[ci];
     const JsonFloatJob job = jobs[c.job];
     // the host refuses arrays whose worst case passes 2^32 - 1, so the
@@ -926,21 +858,8 @@ __global__ void __launch_bounds__(kJfThreads) json_float_place_kernel(const Json
         len = jf_elem_len(d, c, t, count);
         if (len > kJfElemMax) len = 0;  // whatever the slot holds, never past the image
     }
-    uint32_t incl = len;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(incl, off, 64);
-        if (lane >= (uint32_t)off) incl += y;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    uint32_t pos = incl - len, total = 0;
-#pragma unroll
-    for (int w = 0; w < kJfWaves; ++w) {
-        const uint32_t x = wave_tot[w];
-        if ((uint32_t)w < wave) pos += x;
-        total += x;
-    }
+    uint32_t total;
+    const uint32_t pos = wg::block_excl_scan<kJfThreads>(len, wave_tot, &total);
     if (len) {
         char* o = reinterpret_cast<char*>(image + sh + pos);
         const uint32_t body = (uint32_t)sd::FormatJsonDecimal(d, o);
@@ -951,16 +870,7 @@ __global__ void __launch_bounds__(kJfThreads) json_float_place_kernel(const Json
         if (t == 0) res[c.job].err = 4;
         return;
     }
-    // image[sh, sh + total) -> dst, dst = sh (mod 16): 16-byte LDS reads and
-    // 16-byte stores around an unaligned head and tail
-    uint32_t head = (16 - sh) & 15;
-    if (head > total) head = total;
-    if (t < head) dst[t] = image[sh + t];
-    const uint32_t nv = (total - head) / 16;
-    const jf_u32x4* from = reinterpret_cast<const jf_u32x4*>(image + sh + head);
-    jf_u32x4* body16 = reinterpret_cast<jf_u32x4*>(dst + head);
-    for (uint32_t w = t; w < nv; w += kJfThreads) body16[w] = from[w];
-    for (uint32_t j = head + 16 * nv + t; j < total; j += kJfThreads) dst[j] = image[sh + j];
+    wg::copy_out_phased<kJfThreads>(image, sh, dst, total);  // the image sits at dst's phase
 }
 
 }  // namespace

@@ -4,17 +4,17 @@
 // are base/json_string.h, the code the host twins in json/json.cc run.
 //
 // A workgroup of 256 lanes takes one chunk of kJsonStringChunkBytes of one
-// job, a lane 16 bytes. Global loads are aligned 16-byte loads from the
-// aligned-down address (they stay inside 16-byte units that hold a byte of the
-// job) into an LDS stage; what leaves goes through jstr_copy_out: bytes up to
-// the first 16-byte boundary of dst, 16-byte stores, bytes for the rest. The
-// shift between the two alignments happens on chip.
+// job, a lane 16 bytes. The chunk's span of the source is staged in LDS with
+// aligned 16-byte loads (jstr_stage, over wg::stage16); what leaves goes
+// through wg::copy_out_shifted, so the shift between the two alignments
+// happens on chip.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "base/json_string.h"
 #include "gpu/kernels.h"
+#include "gpu/workgroup.h"
 
 namespace mrpc {
 namespace gpu {
@@ -22,36 +22,12 @@ namespace gpu {
 namespace {
 
 namespace js = ::mrpc::json_string;
-typedef uint32_t jstr_u32x4 __attribute__((ext_vector_type(4)));
+using wg::u32x4;
 constexpr int kJstrThreads = 256;
 constexpr uint32_t kC = kJsonStringChunkBytes;
 constexpr uint32_t kNone = kJsonStringNone;
 static_assert(kJstrThreads * 16 == kC, "a lane per 16 bytes");
 static_assert(kC / kJsonStringGroupBytes == 64, "64 groups per chunk");
-
-// the job that owns this chunk: the last whose first_chunk is not past it
-__device__ __forceinline__ int jstr_job_of_chunk(const JsonStringJob* __restrict__ jobs, int njobs, uint32_t chunk) {
-    int ja = 0, jb = njobs - 1;
-    while (ja < jb) {
-        const int mid = (ja + jb + 1) / 2;
-        if (jobs[mid].first_chunk <= chunk) ja = mid;
-        else jb = mid - 1;
-    }
-    return ja;
-}
-__device__ __forceinline__ int jstr_job_of_rblock(const JsonStringJob* __restrict__ jobs, int njobs, uint32_t rb) {
-    int ja = 0, jb = njobs - 1;
-    while (ja < jb) {
-        const int mid = (ja + jb + 1) / 2;
-        if (jobs[mid].first_rblock <= rb) ja = mid;
-        else jb = mid - 1;
-    }
-    return ja;
-}
-
-__device__ __forceinline__ uint32_t jstr_shift(uint32_t lo, uint32_t hi, uint32_t sh) {
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
-}
 
 // The staged span of a chunk: job bytes [at - back, at + len + fwd) cut to
 // [0, n), loaded as whole 16-byte units. stage[pos0 + (i - at)] is job byte i.
@@ -63,52 +39,18 @@ struct JstrStage {
 constexpr uint32_t kStageBack = 16, kStageFwd = 12;
 constexpr int kStage16 = (int)(kStageBack + 15 + kC + kStageFwd + 15) / 16 + 1;  // and a dword to spare
 
-__device__ __forceinline__ JstrStage jstr_stage(jstr_u32x4* stage16, const uint8_t* src, uint32_t n, uint32_t at,
-                                                uint32_t len, uint32_t back, uint32_t fwd) {
+static_assert(kStage16 - 1 <= 2 * kJstrThreads, "two rounds of loads stage a chunk");
+
+__device__ __forceinline__ JstrStage jstr_stage(u32x4* lds, const uint8_t* src, uint32_t n, uint32_t at, uint32_t len,
+                                                uint32_t back, uint32_t fwd) {
     const uint32_t lo = at < back ? 0u : at - back;
     const uint64_t want = (uint64_t)at + len + fwd;
     const uint32_t hi = want > n ? n : (uint32_t)want;  // lo < hi: the chunk holds a byte
-    const uint8_t* first = src + lo;
-    const uint32_t a = (uint32_t)((uintptr_t)first & 15);
-    const jstr_u32x4* from = reinterpret_cast<const jstr_u32x4*>(first - a);
-    const uint32_t nstage = (a + (hi - lo) + 15) / 16;  // <= kStage16 - 1
-    for (uint32_t u = threadIdx.x; u < nstage; u += kJstrThreads) stage16[u] = from[u];
+    const uint32_t a = wg::stage16<kJstrThreads, 2>(src + lo, hi - lo, lds);  // <= kStage16 - 1 units
     JstrStage st;
-    st.bytes = reinterpret_cast<const uint8_t*>(stage16);
+    st.bytes = reinterpret_cast<const uint8_t*>(lds);
     st.pos0 = (int)(a + (at - lo));
     return st;
-}
-
-// image bytes [ioff, ioff + total) (LDS dwords, readable 8 bytes past the
-// last one) -> dst at any alignment. The caller has synchronized the image.
-__device__ __forceinline__ void jstr_copy_out(const uint32_t* image, uint32_t ioff, uint8_t* __restrict__ dst,
-                                              uint32_t total) {
-    const uint32_t t = threadIdx.x;
-    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(image) + ioff;
-    uint32_t head = (16u - (uint32_t)((uintptr_t)dst & 15)) & 15;
-    if (head > total) head = total;
-    if (t < head) dst[t] = bytes[t];
-    const uint32_t nv = (total - head) / 16;
-    const uint32_t sh = ((ioff + head) & 3) * 8;  // uniform: where a unit starts inside an LDS dword
-    jstr_u32x4* body = reinterpret_cast<jstr_u32x4*>(dst + head);
-    for (uint32_t v = t; v < nv; v += kJstrThreads) {
-        const uint32_t w = (ioff + head + 16 * v) >> 2;
-        jstr_u32x4 x;
-        if (sh == 0) {
-            x.x = image[w];
-            x.y = image[w + 1];
-            x.z = image[w + 2];
-            x.w = image[w + 3];
-        } else {
-            const uint32_t d0 = image[w], d1 = image[w + 1], d2 = image[w + 2], d3 = image[w + 3], d4 = image[w + 4];
-            x.x = jstr_shift(d0, d1, sh);
-            x.y = jstr_shift(d1, d2, sh);
-            x.z = jstr_shift(d2, d3, sh);
-            x.w = jstr_shift(d3, d4, sh);
-        }
-        body[v] = x;
-    }
-    for (uint32_t j = head + 16 * nv + t; j < total; j += kJstrThreads) dst[j] = bytes[j];
 }
 
 // The lane's 16 bytes of the chunk as two words; what lies past `mine` bytes
@@ -120,8 +62,8 @@ __device__ __forceinline__ void jstr_words_at(const JstrStage& st, uint32_t p, u
     if (mine != 0) {
         const uint32_t w = p >> 2, sh = (p & 3) * 8;
         const uint32_t d0 = dw[w], d1 = dw[w + 1], d2 = dw[w + 2], d3 = dw[w + 3], d4 = dw[w + 4];
-        a = (uint64_t)jstr_shift(d0, d1, sh) | (uint64_t)jstr_shift(d1, d2, sh) << 32;
-        b = (uint64_t)jstr_shift(d2, d3, sh) | (uint64_t)jstr_shift(d3, d4, sh) << 32;
+        a = (uint64_t)wg::funnel(d0, d1, sh) | (uint64_t)wg::funnel(d1, d2, sh) << 32;
+        b = (uint64_t)wg::funnel(d2, d3, sh) | (uint64_t)wg::funnel(d3, d4, sh) << 32;
         if (mine < 16) {
             const uint64_t keep_a = mine >= 8 ? ~0ull : (1ull << (8 * mine)) - 1;
             const uint64_t keep_b = mine <= 8 ? 0ull : (1ull << (8 * (mine - 8))) - 1;
@@ -141,29 +83,6 @@ __device__ __forceinline__ uint32_t jstr_bits_of(uint64_t w0, uint64_t w1, uint8
     return (uint32_t)(((js::EqMask8(w0, c) >> 7) * spread) >> 56) | (uint32_t)(((js::EqMask8(w1, c) >> 7) * spread) >> 56) << 8;
 }
 
-// Exclusive scan of v over the workgroup; *total its sum. part: 5 words of LDS.
-__device__ __forceinline__ uint32_t jstr_block_scan(uint32_t v, uint32_t* part, uint32_t* total) {
-    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(incl, off, 64);
-        if (lane >= (uint32_t)off) incl += y;
-    }
-    __syncthreads();  // part may still be read from an earlier scan
-    if (lane == 63) part[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, sum = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kJstrThreads / 64; ++k) {
-        const uint32_t x = part[k];
-        if (k < wave) before += x;
-        sum += x;
-    }
-    *total = sum;
-    return before + incl - v;
-}
-
 __device__ __forceinline__ uint32_t jstr_mine(uint32_t len) {
     const uint32_t o = 16 * threadIdx.x;
     return o < len ? (len - o < 16 ? len - o : 16u) : 0u;
@@ -174,10 +93,10 @@ __device__ __forceinline__ uint32_t jstr_mine(uint32_t len) {
 __global__ void __launch_bounds__(kJstrThreads) jstr_escape_size_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
                                                                         uint32_t* __restrict__ prefix,
                                                                         uint32_t* __restrict__ groups) {
-    __shared__ jstr_u32x4 stage16[kStage16];
+    __shared__ u32x4 stage16[kStage16];
     __shared__ uint32_t part[8];
     const uint32_t t = threadIdx.x;
-    const int ji = jstr_job_of_chunk(jobs, njobs, blockIdx.x);
+    const int ji = wg::job_of<&JsonStringJob::first_chunk>(jobs, njobs, blockIdx.x);
     const JsonStringJob job = jobs[ji];
     const uint32_t c = blockIdx.x - job.first_chunk;
     if (c >= job.nchunks) return;  // uniform
@@ -189,14 +108,14 @@ __global__ void __launch_bounds__(kJstrThreads) jstr_escape_size_kernel(const Js
     jstr_lane_words(st, mine, &w0, &w1);
     const uint32_t size = js::EscapedSize8(w0) + js::EscapedSize8(w1) - (16 - mine);
     uint32_t total;
-    const uint32_t before = jstr_block_scan(size, part, &total);
+    const uint32_t before = wg::block_excl_scan<kJstrThreads>(size, part, &total);
     if (job.row_ends && (t & 3) == 0) groups[job.first_group + c * 64 + (t >> 2)] = before;
     if (t == 0) prefix[blockIdx.x] = total;
 }
 
 __global__ void __launch_bounds__(kJstrThreads) jstr_rows_check_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
                                                                        uint32_t* __restrict__ bad) {
-    const int ji = jstr_job_of_rblock(jobs, njobs, blockIdx.x);
+    const int ji = wg::job_of<&JsonStringJob::first_rblock>(jobs, njobs, blockIdx.x);
     const JsonStringJob job = jobs[ji];
     if (!job.row_ends) return;
     const uint64_t r = (uint64_t)(blockIdx.x - job.first_rblock) * kJsonStringBlockRows + threadIdx.x;
@@ -249,7 +168,7 @@ __global__ void __launch_bounds__(kJstrThreads) jstr_rows_punct_kernel(const Jso
                                                                        const uint32_t* __restrict__ prefix,
                                                                        const uint32_t* __restrict__ groups,
                                                                        const int32_t* __restrict__ ok) {
-    const int ji = jstr_job_of_rblock(jobs, njobs, blockIdx.x);
+    const int ji = wg::job_of<&JsonStringJob::first_rblock>(jobs, njobs, blockIdx.x);
     const JsonStringJob job = jobs[ji];
     if (!job.row_ends || !ok[ji]) return;
     const uint64_t r = (uint64_t)(blockIdx.x - job.first_rblock) * kJsonStringBlockRows + threadIdx.x;
@@ -264,18 +183,18 @@ __global__ void __launch_bounds__(kJstrThreads) jstr_rows_punct_kernel(const Jso
     if (r + 1 < job.rows) o[2 + (ee - es)] = ',';
 }
 
-constexpr int kEscImage16 = (int)(6 * kC) / 16 + 1;  // copy_out reads past the last byte
+constexpr int kEscImage16 = (int)(6 * kC) / 16 + 1;  // copy_out_shifted reads one dword past
 
 __global__ void __launch_bounds__(kJstrThreads) jstr_escape_place_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
                                                                          const uint32_t* __restrict__ prefix,
                                                                          const int32_t* __restrict__ ok,
                                                                          JsonStringResult* __restrict__ res) {
-    __shared__ jstr_u32x4 stage16[kStage16];
-    __shared__ jstr_u32x4 image16[kEscImage16];
+    __shared__ u32x4 stage16[kStage16];
+    __shared__ u32x4 image16[kEscImage16];
     __shared__ uint32_t lane_before[kJstrThreads + 1];
     __shared__ uint32_t part[8];
     const uint32_t t = threadIdx.x;
-    const int ji = jstr_job_of_chunk(jobs, njobs, blockIdx.x);
+    const int ji = wg::job_of<&JsonStringJob::first_chunk>(jobs, njobs, blockIdx.x);
     const JsonStringJob job = jobs[ji];
     const uint32_t c = blockIdx.x - job.first_chunk;
     if (c >= job.nchunks || !ok[ji]) return;  // uniform
@@ -287,7 +206,7 @@ __global__ void __launch_bounds__(kJstrThreads) jstr_escape_place_kernel(const J
     jstr_lane_words(st, mine, &w0, &w1);
     const uint32_t size = js::EscapedSize8(w0) + js::EscapedSize8(w1) - (16 - mine);
     uint32_t total;
-    const uint32_t before = jstr_block_scan(size, part, &total);
+    const uint32_t before = wg::block_excl_scan<kJstrThreads>(size, part, &total);
     if (total != prefix[blockIdx.x + 1] - prefix[blockIdx.x]) {  // uniform: the source changed since the size pass
         if (t == 0) res[ji].err = 4;
         return;
@@ -308,7 +227,7 @@ __global__ void __launch_bounds__(kJstrThreads) jstr_escape_place_kernel(const J
     }
     if (!job.row_ends) {
         __syncthreads();
-        jstr_copy_out(image, ioff, job.dst + (job.quote ? 1 : 0) + out0, total);
+        wg::copy_out_shifted<kJstrThreads>(image, ioff, job.dst + (job.quote ? 1 : 0) + out0, total);
         return;
     }
     lane_before[t] = before;
@@ -338,7 +257,7 @@ __global__ void __launch_bounds__(kJstrThreads) jstr_escape_place_kernel(const J
             uint32_t xlo = lane_before[lo >> 4], xhi = lane_before[hi >> 4];
             for (uint32_t i = lo & ~15u; i < lo; ++i) xlo += js::EscapedSize(st.at(i));
             for (uint32_t i = hi & ~15u; i < hi; ++i) xhi += js::EscapedSize(st.at(i));
-            jstr_copy_out(image, ioff + xlo, job.dst + (uint64_t)out0 + xlo + 3ull * r + 1, xhi - xlo);
+            wg::copy_out_shifted<kJstrThreads>(image, ioff + xlo, job.dst + (uint64_t)out0 + xlo + 3ull * r + 1, xhi - xlo);
         }
         return;
     }
@@ -479,11 +398,11 @@ constexpr int kUnImage16 = (int)(kC + 16) / 16 + 1;
 
 __global__ void __launch_bounds__(kJstrThreads) jstr_unescape_scan_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
                                                                           uint32_t* __restrict__ info) {
-    __shared__ jstr_u32x4 stage16[kStage16];
+    __shared__ u32x4 stage16[kStage16];
     __shared__ uint64_t wave_np[4], wave_odd[4];
     __shared__ uint32_t acc[6];  // size 0 / 1, bad 0 / 1, the map, whether any lane met a backslash or a quote
     const uint32_t t = threadIdx.x;
-    const int ji = jstr_job_of_chunk(jobs, njobs, blockIdx.x);
+    const int ji = wg::job_of<&JsonStringJob::first_chunk>(jobs, njobs, blockIdx.x);
     const JsonStringJob job = jobs[ji];
     const uint32_t c = blockIdx.x - job.first_chunk;
     if (c >= job.nchunks) return;  // uniform
@@ -550,15 +469,10 @@ __global__ void __launch_bounds__(kJstrThreads) jstr_unescape_carry_kernel(const
         const uint32_t c = base + t;
         uint32_t* mine = info + (uint64_t)(job.first_chunk + c) * kJsonStringInfoWords;
         const uint32_t map = c < job.nchunks ? mine[4] : kMapIdentity;
-        uint32_t incl = map;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(incl, off, 64);
-            if (lane >= (uint32_t)off) incl = jstr_then(y, incl);
-        }
+        const uint32_t incl = wg::wave_incl_scan(map, [](uint32_t f, uint32_t g) { return jstr_then(f, g); });
         if (lane == 63) wave_map[wave] = incl;
         __syncthreads();
-        uint32_t excl = __shfl_up(incl, 1, 64);
+        uint32_t excl = wg::wave_prev(incl);
         if (lane == 0) excl = kMapIdentity;
         uint32_t front = kMapIdentity, tile = kMapIdentity;
         for (uint32_t k = 0; k < kJstrThreads / 64; ++k) {
@@ -583,12 +497,12 @@ __global__ void __launch_bounds__(kJstrThreads) jstr_unescape_place_kernel(const
                                                                            const uint32_t* __restrict__ prefix,
                                                                            const int32_t* __restrict__ ok,
                                                                            JsonStringResult* __restrict__ res) {
-    __shared__ jstr_u32x4 stage16[kStage16];
-    __shared__ jstr_u32x4 image16[kUnImage16];
+    __shared__ u32x4 stage16[kStage16];
+    __shared__ u32x4 image16[kUnImage16];
     __shared__ uint64_t wave_np[4], wave_odd[4];
     __shared__ uint32_t part[8];
     const uint32_t t = threadIdx.x;
-    const int ji = jstr_job_of_chunk(jobs, njobs, blockIdx.x);
+    const int ji = wg::job_of<&JsonStringJob::first_chunk>(jobs, njobs, blockIdx.x);
     const JsonStringJob job = jobs[ji];
     const uint32_t c = blockIdx.x - job.first_chunk;
     if (c >= job.nchunks || !ok[ji]) return;  // uniform
@@ -610,7 +524,7 @@ __global__ void __launch_bounds__(kJstrThreads) jstr_unescape_place_kernel(const
             if (t == 0) res[ji].err = 4;
             return;
         }
-        jstr_copy_out(reinterpret_cast<const uint32_t*>(stage16), (uint32_t)x.st.pos0, dst, len);
+        wg::copy_out_shifted<kJstrThreads>(reinterpret_cast<const uint32_t*>(stage16), (uint32_t)x.st.pos0, dst, len);
         return;
     }
     const uint32_t cin = info[(uint64_t)blockIdx.x * kJsonStringInfoWords + 5] & 1;
@@ -622,23 +536,23 @@ __global__ void __launch_bounds__(kJstrThreads) jstr_unescape_place_kernel(const
     const uint32_t m = jstr_starters(bs, depends ? cin : par, &mid);
     const uint32_t count = jstr_emit(x, i0, mine, w0, w1, m, &bad, nullptr);
     uint32_t total;
-    const uint32_t before = jstr_block_scan(count, part, &total);
+    const uint32_t before = wg::block_excl_scan<kJstrThreads>(count, part, &total);
     if (total != want || __syncthreads_or(bad != kNone)) {  // uniform: the source changed since the scan
         if (t == 0) res[ji].err = 4;
         return;
     }
     jstr_emit(x, i0, mine, w0, w1, m, &bad, reinterpret_cast<char*>(image16) + before);
     __syncthreads();
-    jstr_copy_out(reinterpret_cast<const uint32_t*>(image16), 0, dst, total);
+    wg::copy_out_shifted<kJstrThreads>(reinterpret_cast<const uint32_t*>(image16), 0, dst, total);
 }
 
 // ------------------------------------------------------------------- UTF-8
 
 __global__ void __launch_bounds__(kJstrThreads) jstr_utf8_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
                                                                  uint32_t* __restrict__ bad) {
-    __shared__ jstr_u32x4 stage16[kStage16];
+    __shared__ u32x4 stage16[kStage16];
     const uint32_t t = threadIdx.x;
-    const int ji = jstr_job_of_chunk(jobs, njobs, blockIdx.x);
+    const int ji = wg::job_of<&JsonStringJob::first_chunk>(jobs, njobs, blockIdx.x);
     const JsonStringJob job = jobs[ji];
     const uint32_t c = blockIdx.x - job.first_chunk;
     if (c >= job.nchunks) return;  // uniform

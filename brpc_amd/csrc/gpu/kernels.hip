@@ -28,6 +28,7 @@
 #include "base/crc32c.h"
 #include "gpu/kernels.h"
 #include "gpu/scoped.h"
+#include "gpu/workgroup.h"
 
 namespace mrpc {
 namespace gpu {
@@ -122,6 +123,8 @@ __device__ __forceinline__ void signal_done(const SegBatch& b) {
     }
 }
 
+// Not wg::job_of: the table is SegBatch's array of starts, not an array of
+// jobs, and this is the copy/CRC hot path.
 __device__ __forceinline__ int find_segment(const SegBatch& b, uint32_t chunk) {
     int lo = 0, hi = b.nseg - 1;
     while (lo < hi) {  // last seg with chunk_start <= chunk
@@ -434,7 +437,7 @@ __global__ void __launch_bounds__(kThreads) crc32c_mfma_kernel(
     const uint64_t nwaves = (uint64_t)gridDim.x * (kThreads / 64);
     for (uint64_t chunk = (uint64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); chunk < total;
          chunk += nwaves) {
-        int64_t lo = 0, hi = nseg - 1;
+        int64_t lo = 0, hi = nseg - 1;  // find_segment over 64-bit starts: stays with this kernel too
         while (lo < hi) {
             const int64_t mid = (lo + hi + 1) >> 1;
             if (chunk_start[mid] <= chunk) lo = mid;
@@ -694,30 +697,6 @@ __global__ void crc_chunk_count_kernel(const uint64_t* __restrict__ lens, int64_
 // ---------------------------------------------------------------- varint
 constexpr int kVTile = kThreads * 16;  // 4 KiB of bytes (or 4096 values) per tile
 
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* total, uint32_t* smem) {
-    // wave inclusive scan
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) smem[wave] = x;
-    __syncthreads();
-    uint32_t wave_prefix = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) {
-        const uint32_t s = smem[w];
-        if (w < wave) wave_prefix += s;
-        sum += s;
-    }
-    __syncthreads();
-    *total = sum;
-    return wave_prefix + x - v;
-}
-
 __global__ void __launch_bounds__(kThreads) varint_count_kernel(const uint8_t* __restrict__ in, uint64_t n,
                                                                 uint64_t* __restrict__ tile_counts) {
     __shared__ uint32_t smem[kThreads / 64];
@@ -732,7 +711,7 @@ __global__ void __launch_bounds__(kThreads) varint_count_kernel(const uint8_t* _
         for (uint64_t i = base; i < base + 16 && i < n; ++i) c += (in[i] & 0x80) ? 0 : 1;
     }
     uint32_t total;
-    block_exclusive_scan(c, &total, smem);
+    wg::block_excl_scan<kThreads>(c, smem, &total);
     if (threadIdx.x == 0) tile_counts[blockIdx.x] = total;
 }
 
@@ -813,10 +792,10 @@ __global__ void __launch_bounds__(kThreads) varint_decode_kernel(const uint8_t* 
     // previous 16 bytes: neighbour lane, or memory for lane 0 (zeros before
     // the stream start act as terminators)
     uint4 prev;
-    prev.x = __shfl_up(cur.x, 1, 64);
-    prev.y = __shfl_up(cur.y, 1, 64);
-    prev.z = __shfl_up(cur.z, 1, 64);
-    prev.w = __shfl_up(cur.w, 1, 64);
+    prev.x = wg::wave_prev(cur.x);
+    prev.y = wg::wave_prev(cur.y);
+    prev.z = wg::wave_prev(cur.z);
+    prev.w = wg::wave_prev(cur.w);
     if (lane == 0) {
         if (base >= 16) {
             if ((reinterpret_cast<uintptr_t>(in + base - 16) & 15) == 0) {
@@ -834,7 +813,7 @@ __global__ void __launch_bounds__(kThreads) varint_decode_kernel(const uint8_t* 
     if (nb < 16) tcur &= (1u << nb) - 1;  // bytes past the end are not terminators
     const uint32_t window_terms = term_mask16(prev) | (tcur << 16);
     uint32_t total;
-    uint64_t idx = tile_offsets[blockIdx.x] + block_exclusive_scan(__popc(tcur), &total, smem);
+    uint64_t idx = tile_offsets[blockIdx.x] + wg::block_excl_scan<kThreads>((uint32_t)__popc(tcur), smem, &total);
     const uint64_t W[4] = {((uint64_t)prev.y << 32) | prev.x, ((uint64_t)prev.w << 32) | prev.z,
                            ((uint64_t)cur.y << 32) | cur.x, ((uint64_t)cur.w << 32) | cur.z};
     uint32_t t = tcur;
@@ -878,16 +857,6 @@ __device__ __forceinline__ uint64_t zz(uint64_t v, int zigzag) {
     return zigzag ? (v << 1) ^ (uint64_t)((int64_t)v >> 63) : v;
 }
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    return x;
-}
-
 // Encode: a tile is 4096 values; wave w owns values [1024w, 1024w+1024) and
 // walks them 64 at a time with coalesced 8 B loads. Pass 1 of the kernel
 // sums the wave's encoded length, the 4 wave totals are scanned in LDS,
@@ -904,7 +873,7 @@ __global__ void __launch_bounds__(kThreads) varint_len_kernel(const uint64_t* __
         if (i < n) c += varint_len(zz(in[i], zigzag));
     }
     uint32_t total;
-    block_exclusive_scan(c, &total, smem);
+    wg::block_excl_scan<kThreads>(c, smem, &total);
     if (threadIdx.x == 0) tile_counts[blockIdx.x] = total;
 }
 
@@ -922,7 +891,7 @@ __global__ void __launch_bounds__(kThreads) varint_encode_kernel(const uint64_t*
         const uint64_t i = base + (uint64_t)k * 64;
         if (i < n) c += varint_len(zz(in[i], zigzag));
     }
-    const uint32_t wt = wave_incl_scan(c);
+    const uint32_t wt = wg::wave_incl_scan(c);
     if (lane == 63) wave_tot[wave] = wt;
     __syncthreads();
     uint64_t pos = tile_offsets[blockIdx.x];
@@ -931,7 +900,7 @@ __global__ void __launch_bounds__(kThreads) varint_encode_kernel(const uint64_t*
         const uint64_t i = base + (uint64_t)k * 64;
         uint64_t v = i < n ? zz(in[i], zigzag) : 0;
         const uint32_t L = i < n ? varint_len(v) : 0;
-        const uint32_t incl = wave_incl_scan(L);
+        const uint32_t incl = wg::wave_incl_scan(L);
         const uint32_t wsum = __shfl(incl, 63, 64);
         uint8_t* dst = out + pos + (incl - L);
         for (uint32_t j = 0; j < L; ++j) {

@@ -23,6 +23,7 @@
 #include "base/pb_rows.h"
 #include "gpu/kernels.h"
 #include "gpu/device_pb.h"
+#include "gpu/workgroup.h"
 
 namespace mrpc {
 namespace gpu {
@@ -30,6 +31,7 @@ namespace gpu {
 namespace {
 
 typedef const __attribute__((address_space(1))) uint8_t gbyte_c;
+using wg::u32x4;
 
 __global__ void __launch_bounds__(256) pb_scan_kernel(const uint8_t* __restrict__ buf_,
                                                       uint64_t buf_len, const int64_t* __restrict__ offsets,
@@ -68,12 +70,11 @@ __global__ void __launch_bounds__(256) pb_scan_ptrs_kernel(const PbScanJob* __re
 // One workgroup (4 waves) per PbRunChunk. The chunk is walked in 8 rounds
 // of 256 consecutive elements: lane t of round r takes element 256r + t
 // (a coalesced 1/4/8-byte load from the source, pinned host or HBM), the
-// encoded lengths are block-scanned (wave shuffles + 4 wave totals in LDS)
-// and every lane writes its bytes into the chunk's output image in LDS
-// (<= 21 B per element: 43 KiB). The image then leaves with byte stores
-// that are contiguous across the lanes of each instruction, so a host
-// destination sees full-line PCIe writes instead of one small write per
-// varint.
+// encoded lengths are block-scanned and every lane writes its bytes into the
+// chunk's output image in LDS (<= 21 B per element: 43 KiB). The image then
+// leaves through wg::copy_out_bytes, 16-byte stores for the aligned middle:
+// over PCIe to pinned host memory a wave's byte stores make 64-byte writes,
+// its 16-byte stores 1 KiB ones.
 constexpr int kRunThreads = 256;
 constexpr uint32_t kRunMaxElemBytes = 21;  // "-9223372036854775808" + ','
 
@@ -126,36 +127,13 @@ __device__ __forceinline__ uint32_t run_digits(uint64_t v) {
     return d;
 }
 
-// Copies an LDS image to dst (any alignment) with 16-byte stores for the
-// aligned middle: over PCIe to pinned host memory a wave's byte stores make
-// 64-byte writes, its 16-byte stores 1 KiB ones.
-__device__ __forceinline__ void copy_out(uint8_t* dst, const uint8_t* image, uint32_t total) {
-    const uint32_t t = threadIdx.x;
-    uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);
-    if (head > total) head = total;
-    if (t < head) dst[t] = image[t];
-    const uint32_t nv = (total - head) / 16;
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    u32x4* body = reinterpret_cast<u32x4*>(dst + head);
-    for (uint32_t w = t; w < nv; w += kRunThreads) {
-        const uint8_t* q = image + head + 16 * w;
-        u32x4 v;
-        v.x = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-        v.y = (uint32_t)q[4] | ((uint32_t)q[5] << 8) | ((uint32_t)q[6] << 16) | ((uint32_t)q[7] << 24);
-        v.z = (uint32_t)q[8] | ((uint32_t)q[9] << 8) | ((uint32_t)q[10] << 16) | ((uint32_t)q[11] << 24);
-        v.w = (uint32_t)q[12] | ((uint32_t)q[13] << 8) | ((uint32_t)q[14] << 16) | ((uint32_t)q[15] << 24);
-        body[w] = v;
-    }
-    for (uint32_t j = head + 16 * nv + t; j < total; j += kRunThreads) dst[j] = image[j];
-}
-
 __global__ void __launch_bounds__(kRunThreads) pb_run_encode_kernel(const PbRunChunk* __restrict__ chunks,
                                                                     int32_t* __restrict__ err) {
     __shared__ uint8_t image[kPbRunChunkElems * kRunMaxElemBytes];
     __shared__ uint32_t wave_tot[kRunThreads / 64];
     __shared__ uint32_t round_base;
     const PbRunChunk c = chunks[blockIdx.x];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x, wave = t >> 6;
     const bool decimal = c.format == PB_RUN_DECIMAL;
     if (t == 0) round_base = 0;
     __syncthreads();
@@ -191,14 +169,10 @@ __global__ void __launch_bounds__(kRunThreads) pb_run_encode_kernel(const PbRunC
             }
             if (decimal && !(c.last && i + 1 == count)) len += 1;  // ','
         }
-        // block exclusive scan of len in element order
-        uint32_t incl = len;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += y;
-        }
-        if (lane == 63) wave_tot[wave] = incl;
+        // block exclusive scan of len in element order: the two halves of
+        // wg::block_excl_scan with the tail written out. wg::scan_rank's
+        // unrolled form costs this kernel 10 VGPRs (57 -> 67), a wave per SIMD
+        const uint32_t incl = wg::scan_post(len, wave_tot);
         __syncthreads();
         uint32_t pos = round_base + incl - len;
         for (int w = 0; w < wave; ++w) pos += wave_tot[w];
@@ -237,7 +211,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_run_encode_kernel(const PbRunC
         if (t == 0) err[blockIdx.x] = 1;
         return;
     }
-    copy_out(c.dst, image, total);
+    wg::copy_out_bytes<kRunThreads>(image, c.dst, total);
     if (t == 0) err[blockIdx.x] = 0;
 }
 
@@ -245,37 +219,16 @@ __global__ void __launch_bounds__(kRunThreads) pb_run_encode_kernel(const PbRunC
 // Packed fields of a decoded body (the reference's ParsePbFromIOBuf walks
 // them element by element on the host, src/brpc/protocol.cpp).
 // Both passes read the chunk (plus up to 16 bytes of the run before it)
-// with 16-byte loads of the aligned span around it (a byte outside the run
-// shares its aligned 16 bytes with a byte inside, so with its page): a
-// wave's load moves 1 KiB instead of the 64 bytes of per-lane byte loads,
-// which held the count pass to ~1 TB/s on HBM. Lane t then owns chunk bytes
-// [16t, 16t + 16) of the staged copy.
+// with 16-byte loads of the aligned span around it (the decode pass through
+// wg::stage16): a wave's load moves 1 KiB instead of the 64 bytes of per-lane
+// byte loads, which held the count pass to ~1 TB/s on HBM. Lane t then owns
+// chunk bytes [16t, 16t + 16) of the staged copy.
 constexpr int kHalo = 16;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // staged at raw + kPad: every lane's 32-byte window (16 bytes before its
 // own 16) stays inside the array
 constexpr int kPad = 16;
 constexpr int kStage16 = (kPad + kHalo + kPbRunDecodeChunkBytes + 64) / 16;
-
-// Stages [p, p + n) into lds (n <= kHalo + chunk); returns the LDS byte
-// offset of p.
-__device__ __forceinline__ uint32_t stage_aligned(const uint8_t* p, uint32_t n, u32x4* lds) {
-    const uint32_t a = (uint32_t)((uintptr_t)p & 15);
-    const u32x4* src = reinterpret_cast<const u32x4*>(p - a);
-    const uint32_t n16 = (a + n + 15) >> 4;
-    u32x4 v[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const uint32_t i = threadIdx.x + (uint32_t)k * kRunThreads;
-        if (i < n16) v[k] = src[i];
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const uint32_t i = threadIdx.x + (uint32_t)k * kRunThreads;
-        if (i < n16) lds[i] = v[k];
-    }
-    return a;
-}
+static_assert((kHalo + kPbRunDecodeChunkBytes + 15 + 15) / 16 <= 2 * kRunThreads, "two rounds of loads stage a chunk");
 
 // Bits 0..3 of each nibble k: byte k of w ends a varint (top bit clear).
 __device__ __forceinline__ uint32_t ends_of(uint32_t w) {
@@ -318,8 +271,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_run_count_kernel(const PbRunDe
                 if (hi > lo) n += __popc(bits & (((1u << hi) - 1) & ~((1u << lo) - 1)));
             }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+        n = wg::wave_sum(n);
         if (lane == 0) {
             counts[ci] = n;  // the host's copy (pinned)
             prefix[ci] = n;  // scanned in HBM by pb_run_prefix_kernel
@@ -335,7 +287,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_run_count_kernel(const PbRunDe
 constexpr int kPrefixThreads = 1024, kPrefixPer = 4;
 __global__ void __launch_bounds__(kPrefixThreads) pb_run_prefix_kernel(uint32_t* __restrict__ prefix, int n) {
     __shared__ uint32_t wave_tot[kPrefixThreads / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     uint32_t carry = 0;
     for (int base = 0; base < n; base += kPrefixThreads * kPrefixPer) {
         const int i0 = base + t * kPrefixPer;
@@ -345,20 +297,8 @@ __global__ void __launch_bounds__(kPrefixThreads) pb_run_prefix_kernel(uint32_t*
             v[j] = i0 + j < n ? prefix[i0 + j] : 0;
             mine += v[j];
         }
-        uint32_t incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += y;
-        }
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        uint32_t run = carry + incl - mine, tile = 0;
-        for (int w = 0; w < kPrefixThreads / 64; ++w) {
-            const uint32_t x = wave_tot[w];
-            if (w < wave) run += x;
-            tile += x;
-        }
+        uint32_t tile;
+        uint32_t run = carry + wg::block_excl_scan<kPrefixThreads>(mine, wave_tot, &tile);
 #pragma unroll
         for (int j = 0; j < kPrefixPer; ++j) {
             if (i0 + j < n) prefix[i0 + j] = run;
@@ -384,20 +324,6 @@ __device__ __forceinline__ void store_elem(uint8_t* o, uint32_t kind, uint64_t r
     }
 }
 
-// dst gets image[sh, sh + total) where dst = sh (mod 16): the aligned body
-// moves as 16-byte LDS reads and 16-byte stores.
-__device__ __forceinline__ void copy_out_aligned(uint8_t* dst, const uint8_t* image, uint32_t sh, uint32_t total) {
-    const uint32_t t = threadIdx.x;
-    uint32_t head = (16 - sh) & 15;
-    if (head > total) head = total;
-    if (t < head) dst[t] = image[sh + t];
-    const uint32_t nv = (total - head) / 16;
-    const u32x4* from = reinterpret_cast<const u32x4*>(image + sh + head);
-    u32x4* body = reinterpret_cast<u32x4*>(dst + head);
-    for (uint32_t w = t; w < nv; w += kRunThreads) body[w] = from[w];
-    for (uint32_t j = head + 16 * nv + t; j < total; j += kRunThreads) dst[j] = image[sh + j];
-}
-
 __global__ void __launch_bounds__(kRunThreads) pb_run_decode_kernel(const PbRunDecodeChunk* __restrict__ chunks,
                                                                     int nchunks,
                                                                     const uint32_t* __restrict__ prefix,
@@ -406,7 +332,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_run_decode_kernel(const PbRunD
     __shared__ __attribute__((aligned(16))) uint8_t image[kPbRunDecodeChunkBytes * 8 + 16];
     __shared__ uint32_t wave_tot[kRunThreads / 64];
     __shared__ int bad;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     PbRunDecodeChunk c = chunks[blockIdx.x];
     // grid-stride over the chunks; the next descriptor (pinned host memory)
     // is fetched while this chunk decodes
@@ -417,7 +343,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_run_decode_kernel(const PbRunD
         const uint32_t halo = c.offset < (uint32_t)kHalo ? c.offset : (uint32_t)kHalo;
         if (t == 0) bad = 0;
         // chunk byte x (x in [-halo, len)) is at LDS byte x + o
-        const uint32_t o = kPad + stage_aligned(c.run + c.offset - halo, halo + len, raw + kPad / 16) + halo;
+        const uint32_t o = kPad + wg::stage16<kRunThreads, 2>(c.run + c.offset - halo, halo + len, raw + kPad / 16) + halo;
         // first element index: the earlier chunks of the run
         const uint32_t base = prefix[ci] - prefix[c.first];
         const uint32_t eb = c.kind == PB_RUN_BOOL ? 1 : (c.kind <= PB_RUN_SINT32 ? 4 : 8);
@@ -442,7 +368,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_run_decode_kernel(const PbRunD
             for (int k = 0; k < 9; ++k) w9[k] = words[k];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                W[k] = fs ? (uint32_t)((((uint64_t)w9[k + 1] << 32) | w9[k]) >> fs) : w9[k];
+                W[k] = fs ? wg::funnel(w9[k], w9[k + 1], fs) : w9[k];
             }
         }
         uint32_t cont = 0;  // bit i: window byte i carries a continuation bit
@@ -459,17 +385,8 @@ __global__ void __launch_bounds__(kRunThreads) pb_run_decode_kernel(const PbRunD
         const uint32_t own = mine_n >= 16 ? 0xFFFFu : (mine_n <= 0 ? 0u : ((1u << mine_n) - 1));
         const uint32_t term = (~cont >> 16) & own;
         const uint32_t mine = __popc(term);
-        uint32_t incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += y;
-        }
-        if (lane == 63) wave_tot[wave] = incl;
-        __syncthreads();
-        uint32_t rank = incl - mine;
-        for (int w = 0; w < wave; ++w) rank += wave_tot[w];
-        const uint32_t total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+        uint32_t total;
+        uint32_t rank = wg::block_excl_scan<kRunThreads>(mine, wave_tot, &total);
 #define WBYTE(i) ((W[(i) >> 2] >> (8 * ((i) & 3))) & 0xFFu)
 #pragma unroll
         for (int p = 16; p < 32; ++p) {
@@ -492,9 +409,9 @@ __global__ void __launch_bounds__(kRunThreads) pb_run_decode_kernel(const PbRunD
         } else {
             const uint32_t nbytes = total * eb;
             if (sh == sh0) {
-                copy_out_aligned(dst, image, sh, nbytes);
+                wg::copy_out_phased<kRunThreads>(image, sh, dst, nbytes);
             } else {
-                copy_out(dst, image, nbytes);
+                wg::copy_out_bytes<kRunThreads>(image, dst, nbytes);
             }
             if (t == 0) err[ci] = 0;
         }
@@ -585,8 +502,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_msg_size_kernel(const PbMsgChu
                     if (i < count) n += run_varint_len(run_value(raws[k], c.kind));
                 }
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+            n = wg::wave_sum(n);
         }
         if (lane == 0) sizes[ci] = n;
     }
@@ -627,9 +543,7 @@ __global__ void __launch_bounds__(64) pb_msg_layout_kernel(const PbMsgJob* __res
             msg_field_lens(fields[m.first_field + f0 + lane], prefix, &plen, &hlen);
             mine = (uint64_t)plen + hlen;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-        total += mine;
+        total += wg::wave_sum(mine);
     }
     const bool fits = total <= m.cap;
     uint64_t carry = 0;
@@ -643,12 +557,7 @@ __global__ void __launch_bounds__(64) pb_msg_layout_kernel(const PbMsgJob* __res
             msg_field_lens(f, prefix, &plen, &hlen);
         }
         const uint64_t mine = (uint64_t)plen + hlen;
-        uint64_t incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint64_t y = __shfl_up(incl, off, 64);
-            if (lane >= (uint32_t)off) incl += y;
-        }
+        const uint64_t incl = wg::wave_incl_scan(mine);
         const uint64_t off = carry + incl - mine;
         if (live) {
             if (fits) {
@@ -671,11 +580,10 @@ __global__ void __launch_bounds__(64) pb_msg_layout_kernel(const PbMsgJob* __res
 
 // One workgroup per chunk. A numeric chunk is encoded like
 // pb_run_encode_kernel's varint path, into an LDS image that sits at the
-// destination's 16-byte phase, so it leaves as 16-byte LDS reads and 16-byte
-// stores around an unaligned head and tail. What the chunk encodes to is
-// compared with what the size pass measured: the two differ only when the
-// source changed in between, and then nothing is written (the offsets of
-// every later chunk were derived from the measured size).
+// destination's 16-byte phase, so it leaves through wg::copy_out_phased. What
+// the chunk encodes to is compared with what the size pass measured: the two
+// differ only when the source changed in between, and then nothing is written
+// (the offsets of every later chunk were derived from the measured size).
 __global__ void __launch_bounds__(kRunThreads) pb_msg_place_kernel(const PbMsgChunk* __restrict__ chunks,
                                                                    const PbMsgField* __restrict__ fields,
                                                                    const uint32_t* __restrict__ prefix,
@@ -690,32 +598,16 @@ __global__ void __launch_bounds__(kRunThreads) pb_msg_place_kernel(const PbMsgCh
     if (!b) return;  // the message did not fit (the whole workgroup leaves)
     const uint32_t want = prefix[ci + 1] - prefix[ci];
     uint8_t* dst = reinterpret_cast<uint8_t*>((uintptr_t)(b + (uint32_t)(prefix[ci] - prefix[c.first])));
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const uint32_t count = msg_chunk_count(c);
-    if (c.kind == PB_MSG_BYTES) {
-        // a straight copy through LDS: 16-byte loads of the aligned span
-        // around the source, all issued before the first is stored
-        const uint8_t* p = static_cast<const uint8_t*>(c.src);
-        const uint32_t a = (uint32_t)((uintptr_t)p & 15);
-        const u32x4* src = reinterpret_cast<const u32x4*>(p - a);
-        const uint32_t n16 = (a + count + 15) >> 4;
+    if (c.kind == PB_MSG_BYTES) {  // a straight copy through LDS
         constexpr int kUnits = (kPbMsgBytesChunk / 16 + 2 + kRunThreads - 1) / kRunThreads;
-        u32x4 v[kUnits];
-#pragma unroll
-        for (int k = 0; k < kUnits; ++k) {
-            const uint32_t i = (uint32_t)t + (uint32_t)k * kRunThreads;
-            if (i < n16) v[k] = src[i];
-        }
-#pragma unroll
-        for (int k = 0; k < kUnits; ++k) {
-            const uint32_t i = (uint32_t)t + (uint32_t)k * kRunThreads;
-            if (i < n16) image16[i] = v[k];
-        }
+        const uint32_t a = wg::stage16<kRunThreads, kUnits>(static_cast<const uint8_t*>(c.src), count, image16);
         __syncthreads();
         if (((uintptr_t)dst & 15) == a) {
-            copy_out_aligned(dst, image, a, count);
+            wg::copy_out_phased<kRunThreads>(image, a, dst, count);
         } else {
-            copy_out(dst, image + a, count);
+            wg::copy_out_bytes<kRunThreads>(image + a, dst, count);
         }
         return;
     }
@@ -736,26 +628,14 @@ __global__ void __launch_bounds__(kRunThreads) pb_msg_place_kernel(const PbMsgCh
         const uint32_t i = (uint32_t)r * kRunThreads + t;
         raws[r] = run_value(raws[r], c.kind);
         lens[r] = i < count ? run_varint_len(raws[r]) : 0;
-        uint32_t incl = lens[r];
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += y;
-        }
-        incls[r] = incl;
-        if (lane == 63) wave_tot[r][wave] = incl;
+        incls[r] = wg::scan_post(lens[r], wave_tot[r]);
     }
     __syncthreads();
     uint32_t total = 0;
 #pragma unroll
     for (int r = 0; r < kRounds; ++r) {
-        uint32_t pos = total + incls[r] - lens[r];
-#pragma unroll
-        for (int w = 0; w < kRunThreads / 64; ++w) {
-            const uint32_t x = wave_tot[r][w];
-            if (w < wave) pos += x;
-            total += x;
-        }
+        const uint32_t before = total;  // the rounds in front of this one
+        const uint32_t pos = before + wg::scan_rank<kRunThreads>(incls[r], lens[r], wave_tot[r], &total);
         uint8_t* o = image + sh + pos;
         uint64_t v = raws[r];
         for (uint32_t j = 0; j < lens[r]; ++j) {
@@ -768,7 +648,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_msg_place_kernel(const PbMsgCh
         if (t == 0) res[fields[c.field].msg].err = 4;
         return;
     }
-    copy_out_aligned(dst, image, sh, total);
+    wg::copy_out_phased<kRunThreads>(image, sh, dst, total);
 }
 
 // ------------------------------------------------------------- row builder
@@ -780,22 +660,6 @@ __global__ void __launch_bounds__(kRunThreads) pb_msg_place_kernel(const PbMsgCh
 constexpr int kRowsRounds = kPbRowsChunkElems / kRunThreads;
 constexpr uint32_t kRowsFewRows = 16;  // a chunk meeting at most this many rows leaves segment by segment
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;
-
-// The job owning chunk (or row block) x: the last one that starts at or
-// before it (a job without chunks shares its start with the next job).
-__device__ __forceinline__ int rows_job_of(const PbRowsJob* jobs, int njobs, uint32_t x, bool by_rblock) {
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        const uint32_t first = by_rblock ? jobs[mid].first_rblock : jobs[mid].first_chunk;
-        if (first <= x) {
-            lo = mid;
-        } else {
-            hi = mid - 1;
-        }
-    }
-    return lo;
-}
 
 __global__ void __launch_bounds__(64) pb_rows_init_kernel(const PbRowsJob* __restrict__ jobs, int njobs,
                                                           PbRowsJob* __restrict__ jobs_dev,
@@ -817,7 +681,7 @@ __global__ void __launch_bounds__(64) pb_rows_init_kernel(const PbRowsJob* __res
 
 __global__ void __launch_bounds__(kRunThreads) pb_rows_size_kernel(const PbRowsJob* __restrict__ jobs, int njobs,
                                                                    uint32_t* __restrict__ groups) {
-    const PbRowsJob job = jobs[rows_job_of(jobs, njobs, blockIdx.x, false)];
+    const PbRowsJob job = jobs[wg::job_of<&PbRowsJob::first_chunk>(jobs, njobs, blockIdx.x)];
     if (!pb_rows::IsVarintKind(job.kind)) return;
     const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbRowsChunkElems;
     const uint32_t n = job.count - cs < kPbRowsChunkElems ? job.count - cs : kPbRowsChunkElems;
@@ -832,9 +696,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_size_kernel(const PbRowsJ
 #pragma unroll
     for (int r = 0; r < kRowsRounds; ++r) {
         const uint32_t i = (uint32_t)r * kRunThreads + t;
-        uint32_t len = i < n ? run_varint_len(v[r]) : 0;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) len += __shfl_xor(len, off, 64);
+        const uint32_t len = wg::wave_sum(i < n ? run_varint_len(v[r]) : 0u);
         const uint32_t g0 = (uint32_t)r * kRunThreads + wave * 64;  // the group's first element in the chunk
         if (lane == 0 && g0 < n) groups[job.first_group + (cs + g0) / kPbRowsGroupElems] = len;
     }
@@ -850,29 +712,6 @@ __device__ __forceinline__ uint32_t rows_bytes_before(const PbRowsJob& job, cons
     return b;
 }
 
-// Sum of v over the workgroup's 256 lanes (every lane calls it), and the sum
-// over the lanes before this one in *before.
-__device__ __forceinline__ uint32_t rows_block_scan(uint32_t v, uint32_t* wave_tot, uint32_t* before) {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(incl, off, 64);
-        if (lane >= (uint32_t)off) incl += y;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    uint32_t sum = 0, mine = incl - v;
-#pragma unroll
-    for (uint32_t k = 0; k < kPbRowsBlockRows / 64; ++k) {
-        const uint32_t x = wave_tot[k];
-        if (k < wave) mine += x;
-        sum += x;
-    }
-    *before = mine;
-    return sum;
-}
-
 __global__ void __launch_bounds__(kPbRowsBlockRows) pb_rows_measure_kernel(const PbRowsJob* __restrict__ jobs,
                                                                            int njobs,
                                                                            const uint32_t* __restrict__ groups,
@@ -882,7 +721,7 @@ __global__ void __launch_bounds__(kPbRowsBlockRows) pb_rows_measure_kernel(const
                                                                            uint32_t* __restrict__ block_off,
                                                                            uint32_t* __restrict__ first_bad) {
     __shared__ uint32_t wave_tot[kPbRowsBlockRows / 64];
-    const int j = rows_job_of(jobs, njobs, blockIdx.x, true);
+    const int j = wg::job_of<&PbRowsJob::first_rblock>(jobs, njobs, blockIdx.x);
     const PbRowsJob job = jobs[j];
     const uint32_t block = blockIdx.x - job.first_rblock;
     const uint64_t r64 = (uint64_t)block * kPbRowsBlockRows + threadIdx.x;
@@ -904,8 +743,8 @@ __global__ void __launch_bounds__(kPbRowsBlockRows) pb_rows_measure_kernel(const
         row_pay[at] = p;
         row_delta[at] = before;
     }
-    uint32_t unused;
-    const uint32_t sum = rows_block_scan(size, wave_tot, &unused);
+    uint32_t sum;
+    wg::block_excl_scan<(int)kPbRowsBlockRows>(size, wave_tot, &sum);
     if (threadIdx.x == 0) {
         // the job's blocks, then one entry that becomes its total under the scan
         const uint32_t at = blockIdx.x + (uint32_t)j;
@@ -929,7 +768,7 @@ __global__ void __launch_bounds__(kPbRowsBlockRows) pb_rows_heads_kernel(const P
                                                                          const uint32_t* __restrict__ first_bad,
                                                                          PbRowsResult* __restrict__ res) {
     __shared__ uint32_t wave_tot[kPbRowsBlockRows / 64];
-    const int j = rows_job_of(jobs, njobs, blockIdx.x, true);
+    const int j = wg::job_of<&PbRowsJob::first_rblock>(jobs, njobs, blockIdx.x);
     const PbRowsJob job = jobs[j];
     const uint64_t r64 = (uint64_t)(blockIdx.x - job.first_rblock) * kPbRowsBlockRows + threadIdx.x;
     const bool live = r64 < job.rows;
@@ -941,8 +780,8 @@ __global__ void __launch_bounds__(kPbRowsBlockRows) pb_rows_heads_kernel(const P
     if (!ok) return;  // the whole workgroup
     const uint32_t at = job.first_row + r;
     // the row's offset: the blocks before this one, then the rows before it here
-    uint32_t off;
-    rows_block_scan(live ? row_size[at] : 0, wave_tot, &off);
+    uint32_t block_size;
+    uint32_t off = wg::block_excl_scan<(int)kPbRowsBlockRows>(live ? row_size[at] : 0u, wave_tot, &block_size);
     if (!live) return;
     off += block_off[blockIdx.x + (uint32_t)j] - block_off[job.first_rblock + (uint32_t)j];
     const uint32_t nelems = job.row_ends[r] - (r ? job.row_ends[r - 1] : 0);
@@ -969,7 +808,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
     __shared__ uint32_t wave_tot[kRowsRounds][kRunThreads / 64];
     __shared__ uint32_t wave_max[kRunThreads / 64];
     uint8_t* image = reinterpret_cast<uint8_t*>(image16);
-    const int j = rows_job_of(jobs, njobs, blockIdx.x, false);
+    const int j = wg::job_of<&PbRowsJob::first_chunk>(jobs, njobs, blockIdx.x);
     const PbRowsJob job = jobs[j];
     if (first_bad[j] != kNoRow) return;
     const uint32_t total = rows_job_total(job, j, block_off);
@@ -1021,25 +860,13 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
         for (int r = 0; r < kRowsRounds; ++r) {
             const uint32_t i = (uint32_t)r * kRunThreads + t;
             lens[r] = i < n ? run_varint_len(vals[r]) : 0;
-            uint32_t incl = lens[r];
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t y = __shfl_up(incl, off, 64);
-                if (lane >= (uint32_t)off) incl += y;
-            }
-            poss[r] = incl - lens[r];
-            if (lane == 63) wave_tot[r][wave] = incl;
+            poss[r] = wg::scan_post(lens[r], wave_tot[r]);  // the wave's inclusive scan until the barrier
         }
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < kRowsRounds; ++r) {
-            poss[r] += bytes;
-#pragma unroll
-            for (int k = 0; k < kRunThreads / 64; ++k) {
-                const uint32_t x = wave_tot[r][k];
-                if ((uint32_t)k < wave) poss[r] += x;
-                bytes += x;
-            }
+            const uint32_t before = bytes;  // the rounds in front of this one
+            poss[r] = before + wg::scan_rank<kRunThreads>(poss[r], lens[r], wave_tot[r], &bytes);
         }
     } else {
         before_cs = cs * w;
@@ -1099,9 +926,9 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
             }
             uint8_t* d = job.dst + off;
             if (((uint32_t)(uintptr_t)d & 15) == ((sh + a) & 15)) {
-                copy_out_aligned(d, image, sh + a, b - a);
+                wg::copy_out_phased<kRunThreads>(image, sh + a, d, b - a);
             } else {
-                copy_out(d, image + sh + a, b - a);
+                wg::copy_out_bytes<kRunThreads>(image + sh + a, d, b - a);
             }
         }
         return;
@@ -1128,14 +955,9 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
             run = run > x ? run : x;
             m[k] = run;
         }
-        uint32_t incl = run;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(incl, off, 64);
-            if (lane >= (uint32_t)off && y > incl) incl = y;
-        }
+        const uint32_t incl = wg::wave_incl_scan(run, [](uint32_t a, uint32_t b) { return a > b ? a : b; });
         if (lane == 63) wave_max[wave] = incl;
-        uint32_t carry = __shfl_up(incl, 1, 64);
+        uint32_t carry = wg::wave_prev(incl);
         if (lane == 0) carry = 0;
         __syncthreads();
         for (uint32_t k = 0; k < wave; ++k) carry = carry > wave_max[k] ? carry : wave_max[k];
@@ -1187,22 +1009,7 @@ constexpr uint32_t kSplitAhead = 32;                         // staged behind a 
 constexpr uint32_t kSplitBack = 16;                          // staged in front of one: a varint's nine earlier bytes
 constexpr int kSplitStage16 = (kSplitBack + kPbSplitChunk + kSplitAhead + 16 + 15) / 16;
 static_assert(kPbSplitChunk == 64 * 64 && kRunThreads == 256 && kSplitAhead >= pb_rows::kSpecReadBytes, "split layout");
-static_assert(2 * kRunThreads * 16 >= kSplitStage16 * 16, "stage_aligned covers a staged chunk");
-
-// which: 0 message chunks, 1 row blocks, 2 output chunks
-__device__ __forceinline__ int split_job_of(const PbSplitJob* jobs, int njobs, uint32_t x, int which) {
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        const uint32_t first = which == 0 ? jobs[mid].first_chunk : (which == 1 ? jobs[mid].first_rblock : jobs[mid].first_ochunk);
-        if (first <= x) {
-            lo = mid;
-        } else {
-            hi = mid - 1;
-        }
-    }
-    return lo;
-}
+static_assert(2 * kRunThreads * 16 >= kSplitStage16 * 16, "two rounds of loads stage a chunk");
 
 __device__ __forceinline__ uint64_t* split_row_table(const PbSplitJob& job, uint32_t* exit) {
     return reinterpret_cast<uint64_t*>(exit + (size_t)job.first_chunk * kPbSplitChunk);
@@ -1260,7 +1067,7 @@ __device__ __forceinline__ const uint8_t* split_stage(const PbSplitJob& job, uin
     back = back < cs ? back : cs;
     const uint32_t rest = job.n - cs;
     const uint32_t fwd = rest < len + kSplitAhead ? rest : len + kSplitAhead;
-    const uint32_t a = stage_aligned(job.msg + cs - back, back + fwd, lds);
+    const uint32_t a = wg::stage16<kRunThreads, 2>(job.msg + cs - back, back + fwd, lds);
     return reinterpret_cast<const uint8_t*>(lds) + a + back;
 }
 
@@ -1311,7 +1118,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_split_spec_kernel(const PbSpli
     __shared__ u32x4 raw[kSplitStage16];
     __shared__ uint32_t nxt[kPbSplitChunk];
     __shared__ uint64_t groups[64];
-    const PbSplitJob job = jobs[split_job_of(jobs, njobs, blockIdx.x, 0)];
+    const PbSplitJob job = jobs[wg::job_of<&PbSplitJob::first_chunk>(jobs, njobs, blockIdx.x)];
     const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbSplitChunk;
     const uint32_t len = job.n - cs < kPbSplitChunk ? job.n - cs : kPbSplitChunk;
@@ -1332,12 +1139,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_split_spec_kernel(const PbSpli
     if (wave == 0) {
         const uint64_t m = groups[lane];
         const uint32_t mine = (uint32_t)__popcll(m);
-        uint32_t incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(incl, off, 64);
-            if (lane >= (uint32_t)off) incl += y;
-        }
+        const uint32_t incl = wg::wave_incl_scan(mine);
         const size_t g = (size_t)blockIdx.x * 64 + lane;
         term_mask[g] = m;
         term_group[g] = incl - mine;
@@ -1358,7 +1160,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_split_spec_kernel(const PbSpli
 __global__ void __launch_bounds__(kRunThreads) pb_split_skip_kernel(const PbSplitJob* __restrict__ jobs, int njobs,
                                                                     const uint32_t* __restrict__ exit,
                                                                     uint32_t* __restrict__ skip, uint32_t hops) {
-    const PbSplitJob job = jobs[split_job_of(jobs, njobs, blockIdx.x, 0)];
+    const PbSplitJob job = jobs[wg::job_of<&PbSplitJob::first_chunk>(jobs, njobs, blockIdx.x)];
     const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbSplitChunk;
     const uint32_t len = job.n - cs < kPbSplitChunk ? job.n - cs : kPbSplitChunk;
     const uint32_t* ex = exit + (size_t)job.first_chunk * kPbSplitChunk;
@@ -1408,7 +1210,7 @@ __global__ void __launch_bounds__(64) pb_split_fill_kernel(const PbSplitJob* __r
                                                            uint32_t nchunks) {
     const uint32_t c = blockIdx.x * 64 + threadIdx.x;
     if (c >= nchunks) return;
-    const PbSplitJob job = jobs[split_job_of(jobs, njobs, c, 0)];
+    const PbSplitJob job = jobs[wg::job_of<&PbSplitJob::first_chunk>(jobs, njobs, c)];
     const uint32_t* ex = exit + (size_t)job.first_chunk * kPbSplitChunk;
     uint32_t pos = land[c];
     for (uint32_t h = 0; h < hops && pos < job.n; ++h) {
@@ -1430,7 +1232,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_split_mark_kernel(const PbSpli
     __shared__ uint64_t starts[64];
     __shared__ uint16_t row_bits[kRunThreads];  // lane t: its 16 offsets; four lanes make a group's mask
     __shared__ uint32_t tally[2];
-    const int j = split_job_of(jobs, njobs, blockIdx.x, 0);
+    const int j = wg::job_of<&PbSplitJob::first_chunk>(jobs, njobs, blockIdx.x);
     const PbSplitJob job = jobs[j];
     const uint32_t t = threadIdx.x;
     const uint32_t ent = entry[blockIdx.x];
@@ -1491,11 +1293,8 @@ __global__ void __launch_bounds__(kRunThreads) pb_split_mark_kernel(const PbSpli
         }
     }
     row_bits[t] = (uint16_t)rows;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        nrows += __shfl_xor(nrows, off, 64);
-        nothers += __shfl_xor(nothers, off, 64);
-    }
+    nrows = wg::wave_sum(nrows);
+    nothers = wg::wave_sum(nothers);
     if ((t & 63) == 0) {
         atomicAdd(&tally[0], nrows);
         atomicAdd(&tally[1], nothers);
@@ -1518,20 +1317,14 @@ __global__ void __launch_bounds__(kRunThreads) pb_split_table_kernel(const PbSpl
                                                                      uint32_t* __restrict__ exit,
                                                                      uint32_t* __restrict__ bad) {
     __shared__ uint32_t before[64];
-    const int j = split_job_of(jobs, njobs, blockIdx.x, 0);
+    const int j = wg::job_of<&PbSplitJob::first_chunk>(jobs, njobs, blockIdx.x);
     const PbSplitJob job = jobs[j];
     if (row_chunk[blockIdx.x + 1] == row_chunk[blockIdx.x]) return;
     const uint32_t t = threadIdx.x, lane = t & 63;
     const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbSplitChunk;
     if (t < 64) {
         const uint32_t mine = (uint32_t)__popcll(row_mask[(size_t)blockIdx.x * 64 + t]);
-        uint32_t incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(incl, off, 64);
-            if (lane >= (uint32_t)off) incl += y;
-        }
-        before[t] = incl - mine;
+        before[t] = wg::wave_incl_scan(mine) - mine;
     }
     __syncthreads();
     const uint64_t m = row_mask[(size_t)blockIdx.x * 64 + (t >> 2)];
@@ -1594,7 +1387,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_split_varint_kernel(const PbSp
                                                                       uint32_t* __restrict__ bad,
                                                                       const int32_t* __restrict__ ok) {
     __shared__ u32x4 raw[kSplitStage16];
-    const int j = split_job_of(jobs, njobs, blockIdx.x, 0);
+    const int j = wg::job_of<&PbSplitJob::first_chunk>(jobs, njobs, blockIdx.x);
     const PbSplitJob job = jobs[j];
     if (!pb_rows::WireIsVarint(job.kind) || (kPlace && !ok[j])) return;
     // the rows that start in this chunk, and the one before them that may reach into it
@@ -1660,7 +1453,7 @@ __global__ void __launch_bounds__(kPbSplitBlockRows) pb_split_rows_kernel(const 
                                                                           uint32_t* __restrict__ row_bias,
                                                                           const int32_t* __restrict__ ok) {
     __shared__ uint32_t wave_tot[kPbSplitBlockRows / 64];
-    const int j = split_job_of(jobs, njobs, blockIdx.x, 1);
+    const int j = wg::job_of<&PbSplitJob::first_rblock>(jobs, njobs, blockIdx.x);
     const PbSplitJob job = jobs[j];
     if (kEnds && !ok[j]) return;
     const uint32_t rows = split_total(row_chunk, job.first_chunk, job.nchunks);
@@ -1677,8 +1470,8 @@ __global__ void __launch_bounds__(kPbSplitBlockRows) pb_split_rows_kernel(const 
             ne = pl / pb_rows::SourceBytes(job.kind);
         }
     }
-    uint32_t before;
-    const uint32_t sum = rows_block_scan(ne, wave_tot, &before);
+    uint32_t sum;
+    uint32_t before = wg::block_excl_scan<(int)kPbSplitBlockRows>(ne, wave_tot, &sum);
     if (!kEnds) {
         if (threadIdx.x == 0) block_sum[blockIdx.x] = sum;
         return;
@@ -1720,7 +1513,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_split_place_kernel(const PbSpl
                                                                      const uint32_t* __restrict__ row_chunk,
                                                                      const uint32_t* __restrict__ block_sum,
                                                                      const int32_t* __restrict__ ok) {
-    const int j = split_job_of(jobs, njobs, blockIdx.x, 2);
+    const int j = wg::job_of<&PbSplitJob::first_ochunk>(jobs, njobs, blockIdx.x);
     const PbSplitJob job = jobs[j];
     if (!ok[j]) return;
     const uint32_t count = split_total(block_sum, job.first_rblock, job.nrblocks);

@@ -104,6 +104,107 @@ def test_run_decode_matches_reference(native, kind, n):
     assert got == want
 
 
+RUN_CHUNK_ELEMS = 2048         # kernels.h kPbRunChunkElems
+RUN_DECODE_CHUNK_BYTES = 4096  # kernels.h kPbRunDecodeChunkBytes
+GUARD = 32
+
+
+def _to_device(raw):
+    return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to("cuda:0")
+
+
+def _phased_slots(buf, sizes_and_phases):
+    """Offsets into buf, one per (size, phase): the slot's address is `phase`
+    mod 16 and GUARD bytes on both sides belong to no other slot."""
+    offs, cursor = [], 0
+    for size, phase in sizes_and_phases:
+        off = cursor + GUARD
+        off += (phase - (buf.data_ptr() + off)) % 16
+        offs.append(off)
+        cursor = off + size + GUARD
+    assert cursor <= buf.numel()
+    return offs
+
+
+def _check_slots(host, offs, wants, what):
+    for k, (off, want) in enumerate(zip(offs, wants)):
+        assert host[off:off + len(want)] == want, (what, k)
+        assert host[off - GUARD:off] == b"\xEE" * GUARD, (what, k, "front guard")
+        assert host[off + len(want):off + len(want) + GUARD] == b"\xEE" * GUARD, (what, k, "back guard")
+
+
+def test_packed_encode_at_every_destination_alignment(native):
+    """device_encode_packed with dst at each of the 16 phases in one call: a
+    varint and a zigzag kind, one element, a chunk less one and a chunk plus
+    one, the bytes of the host reference and nothing outside them. (The
+    binding builds headerless messages: the place pass of the message builder
+    encodes the runs, with pb_run_encode_kernel's varint path.)"""
+    jobs = []
+    for kind in ("int64", "sint32"):
+        code, pk = KINDS[kind]
+        for n in (1, RUN_CHUNK_ELEMS - 1, RUN_CHUNK_ELEMS + 1):
+            vals = _values(kind, n, seed=1000 * code + n)
+            src, want = _to_device(struct.pack("<%d%s" % (n, pk), *vals)), _ref(kind, vals, 0)
+            jobs += [(code, n, phase, src, want) for phase in range(16)]
+    buf = torch.full((sum(len(j[4]) + 2 * GUARD + 16 for j in jobs),), 0xEE, dtype=torch.uint8, device="cuda:0")
+    offs = _phased_slots(buf, [(len(j[4]), j[2]) for j in jobs])
+    torch.cuda.synchronize()  # torch fills/copies run on its own stream
+    res = native.gpu.device_encode_packed([j[3].data_ptr() for j in jobs], [j[1] for j in jobs], [j[0] for j in jobs],
+                                          [buf.data_ptr() + off for off in offs], [len(j[4]) for j in jobs], 0)
+    assert [(buf.data_ptr() + off) % 16 for off in offs] == [j[2] for j in jobs]
+    assert res == [(len(j[4]), 0) for j in jobs]
+    _check_slots(buf.cpu().numpy().tobytes(), offs, [j[4] for j in jobs], "encode")
+
+
+def _payload_of(kind, nbytes, seed, tail=b""):
+    """Values of `kind` whose packed payload is exactly nbytes long and ends
+    with the varint `tail` (the wire value of the last element)."""
+    vals, out = [], bytearray()
+    for v in _values(kind, nbytes, seed):
+        enc = _ref(kind, [v], 0)
+        if len(out) + len(enc) + len(tail) > nbytes:
+            break
+        vals.append(v)
+        out += enc
+    while len(out) + len(tail) < nbytes:  # one-byte varints up to the tail
+        vals.append(1)
+        out += _ref(kind, [1], 0)
+    if tail:
+        wire = sum((b & 0x7F) << (7 * i) for i, b in enumerate(tail))
+        vals.append((wire >> 1) ^ -(wire & 1) if kind.startswith("sint") else wire)
+        out += tail
+    assert len(out) == nbytes and _ref(kind, vals, 0) == bytes(out)
+    return vals, bytes(out)
+
+
+def test_packed_decode_at_every_source_alignment(native):
+    """device_decode_packed with src at each of the 16 phases in one call,
+    the output where torch puts it: runs of one byte, a decode chunk less one
+    and a chunk plus one, the last with a three-byte varint across the chunk
+    edge, so the second chunk decodes it from its staged halo."""
+    jobs = []
+    for kind in ("int64", "sint32"):
+        code, pk = KINDS[kind]
+        for nbytes, tail in ((1, b""), (RUN_DECODE_CHUNK_BYTES - 1, b""), (RUN_DECODE_CHUNK_BYTES + 1, b"\x85\x86\x07")):
+            vals, wire = _payload_of(kind, nbytes, seed=2000 * code + nbytes, tail=tail)
+            want = struct.pack("<%d%s" % (len(vals), pk), *vals)
+            jobs += [(code, phase, wire, want, len(vals)) for phase in range(16)]
+    src = torch.zeros(sum(len(j[2]) + 2 * GUARD + 16 for j in jobs), dtype=torch.uint8, device="cuda:0")
+    soffs = _phased_slots(src, [(len(j[2]), j[1]) for j in jobs])
+    host = bytearray(src.numel())
+    for off, j in zip(soffs, jobs):
+        host[off:off + len(j[2])] = j[2]
+    src.copy_(torch.frombuffer(host, dtype=torch.uint8))
+    out = torch.full((sum(len(j[3]) + 2 * GUARD + 16 for j in jobs),), 0xEE, dtype=torch.uint8, device="cuda:0")
+    ooffs = _phased_slots(out, [(len(j[3]), 0) for j in jobs])
+    torch.cuda.synchronize()  # torch fills/copies run on its own stream
+    res = native.gpu.device_decode_packed([src.data_ptr() + off for off in soffs], [len(j[2]) for j in jobs],
+                                          [j[0] for j in jobs], [out.data_ptr() + off for off in ooffs], 0)
+    assert [(src.data_ptr() + off) % 16 for off in soffs] == [j[1] for j in jobs]
+    assert res == [(j[4], 0) for j in jobs]
+    _check_slots(out.cpu().numpy().tobytes(), ooffs, [j[3] for j in jobs], "decode")
+
+
 def test_run_decode_round_trips_the_encoder(native):
     vals = _values("sint64", 20000, seed=5)
     raw = struct.pack("<20000q", *vals)
