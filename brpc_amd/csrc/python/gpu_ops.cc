@@ -669,6 +669,28 @@ void bind_gpu_ops(py::module_& g) {
               "batched_copy_crc32c");
     }, py::arg("srcs"), py::arg("dsts"), py::arg("lens"), py::arg("out"), py::arg("stream") = 0,
        py::arg("mfma") = true);
+    // The copy engine's launch for -copy_engine_resident=false: out[msg_of[i]]
+    // receives the CRC32C of the message segment i belongs to. msg_of is
+    // non-decreasing in steps of 0 or 1 (consecutive message numbers, as
+    // BatchedCopy builds them); a message of more than 32 segments is refused.
+    g.def("batched_copy_crc32c_messages_launch", [](const std::vector<uintptr_t>& srcs,
+                                                    const std::vector<uintptr_t>& dsts,
+                                                    const std::vector<uint64_t>& lens, const std::vector<int>& msg_of,
+                                                    uintptr_t out, uintptr_t stream, bool mfma) {
+        if (srcs.size() != lens.size() || dsts.size() != lens.size() || msg_of.size() != lens.size())
+            throw std::invalid_argument("size mismatch");
+        for (size_t i = 0; i < msg_of.size(); ++i) {
+            if (msg_of[i] < 0 || (i > 0 && (msg_of[i] < msg_of[i - 1] || msg_of[i] > msg_of[i - 1] + 1)))
+                throw std::invalid_argument("msg_of must be non-negative and rise in steps of 0 or 1");
+        }
+        std::vector<gpu::Segment> segs(lens.size());
+        for (size_t i = 0; i < lens.size(); ++i) segs[i] = gpu::Segment{(const void*)srcs[i], (void*)dsts[i], lens[i]};
+        const int rc = gpu::LaunchBatchedCopyCrc32cMessages(segs.data(), msg_of.data(), (int)segs.size(),
+                                                            (uint32_t*)out, as_stream(stream), nullptr, mfma);
+        if (rc == -2) throw py::value_error("a message has more segments than one launch group holds");
+        check(rc, "batched_copy_crc32c_messages");
+    }, py::arg("srcs"), py::arg("dsts"), py::arg("lens"), py::arg("msg_of"), py::arg("out"), py::arg("stream") = 0,
+       py::arg("mfma") = true);
     g.def("pb_scan_launch", [](uintptr_t buf, uint64_t buf_len, uintptr_t offsets, int64_t n, uint32_t max_fields,
                                uintptr_t fields, uintptr_t nfields, uintptr_t stream) {
         check(gpu::LaunchPbScan((const uint8_t*)buf, buf_len, (const int64_t*)offsets, n, max_fields,

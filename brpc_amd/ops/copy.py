@@ -40,3 +40,31 @@ def batched_copy_crc32c(srcs, dsts, mfma=True):
     native.gpu.batched_copy_crc32c_launch([s.data_ptr() for s in srcs], [d.data_ptr() for d in dsts],
                                           [nbytes(s) for s in srcs], out.data_ptr(), stream_handle(dev), mfma)
     return out.to(torch.int64) & 0xFFFFFFFF
+
+
+def batched_copy_crc32c_messages(srcs, dsts, msg_of, mfma=True):
+    """Fused copy + CRC32C folded per MESSAGE on the device: consecutive
+    segments with equal msg_of[i] (non-decreasing, rising in steps of 0 or 1)
+    are one message, and the result holds the standard CRC32C of each
+    message's concatenated bytes, in order (int64 device tensor). dsts[i] may
+    be None: that segment is only checksummed. A message may have at most 32
+    segments (ValueError beyond). This is the launch the copy engine issues
+    for verified requests that arrive in several blocks."""
+    import torch
+    if len(srcs) != len(dsts) or len(srcs) != len(msg_of):
+        raise ValueError("srcs/dsts/msg_of length mismatch")
+    for s, d in zip(srcs, dsts):
+        require_gpu_tensor(s, "src")
+        if d is not None:
+            require_gpu_tensor(d, "dst")
+            if nbytes(d) < nbytes(s):
+                raise ValueError("destination smaller than source")
+    if not srcs:
+        return None
+    dev = srcs[0].device
+    m0 = int(msg_of[0])
+    out = torch.empty(int(msg_of[-1]) - m0 + 1, dtype=torch.int32, device=dev)
+    native.gpu.batched_copy_crc32c_messages_launch(
+        [s.data_ptr() for s in srcs], [0 if d is None else d.data_ptr() for d in dsts], [nbytes(s) for s in srcs],
+        [int(m) - m0 for m in msg_of], out.data_ptr(), stream_handle(dev), mfma)
+    return out.to(torch.int64) & 0xFFFFFFFF
