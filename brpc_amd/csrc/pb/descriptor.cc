@@ -3,12 +3,14 @@
 #include <string>
 
 #include "pb/message.h"
+#include "pb/plan.h"
 
 namespace mrpc {
 namespace pb {
 
 Descriptor::~Descriptor() {
     if (owns_prototype) delete prototype;
+    DeleteCodecPlan(codec_plan.load(std::memory_order_acquire));
 }
 
 const char* FieldTypeName(FieldType t) {
@@ -95,6 +97,8 @@ const EnumValueDescriptor* EnumDescriptor::FindValueByName(const std::string& s)
 }
 
 void Descriptor::BuildIndex() {
+    // fields or layout changed: a plan compiled from the earlier ones is stale
+    DeleteCodecPlan(codec_plan.exchange(nullptr, std::memory_order_acq_rel));
     _by_number.clear();
     _by_number_sparse.clear();
     _by_name.clear();

@@ -21,6 +21,7 @@ class Descriptor;
 class EnumDescriptor;
 class FileDescriptor;
 class ServiceDescriptor;
+struct CodecPlan;
 
 enum class FieldType : uint8_t {
     DOUBLE = 1, FLOAT = 2, INT64 = 3, UINT64 = 4, INT32 = 5, FIXED64 = 6, FIXED32 = 7, BOOL = 8,
@@ -117,6 +118,9 @@ public:
     // Generated mcpack codec of this message (mcpack::MessageHandler*,
     // installed by `mrpc_protoc --mcpack_out` output at static init).
     std::atomic<const void*> mcpack_handler{nullptr};
+    // The codec's compiled view of this type (pb/plan.h): built on first
+    // codec use, published once, freed with the descriptor.
+    mutable std::atomic<const CodecPlan*> codec_plan{nullptr};
     Descriptor() = default;
     Descriptor(const Descriptor&) = delete;
     Descriptor& operator=(const Descriptor&) = delete;

@@ -21,114 +21,13 @@ template <typename T>
 inline const T& cref(const Message& m, const FieldDescriptor* f) {
     return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(&m) + f->offset);
 }
-inline uint32_t* has_bits(Message* m) {
-    return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(m) + m->GetDescriptor()->has_bits_offset);
+// The has words of the message that `f` belongs to: found through the field's
+// own descriptor, so the slow paths make no virtual call per field either.
+inline uint32_t* has_bits(Message* m, const FieldDescriptor* f) {
+    return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(m) + f->containing_type->has_bits_offset);
 }
-inline const uint32_t* has_bits(const Message& m) {
-    return reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(&m) + m.GetDescriptor()->has_bits_offset);
-}
-
-WireType wire_type_of(FieldType t) {
-    switch (t) {
-    case FieldType::DOUBLE:
-    case FieldType::FIXED64:
-    case FieldType::SFIXED64: return WIRETYPE_FIXED64;
-    case FieldType::FLOAT:
-    case FieldType::FIXED32:
-    case FieldType::SFIXED32: return WIRETYPE_FIXED32;
-    case FieldType::STRING:
-    case FieldType::BYTES:
-    case FieldType::MESSAGE: return WIRETYPE_LENGTH_DELIMITED;
-    case FieldType::GROUP: return WIRETYPE_START_GROUP;
-    default: return WIRETYPE_VARINT;
-    }
-}
-
-// Size of one scalar element (no tag).
-size_t scalar_size(FieldType t, const void* p) {
-    switch (t) {
-    case FieldType::DOUBLE:
-    case FieldType::FIXED64:
-    case FieldType::SFIXED64: return 8;
-    case FieldType::FLOAT:
-    case FieldType::FIXED32:
-    case FieldType::SFIXED32: return 4;
-    case FieldType::BOOL: return 1;
-    case FieldType::INT32:
-    case FieldType::ENUM: return int32_size(*(const int32_t*)p);
-    case FieldType::SINT32: return varint_size(zigzag32(*(const int32_t*)p));
-    case FieldType::UINT32: return varint_size(*(const uint32_t*)p);
-    case FieldType::INT64: return varint_size((uint64_t)*(const int64_t*)p);
-    case FieldType::SINT64: return varint_size(zigzag64(*(const int64_t*)p));
-    case FieldType::UINT64: return varint_size(*(const uint64_t*)p);
-    default: return 0;
-    }
-}
-
-uint8_t* write_scalar(uint8_t* o, FieldType t, const void* p) {
-    switch (t) {
-    case FieldType::DOUBLE:
-    case FieldType::FIXED64:
-    case FieldType::SFIXED64: return write_fixed64(o, *(const uint64_t*)p);
-    case FieldType::FLOAT:
-    case FieldType::FIXED32:
-    case FieldType::SFIXED32: return write_fixed32(o, *(const uint32_t*)p);
-    case FieldType::BOOL: *o++ = (*(const uint8_t*)p) ? 1 : 0; return o;
-    case FieldType::INT32:
-    case FieldType::ENUM: return write_varint(o, (uint64_t)(int64_t)*(const int32_t*)p);
-    case FieldType::SINT32: return write_varint(o, zigzag32(*(const int32_t*)p));
-    case FieldType::UINT32: return write_varint(o, *(const uint32_t*)p);
-    case FieldType::INT64: return write_varint(o, (uint64_t)*(const int64_t*)p);
-    case FieldType::SINT64: return write_varint(o, zigzag64(*(const int64_t*)p));
-    case FieldType::UINT64: return write_varint(o, *(const uint64_t*)p);
-    default: return o;
-    }
-}
-
-// Payload bytes of elements [0, n) of a repeated scalar field in its vector
-// layout: typed, branch-free loops (varint size = (bit width * 9 + 64) / 64)
-// instead of a per-element switch and loop; packed runs of 10^4..10^5
-// elements are sized twice per serialization.
-inline size_t vsize64(uint64_t v) { return (size_t)(((63 - __builtin_clzll(v | 1)) * 9 + 73) >> 6); }
-size_t repeated_payload_bytes(FieldType t, const char* data, size_t n) {
-    size_t s = 0;
-    switch (t) {
-    case FieldType::DOUBLE:
-    case FieldType::FIXED64:
-    case FieldType::SFIXED64: return 8 * n;
-    case FieldType::FLOAT:
-    case FieldType::FIXED32:
-    case FieldType::SFIXED32: return 4 * n;
-    case FieldType::BOOL: return n;
-    case FieldType::INT32:
-    case FieldType::ENUM: {
-        const int32_t* v = reinterpret_cast<const int32_t*>(data);
-        for (size_t i = 0; i < n; ++i) s += vsize64((uint64_t)(int64_t)v[i]);
-        return s;
-    }
-    case FieldType::SINT32: {
-        const int32_t* v = reinterpret_cast<const int32_t*>(data);
-        for (size_t i = 0; i < n; ++i) s += vsize64(zigzag32(v[i]));
-        return s;
-    }
-    case FieldType::UINT32: {
-        const uint32_t* v = reinterpret_cast<const uint32_t*>(data);
-        for (size_t i = 0; i < n; ++i) s += vsize64(v[i]);
-        return s;
-    }
-    case FieldType::INT64:
-    case FieldType::UINT64: {
-        const uint64_t* v = reinterpret_cast<const uint64_t*>(data);
-        for (size_t i = 0; i < n; ++i) s += vsize64(v[i]);
-        return s;
-    }
-    case FieldType::SINT64: {
-        const int64_t* v = reinterpret_cast<const int64_t*>(data);
-        for (size_t i = 0; i < n; ++i) s += vsize64(zigzag64(v[i]));
-        return s;
-    }
-    default: return 0;
-    }
+inline const uint32_t* has_bits(const Message& m, const FieldDescriptor* f) {
+    return reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(&m) + f->containing_type->has_bits_offset);
 }
 
 size_t elem_bytes(FieldType t) {
@@ -211,16 +110,16 @@ bool is_default_scalar(const Message& m, const FieldDescriptor* f) {
 
 bool field_present(const Message& m, const FieldDescriptor* f) {
     if (f->cpp_type() == CppType::MESSAGE) return cref<Message*>(m, f) != nullptr;
-    if (f->has_bit >= 0) return (has_bits(m)[f->has_bit >> 5] >> (f->has_bit & 31)) & 1;
+    if (f->has_bit >= 0) return (has_bits(m, f)[f->has_bit >> 5] >> (f->has_bit & 31)) & 1;
     return !is_default_scalar(m, f);
 }
 
 void set_has(Message* m, const FieldDescriptor* f) {
-    if (f->has_bit >= 0) has_bits(m)[f->has_bit >> 5] |= (1u << (f->has_bit & 31));
+    if (f->has_bit >= 0) has_bits(m, f)[f->has_bit >> 5] |= (1u << (f->has_bit & 31));
 }
 
 void clear_has(Message* m, const FieldDescriptor* f) {
-    if (f->has_bit >= 0) has_bits(m)[f->has_bit >> 5] &= ~(1u << (f->has_bit & 31));
+    if (f->has_bit >= 0) has_bits(m, f)[f->has_bit >> 5] &= ~(1u << (f->has_bit & 31));
 }
 
 void set_scalar_default(Message* m, const FieldDescriptor* f) {
@@ -254,276 +153,11 @@ void clear_repeated(Message* m, const FieldDescriptor* f) {
     }
 }
 
-template <typename T>
-void push_raw(Message* m, const FieldDescriptor* f, T v) {
-    ref<std::vector<T>>(m, f).push_back(v);
-}
-
-// Store a decoded varint/fixed value into field f (singular or repeated).
-void store_number(Message* m, const FieldDescriptor* f, uint64_t raw) {
-    const bool rep = f->is_repeated();
-    switch (f->type) {
-    case FieldType::INT32:
-    case FieldType::ENUM:
-    case FieldType::SFIXED32: {
-        int32_t v = (int32_t)raw;
-        if (rep) push_raw<int32_t>(m, f, v); else ref<int32_t>(m, f) = v;
-        break;
-    }
-    case FieldType::SINT32: {
-        int32_t v = unzigzag32((uint32_t)raw);
-        if (rep) push_raw<int32_t>(m, f, v); else ref<int32_t>(m, f) = v;
-        break;
-    }
-    case FieldType::UINT32:
-    case FieldType::FIXED32: {
-        uint32_t v = (uint32_t)raw;
-        if (rep) push_raw<uint32_t>(m, f, v); else ref<uint32_t>(m, f) = v;
-        break;
-    }
-    case FieldType::INT64:
-    case FieldType::SFIXED64: {
-        int64_t v = (int64_t)raw;
-        if (rep) push_raw<int64_t>(m, f, v); else ref<int64_t>(m, f) = v;
-        break;
-    }
-    case FieldType::SINT64: {
-        int64_t v = unzigzag64(raw);
-        if (rep) push_raw<int64_t>(m, f, v); else ref<int64_t>(m, f) = v;
-        break;
-    }
-    case FieldType::UINT64:
-    case FieldType::FIXED64: {
-        if (rep) push_raw<uint64_t>(m, f, raw); else ref<uint64_t>(m, f) = raw;
-        break;
-    }
-    case FieldType::BOOL: {
-        uint8_t v = raw != 0;
-        if (rep) push_raw<uint8_t>(m, f, v); else ref<bool>(m, f) = v;
-        break;
-    }
-    case FieldType::FLOAT: {
-        uint32_t b = (uint32_t)raw;
-        float v;
-        memcpy(&v, &b, 4);
-        if (rep) push_raw<float>(m, f, v); else ref<float>(m, f) = v;
-        break;
-    }
-    case FieldType::DOUBLE: {
-        double v;
-        memcpy(&v, &raw, 8);
-        if (rep) push_raw<double>(m, f, v); else ref<double>(m, f) = v;
-        break;
-    }
-    default: break;
-    }
-    if (!rep) {
-        if (f->oneof_index >= 0) ClearOneofSiblings(m, f);
-        set_has(m, f);
-    }
-}
-
-bool read_number(CodedInput* in, FieldType t, uint64_t* out) {
-    switch (wire_type_of(t)) {
-    case WIRETYPE_VARINT: return in->read_varint(out);
-    case WIRETYPE_FIXED32: {
-        uint32_t v;
-        if (!in->read_fixed32(&v)) return false;
-        *out = v;
-        return true;
-    }
-    case WIRETYPE_FIXED64: return in->read_fixed64(out);
-    default: return false;
-    }
-}
-
-bool parse_message(Message* m, CodedInput* in);
-
-// Packed payload p[0, len) appended to a repeated scalar field in bulk:
-// fixed-width types are one memcpy, varints are counted first (one pass
-// over the terminator bits, so the vector grows once) and decoded by a
-// typed loop instead of a per-element switch. Same results and the same
-// failures as the element-wise path.
-template <typename T, typename Conv>
-bool bulk_varints(Message* m, const FieldDescriptor* f, const uint8_t* p, size_t len, Conv conv) {
-    size_t n = 0;
-    for (size_t i = 0; i < len; ++i) n += (p[i] >> 7) ^ 1;
-    auto& vec = ref<std::vector<T>>(m, f);
-    const size_t base = vec.size();
-    vec.resize(base + n);
-    T* out = vec.data() + base;
-    CodedInput in(p, len);
-    for (size_t k = 0; k < n; ++k) {
-        uint64_t v;
-        if (!in.read_varint(&v)) {
-            vec.resize(base + k);
-            return false;
-        }
-        out[k] = conv(v);
-    }
-    return in.at_limit();
-}
-
-template <typename T>
-bool bulk_fixed(Message* m, const FieldDescriptor* f, const uint8_t* p, size_t len) {
-    if (len % sizeof(T)) return false;
-    auto& vec = ref<std::vector<T>>(m, f);
-    const size_t base = vec.size();
-    vec.resize(base + len / sizeof(T));
-    memcpy(vec.data() + base, p, len);
-    return true;
-}
-
-bool parse_packed(Message* m, const FieldDescriptor* f, const uint8_t* p, size_t len) {
-    switch (f->type) {
-    case FieldType::INT32:
-    case FieldType::ENUM: return bulk_varints<int32_t>(m, f, p, len, [](uint64_t v) { return (int32_t)v; });
-    case FieldType::SINT32:
-        return bulk_varints<int32_t>(m, f, p, len, [](uint64_t v) { return unzigzag32((uint32_t)v); });
-    case FieldType::UINT32: return bulk_varints<uint32_t>(m, f, p, len, [](uint64_t v) { return (uint32_t)v; });
-    case FieldType::INT64: return bulk_varints<int64_t>(m, f, p, len, [](uint64_t v) { return (int64_t)v; });
-    case FieldType::SINT64: return bulk_varints<int64_t>(m, f, p, len, [](uint64_t v) { return unzigzag64(v); });
-    case FieldType::UINT64: return bulk_varints<uint64_t>(m, f, p, len, [](uint64_t v) { return v; });
-    case FieldType::BOOL: return bulk_varints<uint8_t>(m, f, p, len, [](uint64_t v) { return (uint8_t)(v != 0); });
-    case FieldType::FIXED32:
-    case FieldType::SFIXED32: return f->cpp_type() == CppType::UINT32 ? bulk_fixed<uint32_t>(m, f, p, len)
-                                                                      : bulk_fixed<int32_t>(m, f, p, len);
-    case FieldType::FIXED64: return bulk_fixed<uint64_t>(m, f, p, len);
-    case FieldType::SFIXED64: return bulk_fixed<int64_t>(m, f, p, len);
-    case FieldType::FLOAT: return bulk_fixed<float>(m, f, p, len);
-    case FieldType::DOUBLE: return bulk_fixed<double>(m, f, p, len);
-    default: return false;
-    }
-}
-
-bool parse_field(Message* m, const FieldDescriptor* f, uint32_t tag, CodedInput* in) {
-    const WireType wt = (WireType)(tag & 7);
-    const WireType expected = wire_type_of(f->type);
-    if (f->is_repeated() && f->is_packable() && wt == WIRETYPE_LENGTH_DELIMITED) {
-        uint64_t len;
-        const uint8_t* p;
-        if (!in->read_varint(&len) || !in->read_bytes((size_t)len, &p)) return false;
-        return parse_packed(m, f, p, (size_t)len);
-    }
-    if (wt != expected) {
-        // Mismatched wire type: keep as unknown field (protobuf semantics).
-        return in->skip_field(tag, m->mutable_unknown_fields());
-    }
-    switch (f->cpp_type()) {
-    case CppType::STRING: {
-        uint64_t len;
-        const uint8_t* d;
-        if (!in->read_varint(&len) || !in->read_bytes((size_t)len, &d)) return false;
-        if (f->is_repeated()) {
-            ref<std::vector<std::string>>(m, f).emplace_back((const char*)d, (size_t)len);
-        } else {
-            if (f->oneof_index >= 0) ClearOneofSiblings(m, f);
-            ref<std::string>(m, f).assign((const char*)d, (size_t)len);
-            set_has(m, f);
-        }
-        return true;
-    }
-    case CppType::MESSAGE: {
-        if (f->type == FieldType::GROUP) return in->skip_field(tag, m->mutable_unknown_fields());
-        uint64_t len;
-        const uint8_t* old;
-        if (!in->read_varint(&len) || !in->push_limit((size_t)len, &old)) return false;
-        Message* sub = f->is_repeated() ? Reflection::AddMessage(m, f) : Reflection::MutableMessage(m, f);
-        if (!in->inc_depth()) return false;
-        if (!parse_message(sub, in)) return false;
-        in->dec_depth();
-        if (!in->at_limit()) return false;
-        in->pop_limit(old);
-        return true;
-    }
-    default: {
-        uint64_t v;
-        if (!read_number(in, f->type, &v)) return false;
-        store_number(m, f, v);
-        return true;
-    }
-    }
-}
-
-bool parse_message(Message* m, CodedInput* in) { return m->MergePartialFromCodedInput(in); }
-
 }  // namespace
 
 // ---------------------------------------------------------------- Message
 
 Message::~Message() {}
-
-void Message::Clear() {
-    const Descriptor* d = GetDescriptor();
-    for (const FieldDescriptor& fd : d->fields) {
-        const FieldDescriptor* f = &fd;
-        if (f->is_repeated()) {
-            clear_repeated(this, f);
-        } else if (f->cpp_type() == CppType::MESSAGE) {
-            Message*& sub = ref<Message*>(this, f);
-            if (sub) sub->Clear();
-            delete sub;
-            sub = nullptr;
-        } else {
-            set_scalar_default(this, f);
-        }
-    }
-    uint32_t* hb = has_bits(this);
-    for (uint32_t i = 0; i < (d->num_has_bits + 31) / 32; ++i) hb[i] = 0;
-    _unknown.clear();
-}
-
-size_t Message::ByteSizeLong() const {
-    const Descriptor* d = GetDescriptor();
-    size_t total = 0;
-    for (const FieldDescriptor& fd : d->fields) {
-        const FieldDescriptor* f = &fd;
-        const size_t tag_size = varint_size(make_tag(f->number, WIRETYPE_VARINT));
-        if (f->is_repeated()) {
-            switch (f->cpp_type()) {
-            case CppType::STRING: {
-                const auto& v = cref<std::vector<std::string>>(*this, f);
-                for (const auto& s : v) total += tag_size + varint_size(s.size()) + s.size();
-                break;
-            }
-            case CppType::MESSAGE: {
-                const auto& v = cref<RepeatedPtrBase>(*this, f);
-                for (int i = 0; i < v.size(); ++i) {
-                    size_t s = v.Get(i)->ByteSizeLong();
-                    total += tag_size + varint_size(s) + s;
-                }
-                break;
-            }
-            default: {
-                RawVec rv = raw_repeated(*this, f);
-                if (rv.n == 0) break;
-                const size_t data = repeated_payload_bytes(f->type, rv.data, rv.n);
-                if (f->packed) total += tag_size + varint_size(data) + data;
-                else total += tag_size * rv.n + data;
-            }
-            }
-            continue;
-        }
-        if (!field_present(*this, f)) continue;
-        switch (f->cpp_type()) {
-        case CppType::STRING: {
-            const auto& s = cref<std::string>(*this, f);
-            total += tag_size + varint_size(s.size()) + s.size();
-            break;
-        }
-        case CppType::MESSAGE: {
-            size_t s = cref<Message*>(*this, f)->ByteSizeLong();
-            total += tag_size + varint_size(s) + s;
-            break;
-        }
-        default:
-            total += tag_size + scalar_size(f->type, reinterpret_cast<const char*>(this) + f->offset);
-        }
-    }
-    total += _unknown.size();
-    _cached_size = (int)total;
-    return total;
-}
 
 const void* Reflection::RepeatedScalarData(const Message& m, const FieldDescriptor* f, size_t* n, size_t* eb) {
     *n = 0;
@@ -533,145 +167,6 @@ const void* Reflection::RepeatedScalarData(const Message& m, const FieldDescript
     *n = rv.n;
     *eb = elem_bytes(f->type);
     return rv.data;
-}
-
-static thread_local PackedRunSink* tls_run_sink = nullptr;
-
-PackedRunSink* SetThreadPackedRunSink(PackedRunSink* sink) {
-    PackedRunSink* prev = tls_run_sink;
-    tls_run_sink = sink;
-    return prev;
-}
-
-bool IsVarintFieldType(FieldType t) {
-    switch (t) {
-    case FieldType::INT32:
-    case FieldType::ENUM:
-    case FieldType::SINT32:
-    case FieldType::UINT32:
-    case FieldType::INT64:
-    case FieldType::SINT64:
-    case FieldType::UINT64:
-    case FieldType::BOOL: return true;
-    default: return false;
-    }
-}
-
-void EncodePackedRunOnHost(const PackedRun& run) {
-    uint8_t* o = run.dst;
-    const char* v = static_cast<const char*>(run.values);
-    for (size_t i = 0; i < run.n; ++i) o = write_scalar(o, run.type, v + i * run.elem_bytes);
-}
-
-uint8_t* Message::SerializeWithCachedSizesToArray(uint8_t* o) const {
-    const Descriptor* d = GetDescriptor();
-    for (const FieldDescriptor& fd : d->fields) {
-        const FieldDescriptor* f = &fd;
-        if (f->is_repeated()) {
-            switch (f->cpp_type()) {
-            case CppType::STRING: {
-                for (const auto& s : cref<std::vector<std::string>>(*this, f)) {
-                    o = write_tag(o, f->number, WIRETYPE_LENGTH_DELIMITED);
-                    o = write_varint(o, s.size());
-                    memcpy(o, s.data(), s.size());
-                    o += s.size();
-                }
-                break;
-            }
-            case CppType::MESSAGE: {
-                const auto& v = cref<RepeatedPtrBase>(*this, f);
-                for (int i = 0; i < v.size(); ++i) {
-                    const Message* sub = v.Get(i);
-                    o = write_tag(o, f->number, WIRETYPE_LENGTH_DELIMITED);
-                    o = write_varint(o, (uint64_t)sub->GetCachedSize());
-                    o = sub->SerializeWithCachedSizesToArray(o);
-                }
-                break;
-            }
-            default: {
-                RawVec rv = raw_repeated(*this, f);
-                if (rv.n == 0) break;
-                const size_t eb = elem_bytes(f->type);
-                PackedRunSink* sink = tls_run_sink;
-                if (f->packed && sink && rv.n >= sink->min_elems() && IsVarintFieldType(f->type)) {
-                    PackedRun run;
-                    run.values = rv.data;
-                    run.n = rv.n;
-                    run.elem_bytes = eb;
-                    run.type = f->type;
-                    run.chunk_bytes.reserve((rv.n + kPackedRunChunkElems - 1) / kPackedRunChunkElems);
-                    size_t data = 0;
-                    for (size_t c = 0; c < rv.n; c += kPackedRunChunkElems) {
-                        const size_t e = std::min(rv.n, c + kPackedRunChunkElems);
-                        const size_t cb = repeated_payload_bytes(f->type, rv.data + c * eb, e - c);
-                        run.chunk_bytes.push_back((uint32_t)cb);
-                        data += cb;
-                    }
-                    o = write_tag(o, f->number, WIRETYPE_LENGTH_DELIMITED);
-                    o = write_varint(o, data);
-                    run.dst = o;
-                    run.bytes = data;
-                    o += data;
-                    sink->Take(std::move(run));
-                } else if (f->packed) {
-                    const size_t data = repeated_payload_bytes(f->type, rv.data, rv.n);
-                    o = write_tag(o, f->number, WIRETYPE_LENGTH_DELIMITED);
-                    o = write_varint(o, data);
-                    for (size_t i = 0; i < rv.n; ++i) o = write_scalar(o, f->type, rv.data + i * eb);
-                } else {
-                    const WireType wt = wire_type_of(f->type);
-                    for (size_t i = 0; i < rv.n; ++i) {
-                        o = write_tag(o, f->number, wt);
-                        o = write_scalar(o, f->type, rv.data + i * eb);
-                    }
-                }
-            }
-            }
-            continue;
-        }
-        if (!field_present(*this, f)) continue;
-        switch (f->cpp_type()) {
-        case CppType::STRING: {
-            const auto& s = cref<std::string>(*this, f);
-            o = write_tag(o, f->number, WIRETYPE_LENGTH_DELIMITED);
-            o = write_varint(o, s.size());
-            memcpy(o, s.data(), s.size());
-            o += s.size();
-            break;
-        }
-        case CppType::MESSAGE: {
-            const Message* sub = cref<Message*>(*this, f);
-            o = write_tag(o, f->number, WIRETYPE_LENGTH_DELIMITED);
-            o = write_varint(o, (uint64_t)sub->GetCachedSize());
-            o = sub->SerializeWithCachedSizesToArray(o);
-            break;
-        }
-        default:
-            o = write_tag(o, f->number, wire_type_of(f->type));
-            o = write_scalar(o, f->type, reinterpret_cast<const char*>(this) + f->offset);
-        }
-    }
-    if (!_unknown.empty()) {
-        memcpy(o, _unknown.data(), _unknown.size());
-        o += _unknown.size();
-    }
-    return o;
-}
-
-bool Message::MergePartialFromCodedInput(CodedInput* in) {
-    const Descriptor* d = GetDescriptor();
-    for (;;) {
-        const uint32_t tag = in->read_tag();
-        if (tag == 0) return true;
-        if (tag == 0xFFFFFFFFu || (tag >> 3) == 0) return false;
-        if ((tag & 7) == WIRETYPE_END_GROUP) return false;
-        const FieldDescriptor* f = d->FindFieldByNumber((int)(tag >> 3));
-        if (!f) {
-            if (!in->skip_field(tag, &_unknown)) return false;
-            continue;
-        }
-        if (!parse_field(this, f, tag, in)) return false;
-    }
 }
 
 static bool is_initialized_impl(const Message& m, std::string* missing, const std::string& prefix) {
@@ -707,8 +202,6 @@ static bool is_initialized_impl(const Message& m, std::string* missing, const st
     }
     return ok;
 }
-
-bool Message::IsInitialized() const { return is_initialized_impl(*this, nullptr, ""); }
 
 std::string Message::InitializationErrorString() const {
     std::string s;
@@ -819,97 +312,6 @@ bool Message::ParseFromBuf(const Buf& in) {
     tmp.resize(in.size());
     in.copy_to(&tmp[0], in.size());
     return ParseFromArray(tmp.data(), tmp.size());
-}
-
-namespace {
-template <typename T>
-void append_elems(Message* m, const FieldDescriptor* f, const void* v, size_t n) {
-    const T* p = static_cast<const T*>(v);
-    auto& vec = ref<std::vector<T>>(m, f);
-    vec.insert(vec.end(), p, p + n);
-}
-void append_decoded(Message* m, const FieldDescriptor* f, const void* v, size_t n) {
-    switch (f->cpp_type()) {
-    case CppType::BOOL: append_elems<uint8_t>(m, f, v, n); break;
-    case CppType::INT32:
-    case CppType::ENUM: append_elems<int32_t>(m, f, v, n); break;
-    case CppType::UINT32: append_elems<uint32_t>(m, f, v, n); break;
-    case CppType::INT64: append_elems<int64_t>(m, f, v, n); break;
-    case CppType::UINT64: append_elems<uint64_t>(m, f, v, n); break;
-    default: break;
-    }
-}
-}  // namespace
-
-bool Message::MergeFromFieldTable(const uint8_t* data, size_t size, const uint64_t* fields, int nfields,
-                                  PackedRunDecoder* decoder) {
-    const Descriptor* d = GetDescriptor();
-    // large packed varint runs go to the decoder first, all in one call
-    std::vector<PackedRunIn> runs;
-    std::vector<int> run_of;  // field row -> runs index (or -1)
-    if (decoder) {
-        const size_t min = std::max<size_t>(1, decoder->min_bytes());
-        for (int i = 0; i < nfields; ++i) {
-            const uint64_t tag = fields[2 * i], v = fields[2 * i + 1];
-            if ((tag & 7) != WIRETYPE_LENGTH_DELIMITED || (v & 0xFFFFFFFFu) < min) continue;
-            const FieldDescriptor* f = d->FindFieldByNumber((int)(tag >> 3));
-            if (!f || !f->is_repeated() || !f->is_packable() || !IsVarintFieldType(f->type)) continue;
-            const size_t off = (size_t)(v >> 32), len = (size_t)(v & 0xFFFFFFFFu);
-            if (off > size || len > size - off) return false;
-            if (run_of.empty()) run_of.assign(nfields, -1);
-            run_of[i] = (int)runs.size();
-            PackedRunIn r;
-            r.p = data + off;
-            r.len = len;
-            r.type = f->type;
-            r.elem_bytes = elem_bytes(f->type);
-            runs.push_back(r);
-        }
-        if (!runs.empty()) decoder->Decode(&runs);
-    }
-    for (int i = 0; i < nfields; ++i) {
-        if (!run_of.empty() && run_of[i] >= 0 && runs[run_of[i]].values) {
-            const PackedRunIn& r = runs[run_of[i]];
-            append_decoded(this, d->FindFieldByNumber((int)(fields[2 * i] >> 3)), r.values, r.count);
-            continue;
-        }
-        const uint64_t tag = fields[2 * i], v = fields[2 * i + 1];
-        const WireType wt = (WireType)(tag & 7);
-        const FieldDescriptor* f = d->FindFieldByNumber((int)(tag >> 3));
-        if (!f || f->type == FieldType::GROUP) return false;
-        if (wt != WIRETYPE_LENGTH_DELIMITED) {
-            if (wt != wire_type_of(f->type)) return false;
-            store_number(this, f, v);
-            continue;
-        }
-        const size_t off = (size_t)(v >> 32), len = (size_t)(v & 0xFFFFFFFFu);
-        if (off > size || len > size - off) return false;
-        const uint8_t* p = data + off;
-        if (f->is_repeated() && f->is_packable()) {
-            if (!parse_packed(this, f, p, len)) return false;
-            continue;
-        }
-        switch (f->cpp_type()) {
-        case CppType::STRING:
-            if (f->is_repeated()) {
-                ref<std::vector<std::string>>(this, f).emplace_back((const char*)p, len);
-            } else {
-                if (f->oneof_index >= 0) ClearOneofSiblings(this, f);
-                ref<std::string>(this, f).assign((const char*)p, len);
-                set_has(this, f);
-            }
-            break;
-        case CppType::MESSAGE: {
-            Message* sub = f->is_repeated() ? Reflection::AddMessage(this, f) : Reflection::MutableMessage(this, f);
-            CodedInput in(p, len);
-            if (!parse_message(sub, &in) || !in.at_limit()) return false;
-            break;
-        }
-        default:
-            return false;  // a scalar field sent length-delimited but not packable
-        }
-    }
-    return true;
 }
 
 // ---------------------------------------------------------------- text format

@@ -67,9 +67,13 @@ public:
 
     const std::string& unknown_fields() const { return _unknown; }
     std::string* mutable_unknown_fields() { return &_unknown; }
+    // True for mrpc::SerializedRequest alone (rpc/serialized_request.h):
+    // the serialize path of every RPC asks, so it is a load, not a cast.
+    bool is_serialized_request() const { return _serialized_request; }
 
 protected:
     mutable int _cached_size;
+    bool _serialized_request = false;  // in the padding after _cached_size
     std::string _unknown;
 };
 

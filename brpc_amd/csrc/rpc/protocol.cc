@@ -105,8 +105,8 @@ bool ParsePbFromString(pb::Message* msg, const std::string& s) {
 }
 
 bool SerializeAsCompressedData(const pb::Message& msg, Buf* buf, CompressType type) {
-    if (const SerializedRequest* sr = dynamic_cast<const SerializedRequest*>(&msg)) {
-        buf->append(sr->serialized_data());  // already encoded with `type`
+    if (msg.is_serialized_request()) {
+        buf->append(static_cast<const SerializedRequest&>(msg).serialized_data());  // already encoded with `type`
         return true;
     }
     if (type == COMPRESS_TYPE_NONE) return msg.SerializeToBuf(buf);

@@ -11,6 +11,7 @@ namespace mrpc {
 
 class SerializedRequest : public pb::Message {
 public:
+    SerializedRequest() { _serialized_request = true; }
     const pb::Descriptor* GetDescriptor() const override { return OpaqueDescriptor("mrpc.SerializedRequest"); }
     pb::Message* New() const override { return new SerializedRequest; }
     void Clear() override { _data.clear(); }

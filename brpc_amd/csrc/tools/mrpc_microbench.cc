@@ -7,7 +7,7 @@
 // docs/en/iobuf.md:101-103) and a contended atomic fetch_add (~700 ns,
 // docs/en/atomic_instructions.md:23). One JSON line per measurement.
 //
-//   build/bin/mrpc_microbench [--seconds S] [--threads 1,2,4,8,16]
+//   build/bin/mrpc_microbench [--seconds S] [--threads 1,2,4,8,16] [--only pb]
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -26,6 +27,8 @@
 #include "base/time.h"
 #include "fiber/fiber.h"
 #include "fiber/sync.h"
+#include "mrpc/proto/echo.pb.h"
+#include "mrpc/proto/rpc_meta.pb.h"
 #include "var/reducer.h"
 
 using namespace mrpc;
@@ -294,9 +297,79 @@ void bench_timer() {
              (double)(t1 - t0) / kN, (double)(t2 - t1) / kN, (long long)g_fired.load()));
 }
 
+// ---------------------------------------------------------------- pb codec
+// The four messages every 32 B baidu_std echo encodes and decodes, filled
+// as that path fills them, and one wide case (16384 packed ids): ns per
+// serialize (IsInitialized + SerializeToBuf), per ParseFromArray, and per
+// Clear of a parsed message. `--only pb` runs this section alone.
+template <typename F>
+double ns_per_op(F&& op) {
+    for (int i = 0; i < 200; ++i) op();
+    int64_t n = 0;
+    const int64_t t0 = monotonic_ns(), end = t0 + (int64_t)(g_seconds * 1e9 / 4);
+    int64_t t1 = t0;
+    while (t1 < end) {
+        for (int i = 0; i < 64; ++i) op();
+        n += 64;
+        t1 = monotonic_ns();
+    }
+    return (double)(t1 - t0) / (double)n;
+}
+
+void bench_pb_message(const char* name, const pb::Message& filled) {
+    const std::string wire = filled.SerializeAsString();
+    bool ok = true;
+    const double ser = ns_per_op([&] {
+        Buf out;
+        ok &= filled.IsInitialized() && filled.SerializeToBuf(&out);
+    });
+    std::unique_ptr<pb::Message> m(filled.New());
+    const double parse = ns_per_op([&] { ok &= m->ParseFromArray(wire.data(), wire.size()); });
+    // Clear: a batch of parsed messages, only the Clear calls inside the clock
+    const int kBatch = wire.size() > 4096 ? 8 : 256;
+    std::vector<std::unique_ptr<pb::Message>> batch;
+    for (int i = 0; i < kBatch; ++i) batch.emplace_back(filled.New());
+    int64_t clear_ns = 0, cleared = 0;
+    const int64_t end = monotonic_ns() + (int64_t)(g_seconds * 1e9 / 4);
+    while (monotonic_ns() < end) {
+        for (auto& b : batch) ok &= b->ParseFromArray(wire.data(), wire.size());
+        const int64_t t0 = monotonic_ns();
+        for (auto& b : batch) b->Clear();
+        clear_ns += monotonic_ns() - t0;
+        cleared += kBatch;
+    }
+    emit(fmt("{\"bench\": \"pb\", \"message\": \"%s\", \"wire_bytes\": %zu, \"serialize_ns\": %.1f, \"parse_ns\": %.1f, "
+             "\"clear_ns\": %.1f, \"ok\": %s}",
+             name, wire.size(), ser, parse, (double)clear_ns / (double)cleared, ok ? "true" : "false"));
+}
+
+void bench_pb() {
+    policy::RpcMeta req_meta;
+    req_meta.mutable_request()->set_service_name("example.EchoService");
+    req_meta.mutable_request()->set_method_name("Echo");
+    req_meta.set_compress_type(0);
+    req_meta.set_correlation_id(0x100000001ll * 77);
+    bench_pb_message("RpcMeta_request", req_meta);
+    policy::RpcMeta res_meta;
+    res_meta.set_compress_type(0);
+    res_meta.set_correlation_id(0x100000001ll * 77);
+    bench_pb_message("RpcMeta_response", res_meta);
+    example::EchoRequest req;
+    req.set_message(std::string(32, 'x'));
+    bench_pb_message("EchoRequest_32B", req);
+    example::EchoResponse res;
+    res.set_message(std::string(32, 'x'));
+    bench_pb_message("EchoResponse_32B", res);
+    example::EchoRequest wide;
+    wide.set_message("ids");
+    for (int i = 0; i < 16384; ++i) wide.add_ids((int64_t)i * 2654435761ll >> (i % 40));
+    bench_pb_message("EchoRequest_ids16k", wide);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+    std::string only;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--seconds") && i + 1 < argc) {
             g_seconds = atof(argv[++i]);
@@ -317,10 +390,20 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "bad --flag %s\n", kv.c_str());
                 return 2;
             }
+        } else if (!strcmp(argv[i], "--only") && i + 1 < argc) {
+            only = argv[++i];
         } else {
-            fprintf(stderr, "usage: %s [--seconds S] [--threads 1,2,4] [--flag name=value]...\n", argv[0]);
+            fprintf(stderr, "usage: %s [--seconds S] [--threads 1,2,4] [--only pb] [--flag name=value]...\n", argv[0]);
             return 2;
         }
+    }
+    if (only == "pb") {
+        bench_pb();
+        return 0;
+    }
+    if (!only.empty()) {
+        fprintf(stderr, "unknown section %s\n", only.c_str());
+        return 2;
     }
     fiber::init_runtime();
     bench_fiber_create();
@@ -330,5 +413,6 @@ int main(int argc, char** argv) {
     bench_contended_atomic();
     bench_buf_pipeline();
     bench_timer();
+    bench_pb();
     return 0;
 }
