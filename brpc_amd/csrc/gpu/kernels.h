@@ -142,7 +142,9 @@ int LaunchSnappyDecompressPiecesSerial(const SnappyPiece* pieces_dev, int n, uin
 int LaunchSnappyDecompressPiecesStamped(const SnappyPiece* pieces_dev, int n, uint32_t lo, uint32_t hi, int* err_dev,
                                         uint64_t* stamps, hipStream_t s);
 // Batched snappy compression: job.src = raw block (<= kSnappyMaxBlock),
-// job.dst = output with job.dst_cap >= SnappyMaxCompressedLength(src_len).
+// job.dst = output with job.dst_cap >= SnappyMaxCompressedLength(src_len),
+// which is enough for every src_len and content (blocks under 449 bytes are
+// cut into segments of 8 bytes, not 64 shorter ones, to stay within it).
 // scratch: n * SnappyCompressScratchPerBlock() bytes of device memory.
 // out_len_dev[i] = compressed size, err_dev[i] = 0 or an error code.
 constexpr uint32_t SnappyCompressSlot() { return ((kSnappyMaxBlock / 64) + 32 + 63) & ~63u; }

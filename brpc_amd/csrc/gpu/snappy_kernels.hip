@@ -39,9 +39,9 @@
 // header, copied out coalesced) is a valid snappy stream any decoder
 // accepts; its size lands within ~10% of the CPU codec's on repetitive
 // data. Blocks up to 16 KiB also keep the output slots in LDS (a lane's
-// output never exceeds its segment plus one literal header); 4 KiB blocks
-// take 42 KiB of LDS per wave, 3 waves per CU. (A/B on the MI355X: 32-bit
-// (position, fingerprint) entries that skip most verification loads ran
+// output never exceeds its segment by more than 16 bytes: CompressSegment
+// below); 4 KiB blocks take 42 KiB of LDS per wave, 3 waves per CU. (A/B on
+// the MI355X: 32-bit (position, fingerprint) entries that skip most verification loads ran
 // slower — 48 KiB/wave drops to 3 waves per CU; a double-buffered window
 // prefetch in the decompressor also lost to the single re-centred window.)
 #include <hip/hip_runtime.h>
@@ -871,6 +871,29 @@ static_assert(kCandMax / kWave <= 128, "match records hold a slice offset and le
 // hit distinct LDS banks was measured slower on MI355X: 56 vs 51 us per
 // 112-block launch of text; the layouts stay dense.)
 __host__ __device__ constexpr uint32_t CompressInBytes(uint32_t in_cap, bool) { return in_cap; }
+// Bytes per lane segment of a block of ulen bytes: a 64th of it, but at
+// least kMinSegment, so that a short block is cut into fewer lanes (the
+// rest stay empty) instead of segments of 1..7 bytes. Every non-empty lane
+// may end in a literal of its own, one tag byte each: 64 one-byte segments
+// made 129 bytes of a 64-byte block, past SnappyMaxCompressedLength; with
+// segments of 8 and more the worst case is n + ceil(n / 8) + the length
+// varint, within 32 + n + n / 6 for every n. Blocks of 449 bytes and more
+// are cut as before. The launchers size the output slots with the same
+// function of the launch's max_ulen (a job's segment is never longer).
+//
+// A lane's output exceeds its segment by at most 16 bytes, the slots'
+// margin: a copy element (2 or 3 bytes) is at least one byte shorter than
+// the >= 4 bytes it covers, and a literal adds its tag: 1 byte up to 60
+// bytes, 2 up to 256, 3 beyond. So a literal followed by a copy adds
+// nothing (short literal), 1 byte per 65 input bytes (61 + 4) or 2 bytes per
+// 261 (257 + 4), and only the segment's last literal keeps its whole tag.
+// The longest segment, 1024 bytes, is worst as 15 x (61 + 4) + a literal of
+// 49, 16 bytes of tags net; one long literal adds 3.
+constexpr uint32_t kMinSegment = 8;
+__host__ __device__ constexpr uint32_t CompressSegment(uint32_t ulen) {
+    return (ulen + kWave - 1) / kWave > kMinSegment ? (ulen + kWave - 1) / kWave : kMinSegment;
+}
+static_assert(CompressSegment(kSnappyMaxBlock) + 16 <= SnappyCompressSlot(), "scratch slots hold a lane's output");
 __host__ __device__ constexpr uint32_t CompressCandBytes(uint32_t in_cap) { return 2 * in_cap + 16; }
 // One block per wave; the body of snappy_compress_kernel and of the
 // compress role of codec_waves_kernel.
@@ -933,7 +956,7 @@ __device__ __forceinline__ void compress_wave(const SnappyJob* __restrict__ jobs
     }
     __syncthreads();
     stamp(stamps, blk, lane, 1);
-    const uint32_t seg = (ulen + kWave - 1) / kWave;
+    const uint32_t seg = CompressSegment(ulen);
     const uint32_t s = min(ulen, seg * (uint32_t)lane);
     const uint32_t e = min(ulen, s + seg);
     if (kCand) {
@@ -1329,7 +1352,7 @@ int LaunchCodecWaves(const FusedCodecArgs& a, hipStream_t s) {
     const uint32_t mu = a.max_ulen ? a.max_ulen : 1;
     if (mu > kCandMax || mu > kParMax) return -1;
     const uint32_t in_cap = (mu + 15) & ~15u;
-    const uint32_t seg = (mu + kWave - 1) / kWave;
+    const uint32_t seg = CompressSegment(mu);
     const uint32_t slot = (seg + 16 + 15) & ~15u;
     const uint32_t comp_lds = CompressInBytes(in_cap, true) + kWave * slot + CompressCandBytes(in_cap);
     const uint32_t cin_cap = (uint32_t)((SnappyMaxCompressedLength(mu) + 16 + 15) & ~15ull);
@@ -1405,8 +1428,8 @@ int LaunchSnappyCompressStamped(const SnappyJob* jobs_dev, int n, uint32_t max_u
     if (max_ulen == 0) max_ulen = 1;
     if (max_ulen > kSnappyMaxBlock) return -1;
     const uint32_t in_cap = (max_ulen + 15) & ~15u;  // larger jobs fail with code 1
-    // a lane's output never exceeds its segment plus one literal header
-    const uint32_t seg = (max_ulen + kWave - 1) / kWave;
+    // a lane's output exceeds its segment by at most 16 bytes (CompressSegment)
+    const uint32_t seg = CompressSegment(max_ulen);
     const uint32_t slot = (seg + 16 + 15) & ~15u;
     // slots in LDS too while that keeps >= 2 waves per CU (blocks up to
     // 16 KiB: <= 67 KiB); a 32 KiB block with LDS slots would run alone on its CU
