@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "base/json_string.h"
+#include "base/json_string_rows.h"
 #include "gpu/kernels.h"
 #include "gpu/workgroup.h"
 
@@ -314,11 +315,15 @@ __device__ __forceinline__ uint32_t jstr_starters(uint32_t backslashes, uint32_t
 
 // The bytes the lane's own 16 bytes give, with starter mask m of its window:
 // returns their number, lowers *bad to the first offender; writes them at out
-// when it is not null.
+// when it is not null. kMasked (the rows kernels): only the bytes whose bit is
+// set in `inside` are looked at, the bytes of a string's body; the others give
+// nothing and offend nobody here.
+template <bool kMasked = false>
 __device__ __forceinline__ uint32_t jstr_emit(const JstrText& x, int64_t i0, uint32_t mine, uint64_t w0, uint64_t w1,
-                                              uint32_t m, uint32_t* bad, char* out) {
+                                              uint32_t m, uint32_t* bad, char* out, uint32_t inside = 0) {
     uint32_t count = 0;
     for (uint32_t j = 0; j < mine; ++j) {
+        if (kMasked && !((inside >> j) & 1)) continue;
         const int64_t i = i0 + j;
         const uint32_t before = m >> (10 + j);  // bit 6 - k: whether byte i - k starts an escape, k = 1..6
         if (before & 32u) continue;            // the letter of an escape
@@ -546,6 +551,391 @@ __global__ void __launch_bounds__(kJstrThreads) jstr_unescape_place_kernel(const
     wg::copy_out_shifted<kJstrThreads>(reinterpret_cast<const uint32_t*>(image16), 0, dst, total);
 }
 
+// ----------------------------------------------------------- unescape rows
+
+namespace jr = ::mrpc::json_string_rows;
+// The carried state: 0..4 outside a string after that kind of token (jr::Kind,
+// kStart: none yet), 5 / 6 inside one after an even / odd backslash run.
+constexpr uint32_t kRowsInside = 5;
+constexpr uint32_t kRowsPass = 7;  // a chunk's exit only: outside and no token met, the entry's kind stays
+constexpr uint32_t kRowsW = kJsonStringRowsEntryWords;
+// words of an entry: size, closing quotes, lowest offender, first token, first ']', exit (in the scan: last token)
+enum { kRwSize = 0, kRwClose = 1, kRwBad = 2, kRwFirst = 3, kRwBracket = 4, kRwExit = 5 };
+constexpr uint32_t kRwChosen = 3 * kRowsW;  // the entry state the carry picked
+
+// A bit per own byte of the lane.
+struct JrowBits {
+    uint32_t quote, ws, lb, comma, rb, backslash, valid;
+};
+__device__ __forceinline__ JrowBits jrow_bits(uint64_t w0, uint64_t w1, uint32_t mine) {
+    JrowBits b;
+    b.valid = mine >= 16 ? 0xFFFFu : (1u << mine) - 1;  // what lies past `mine` reads as '0': none of these
+    b.quote = jstr_bits_of(w0, w1, '"');
+    b.ws = jstr_bits_of(w0, w1, ' ') | jstr_bits_of(w0, w1, '\t') | jstr_bits_of(w0, w1, '\n') | jstr_bits_of(w0, w1, '\r');
+    b.lb = jstr_bits_of(w0, w1, '[');
+    b.comma = jstr_bits_of(w0, w1, ',');
+    b.rb = jstr_bits_of(w0, w1, ']');
+    b.backslash = jstr_bits_of(w0, w1, '\\');
+    return b;
+}
+// The quotes of the lane's bytes that no escape covers: byte j is covered when
+// byte j - 1 starts an escape (bit 15 + j of the window's starter mask).
+__device__ __forceinline__ uint32_t jrow_open_quotes(const JrowBits& b, uint32_t m) { return b.quote & ~(m >> 15); }
+// Bit j: whether the lane's byte j lies inside a string, seen from in front of
+// it: the state in front of the lane's bytes, flipped by every uncovered quote
+// below j (the prefix-xor of uq, exclusive).
+__device__ __forceinline__ uint32_t jrow_inside(uint32_t uq, uint32_t before) {
+    uint32_t p = uq;
+    p ^= p << 1;
+    p ^= p << 2;
+    p ^= p << 4;
+    p ^= p << 8;
+    return ((p << 1) ^ (before ? 0xFFFFu : 0u)) & 0xFFFFu;
+}
+// The decoded bytes of the lane's `upto` first bytes, `content` the bytes of
+// string bodies among them; writes them at out when it is not null.
+__device__ __forceinline__ uint32_t jrow_emit(const JstrText& x, int64_t i0, uint32_t upto, uint64_t w0, uint64_t w1,
+                                              uint32_t m, const JrowBits& b, uint32_t content, uint32_t* bad, char* out) {
+    content &= upto >= 16 ? 0xFFFFu : (1u << upto) - 1;
+    if (content == 0) return 0;
+    // no escape reaches the lane's bytes (none starts in them or in the 6 before): every body byte is itself
+    if (out == nullptr && (m >> 10) == 0 && (b.backslash & content) == 0) return (uint32_t)__popc(content);
+    return jstr_emit<true>(x, i0, upto, w0, w1, m, bad, out, content);
+}
+
+struct JrowLane {
+    uint32_t size, nclose, bad, first, last, rb;
+};
+// What the lane's bytes hold for one entry. m: the starter mask of its window,
+// uq: its uncovered quotes, inside: jrow_inside. A token is the word
+// (offset in the chunk) << 3 | kind; first / last: the lane's, kNone / 0 when
+// it has none. Tokens after its first are judged here, against the token
+// before them; bad and rb are job offsets.
+__device__ __forceinline__ JrowLane jrow_lane(const JstrText& x, int64_t i0, uint32_t mine, uint64_t w0, uint64_t w1,
+                                              uint32_t m, const JrowBits& b, uint32_t uq, uint32_t inside) {
+    JrowLane r;
+    r.bad = kNone;
+    r.size = jrow_emit(x, i0, mine, w0, w1, m, b, inside & ~uq & b.valid, &r.bad, nullptr);
+    r.nclose = (uint32_t)__popc(uq & inside);
+    const uint32_t outside = ~inside & ~uq & b.valid;
+    const uint32_t illegal = outside & ~(b.ws | b.lb | b.comma | b.rb);
+    if (illegal) {
+        const uint32_t at = (uint32_t)i0 + (uint32_t)__builtin_ctz(illegal);
+        if (at < r.bad) r.bad = at;
+    }
+    r.first = kNone;
+    r.last = 0;
+    r.rb = kNone;
+    uint32_t pred = 0;  // no token of this lane yet (kStart is no token)
+    for (uint32_t tokens = uq | (outside & (b.lb | b.comma | b.rb)); tokens; tokens &= tokens - 1) {
+        const uint32_t j = (uint32_t)__builtin_ctz(tokens), bit = 1u << j;
+        const uint32_t kind = (uq & bit)        ? ((inside & bit) ? jr::kCloseQuote : jr::kOpenQuote)
+                              : (b.lb & bit)    ? jr::kOpenBracket
+                              : (b.comma & bit) ? jr::kComma
+                                                : jr::kCloseBracket;
+        const uint32_t at = (uint32_t)i0 + j;
+        r.last = (16 * threadIdx.x + j) << 3 | kind;
+        if (pred == 0) r.first = r.last;
+        else if (!jr::Follows(pred, kind) && at < r.bad) r.bad = at;
+        if (kind == jr::kCloseBracket && r.rb == kNone) r.rb = at;
+        pred = kind;
+    }
+    return r;
+}
+
+__device__ __forceinline__ uint32_t jrow_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
+
+__global__ void __launch_bounds__(kJstrThreads) jstr_rows_scan_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
+                                                                      uint32_t* __restrict__ info) {
+    __shared__ u32x4 stage16[kStage16];
+    __shared__ uint64_t wave_np[4], wave_odd[4];
+    __shared__ uint32_t wave_par[2][4];   // parity of each wave's uncovered quotes, backslash carry-in 0 / 1
+    __shared__ uint32_t wave_last[3][4];  // the last token of each wave, per entry
+    __shared__ uint32_t acc[3][kRowsW];
+    __shared__ uint32_t exit_par;  // bit c: the backslash carry-out for carry-in c
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int ji = wg::job_of<&JsonStringJob::first_chunk>(jobs, njobs, blockIdx.x);
+    const JsonStringJob job = jobs[ji];
+    const uint32_t c = blockIdx.x - job.first_chunk;
+    if (c >= job.nchunks) return;  // uniform
+    const uint32_t at = c * kC, left = job.n - at, len = left < kC ? left : kC;
+    JstrText x;
+    x.st = jstr_stage(stage16, job.src, job.n, at, len, kStageBack, kStageFwd);
+    x.at = at;
+    x.n = job.n;
+    if (t < 3 * kRowsW) {
+        const uint32_t k = t % kRowsW;
+        acc[t / kRowsW][k] = k == kRwBad || k == kRwFirst || k == kRwBracket ? kNone : 0u;
+    }
+    __syncthreads();
+    const uint32_t mine = jstr_mine(len);
+    uint64_t w0, w1;
+    jstr_lane_words(x.st, mine, &w0, &w1);
+    const JrowBits b = jrow_bits(w0, w1, mine);
+    uint32_t special = b.quote | b.backslash;
+    if (t < 16 && x.byte((int64_t)at - 16 + t) == '\\') special = 1;
+    // starter masks of the lane's window for backslash carry-in 0 and 1; without a quote or a backslash in reach
+    // nothing starts an escape and no quote flips a state
+    uint32_t m0 = 0, m1 = 0, mid0 = 0, mid1 = 0;
+    if (__syncthreads_or(special != 0)) {
+        const uint32_t bs = jstr_window_backslashes(x, b.backslash);
+        bool depends;
+        const uint32_t par = jstr_window_parity(bs & 0xFFFFu, wave_np, wave_odd, &depends);
+        m0 = jstr_starters(bs, depends ? 0u : par, &mid0);
+        if (depends) m1 = jstr_starters(bs, 1u, &mid1);
+        else m1 = m0, mid1 = mid0;
+    }
+    const uint32_t uq0 = jrow_open_quotes(b, m0), uq1 = jrow_open_quotes(b, m1);
+    const uint64_t odd0 = __ballot(__popc(uq0) & 1), odd1 = __ballot(__popc(uq1) & 1);
+    if (lane == 0) {
+        wave_par[0][wave] = (uint32_t)__popcll(odd0) & 1;
+        wave_par[1][wave] = (uint32_t)__popcll(odd1) & 1;
+    }
+    // the parity in front of the last lane's own bytes is the one in front of byte at + kC - 16: the carry
+    if (t == kJstrThreads - 1) exit_par = (mid0 & 1) | (mid1 & 1) << 1;
+    __syncthreads();
+    const uint64_t below = (1ull << lane) - 1;
+    uint32_t before0 = (uint32_t)__popcll(odd0 & below) & 1, before1 = (uint32_t)__popcll(odd1 & below) & 1;
+    uint32_t flips0 = 0, flips1 = 0;  // of the whole chunk
+#pragma unroll
+    for (uint32_t k = 0; k < kJstrThreads / 64; ++k) {
+        if (k < wave) before0 ^= wave_par[0][k], before1 ^= wave_par[1][k];
+        flips0 ^= wave_par[0][k];
+        flips1 ^= wave_par[1][k];
+    }
+    // entry 0: outside. entry 1: inside after an even run, every state the other way round. entry 2: inside after
+    // an odd run, which differs from entry 1 from the first lane on whose escapes depend on the carry-in
+    const int64_t i0 = (int64_t)at + 16 * t;
+    const uint32_t in0 = jrow_inside(uq0, before0), in1 = in0 ^ 0xFFFFu, in2 = jrow_inside(uq1, before1 ^ 1u);
+    JrowLane v[3];
+    v[0] = jrow_lane(x, i0, mine, w0, w1, m0, b, uq0, in0);
+    v[1] = jrow_lane(x, i0, mine, w0, w1, m0, b, uq0, in1);
+    v[2] = (m1 != m0 || in2 != in1) ? jrow_lane(x, i0, mine, w0, w1, m1, b, uq1, in2) : v[1];
+    uint32_t prev[3];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        const uint32_t size = wg::wave_sum(v[e].size), nclose = wg::wave_sum(v[e].nclose);
+        if (lane == 0) {
+            if (size) atomicAdd(&acc[e][kRwSize], size);
+            if (nclose) atomicAdd(&acc[e][kRwClose], nclose);
+        }
+        if (v[e].bad != kNone) atomicMin(&acc[e][kRwBad], v[e].bad);
+        if (v[e].rb != kNone) atomicMin(&acc[e][kRwBracket], v[e].rb);
+        // the last token in front of the lane: tokens ascend with the lanes, so the highest word below it
+        const uint32_t incl = wg::wave_incl_scan(v[e].last, [](uint32_t p, uint32_t q) { return jrow_max(p, q); });
+        if (lane == 63) wave_last[e][wave] = incl;
+        prev[e] = wg::wave_prev(incl);
+        if (lane == 0) prev[e] = 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        uint32_t last = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kJstrThreads / 64; ++k) {
+            if (k < wave) prev[e] = jrow_max(prev[e], wave_last[e][k]);
+            last = jrow_max(last, wave_last[e][k]);
+        }
+        if (v[e].first != kNone) {
+            // the lane's first token: judged against the token before it in the chunk; the chunk's first is the
+            // carry kernel's to judge
+            if (prev[e] == 0) atomicMin(&acc[e][kRwFirst], v[e].first);
+            else if (!jr::Follows(prev[e] & 7, v[e].first & 7)) atomicMin(&acc[e][kRwBad], at + (v[e].first >> 3));
+        }
+        if (t == 0) {
+            const uint32_t inside = (e ? 1u : 0u) ^ (e == 2 ? flips1 : flips0);
+            const uint32_t carry = (exit_par >> (e == 2 ? 1 : 0)) & 1;
+            acc[e][kRwExit] = inside ? kRowsInside + carry : (last ? (last & 7) : kRowsPass);
+        }
+    }
+    __syncthreads();
+    if (t < 3 * kRowsW) info[(uint64_t)blockIdx.x * kJsonStringRowsInfoWords + t] = acc[t / kRowsW][t % kRowsW];
+}
+
+// maps of the seven states to themselves, three bits per image
+__device__ __forceinline__ uint32_t jrow_then(uint32_t f, uint32_t g) {  // first f, then g
+    uint32_t r = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < 7; ++s) r |= ((g >> (3 * ((f >> (3 * s)) & 7))) & 7) << (3 * s);
+    return r;
+}
+constexpr uint32_t kRowsIdentity = 0u | 1u << 3 | 2u << 6 | 3u << 9 | 4u << 12 | 5u << 15 | 6u << 18;
+
+__global__ void __launch_bounds__(kJstrThreads) jstr_rows_carry_kernel(const JsonStringJob* __restrict__ jobs,
+                                                                       uint32_t* __restrict__ info,
+                                                                       uint32_t* __restrict__ prefix, uint32_t nchunks_all,
+                                                                       uint32_t* __restrict__ state) {
+    __shared__ uint32_t wave_map[kJstrThreads / 64];
+    __shared__ uint32_t low[3];  // lowest offender, first ']' outside, depth
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const JsonStringJob job = jobs[blockIdx.x];
+    if (t < 3) low[t] = t == 2 ? 0u : kNone;
+    uint32_t carry = jr::kStart, lowest = kNone, bracket = kNone;
+    for (uint32_t base = 0; base < job.nchunks; base += kJstrThreads) {
+        const uint32_t c = base + t;
+        uint32_t* mine = info + (uint64_t)(job.first_chunk + c) * kJsonStringRowsInfoWords;
+        uint32_t map = kRowsIdentity;
+        if (c < job.nchunks) {
+            const uint32_t e0 = mine[kRwExit], e1 = mine[kRowsW + kRwExit], e2 = mine[2 * kRowsW + kRwExit];
+            map = e1 << 15 | e2 << 18;
+#pragma unroll
+            for (uint32_t s = 0; s < kRowsInside; ++s) map |= (e0 == kRowsPass ? s : e0) << (3 * s);
+        }
+        const uint32_t incl = wg::wave_incl_scan(map, [](uint32_t f, uint32_t g) { return jrow_then(f, g); });
+        if (lane == 63) wave_map[wave] = incl;
+        __syncthreads();
+        uint32_t excl = wg::wave_prev(incl);
+        if (lane == 0) excl = kRowsIdentity;
+        uint32_t front = kRowsIdentity, tile = kRowsIdentity;
+        for (uint32_t k = 0; k < kJstrThreads / 64; ++k) {
+            if (k < wave) front = jrow_then(front, wave_map[k]);
+            tile = jrow_then(tile, wave_map[k]);
+        }
+        const uint32_t st = (jrow_then(front, excl) >> (3 * carry)) & 7;
+        if (c < job.nchunks) {
+            const uint32_t* w = mine + (st < kRowsInside ? 0u : st - 4u) * kRowsW;
+            prefix[job.first_chunk + c] = w[kRwSize];
+            prefix[nchunks_all + 1 + job.first_chunk + c] = w[kRwClose];
+            mine[kRwChosen] = st;
+            if (w[kRwBad] < lowest) lowest = w[kRwBad];
+            if (w[kRwBracket] < bracket) bracket = w[kRwBracket];
+            if (st < kRowsInside && w[kRwFirst] != kNone) {  // the chunk's first token, against its true predecessor
+                const uint32_t kind = w[kRwFirst] & 7, where = c * kC + (w[kRwFirst] >> 3);
+                if (!jr::Follows(st, kind) && where < lowest) lowest = where;
+                if (st == jr::kStart && kind == jr::kOpenBracket) low[2] = 1;  // the text's first token
+            }
+        }
+        carry = (tile >> (3 * carry)) & 7;
+        __syncthreads();  // wave_map is rewritten by the next tile
+    }
+    if (lowest != kNone) atomicMin(&low[0], lowest);
+    if (bracket != kNone) atomicMin(&low[1], bracket);
+    __syncthreads();
+    if (t == 0) {
+        uint32_t* st = state + (uint64_t)blockIdx.x * kJsonStringRowsStateWords;
+        st[0] = low[0];
+        st[1] = carry;
+        st[2] = low[2];
+        st[3] = low[1];
+    }
+}
+
+// a lane per job, after the prefix scan over both tables
+__global__ void jstr_rows_verdict_kernel(const JsonStringJob* __restrict__ jobs, int njobs, const uint32_t* __restrict__ prefix,
+                                         uint32_t nchunks_all, const uint32_t* __restrict__ state, int32_t* __restrict__ ok,
+                                         JsonStringRowsResult* __restrict__ res) {
+    const int ji = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (ji >= njobs) return;
+    const JsonStringJob job = jobs[ji];
+    const uint32_t* bytes = prefix + job.first_chunk;
+    const uint32_t* quotes = bytes + nchunks_all + 1;
+    const uint32_t* st = state + (uint64_t)ji * kJsonStringRowsStateWords;
+    const uint32_t depth = st[2];
+    uint32_t bad = st[0];
+    if (depth == 0 && st[3] < bad) bad = st[3];                    // a ']' without its '['
+    if (bad == kNone && !jr::EndsWell(st[1], depth)) bad = job.n;  // the text ends too soon
+    JsonStringRowsResult r;
+    r.len = (uint32_t)(bytes[job.nchunks] - bytes[0]);
+    r.rows = quotes[job.nchunks] - quotes[0];
+    r.depth = depth;
+    r.first_bad = 0;
+    r.err = 0;
+    if (bad != kNone) {
+        r.err = 1;
+        r.first_bad = bad;
+        r.len = 0;
+        r.rows = r.depth = 0;
+    } else if (r.len > job.cap || r.rows > job.rows) {
+        r.err = 3;
+    }
+    ok[ji] = r.err == 0;
+    res[ji] = r;
+}
+
+__global__ void __launch_bounds__(kJstrThreads) jstr_rows_place_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
+                                                                       const uint32_t* __restrict__ info,
+                                                                       const uint32_t* __restrict__ prefix,
+                                                                       uint32_t nchunks_all, const int32_t* __restrict__ ok,
+                                                                       JsonStringRowsResult* __restrict__ res) {
+    __shared__ u32x4 stage16[kStage16];
+    __shared__ u32x4 image16[kUnImage16];
+    __shared__ uint64_t wave_np[4], wave_odd[4];
+    __shared__ uint32_t wave_par[4];
+    __shared__ uint32_t part[2][kJstrThreads / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int ji = wg::job_of<&JsonStringJob::first_chunk>(jobs, njobs, blockIdx.x);
+    const JsonStringJob job = jobs[ji];
+    const uint32_t c = blockIdx.x - job.first_chunk;
+    if (c >= job.nchunks || !ok[ji]) return;  // uniform
+    const uint32_t at = c * kC, left = job.n - at, len = left < kC ? left : kC;
+    JstrText x;
+    x.st = jstr_stage(stage16, job.src, job.n, at, len, kStageBack, kStageFwd);
+    x.at = at;
+    x.n = job.n;
+    __syncthreads();
+    const uint32_t* bytes = prefix + blockIdx.x;
+    const uint32_t* quotes = bytes + nchunks_all + 1;
+    const uint32_t want = bytes[1] - bytes[0], want_rows = quotes[1] - quotes[0];
+    // decoded bytes and closing quotes of the job in front of this chunk: below cap and row_cap, the verdict
+    // compared the job's totals
+    const uint32_t out0 = bytes[0] - prefix[job.first_chunk];
+    const uint32_t row0 = quotes[0] - prefix[nchunks_all + 1 + job.first_chunk];
+    const uint32_t entry = info[(uint64_t)blockIdx.x * kJsonStringRowsInfoWords + kRwChosen];
+    const uint32_t enters_inside = entry >= kRowsInside, cin = entry == kRowsInside + 1;
+    const uint32_t mine = jstr_mine(len);
+    uint64_t w0, w1;
+    jstr_lane_words(x.st, mine, &w0, &w1);
+    const JrowBits b = jrow_bits(w0, w1, mine);
+    uint32_t special = b.quote | b.backslash;
+    if (t < 16 && x.byte((int64_t)at - 16 + t) == '\\') special = 1;
+    if (!__syncthreads_or(special != 0)) {  // all copy, or all punctuation
+        if (want != (enters_inside ? len : 0u) || want_rows != 0) {
+            if (t == 0) res[ji].err = 4;
+            return;
+        }
+        if (enters_inside)
+            wg::copy_out_shifted<kJstrThreads>(reinterpret_cast<const uint32_t*>(stage16), (uint32_t)x.st.pos0,
+                                               job.dst + out0, len);
+        return;
+    }
+    const int64_t i0 = (int64_t)at + 16 * t;
+    const uint32_t bs = jstr_window_backslashes(x, b.backslash);
+    bool depends;
+    const uint32_t par = jstr_window_parity(bs & 0xFFFFu, wave_np, wave_odd, &depends);
+    uint32_t mid, bad = kNone;
+    const uint32_t m = jstr_starters(bs, depends ? cin : par, &mid);
+    const uint32_t uq = jrow_open_quotes(b, m);
+    const uint64_t odd = __ballot(__popc(uq) & 1);
+    if (lane == 0) wave_par[wave] = (uint32_t)__popcll(odd) & 1;
+    __syncthreads();
+    uint32_t before = enters_inside ^ ((uint32_t)__popcll(odd & ((1ull << lane) - 1)) & 1);
+#pragma unroll
+    for (uint32_t k = 0; k < kJstrThreads / 64; ++k) {
+        if (k < wave) before ^= wave_par[k];
+    }
+    const uint32_t inside = jrow_inside(uq, before), content = inside & ~uq & b.valid, closing = uq & inside;
+    const uint32_t count = jrow_emit(x, i0, mine, w0, w1, m, b, content, &bad, nullptr);
+    const uint32_t nclose = (uint32_t)__popc(closing);
+    const uint32_t incl_bytes = wg::scan_post(count, part[0]), incl_rows = wg::scan_post(nclose, part[1]);
+    __syncthreads();
+    uint32_t total = 0, total_rows = 0;
+    const uint32_t bytes_before = wg::scan_rank<kJstrThreads>(incl_bytes, count, part[0], &total);
+    const uint32_t rows_before = wg::scan_rank<kJstrThreads>(incl_rows, nclose, part[1], &total_rows);
+    if (total != want || total_rows != want_rows || __syncthreads_or(bad != kNone)) {  // uniform: the source changed
+        if (t == 0) res[ji].err = 4;
+        return;
+    }
+    if (count) jstr_emit<true>(x, i0, mine, w0, w1, m, &bad, reinterpret_cast<char*>(image16) + bytes_before, content);
+    __syncthreads();
+    wg::copy_out_shifted<kJstrThreads>(reinterpret_cast<const uint32_t*>(image16), 0, job.dst + out0, total);
+    // the lane that holds the k-th closing quote of the job writes row_ends[k]
+    uint32_t* ends = const_cast<uint32_t*>(job.row_ends) + row0 + rows_before;
+    for (uint32_t q = closing; q; q &= q - 1) {
+        const uint32_t j = (uint32_t)__builtin_ctz(q);
+        *ends++ = out0 + bytes_before + jrow_emit(x, i0, j, w0, w1, m, b, content, &bad, nullptr);
+    }
+}
+
 // ------------------------------------------------------------------- UTF-8
 
 __global__ void __launch_bounds__(kJstrThreads) jstr_utf8_kernel(const JsonStringJob* __restrict__ jobs, int njobs,
@@ -595,7 +985,7 @@ __global__ void jstr_utf8_publish_kernel(const uint32_t* __restrict__ bad, int n
 
 // the job table to device memory, the counters to their start values
 int jstr_begin(const JsonStringTables& t, hipStream_t s) {
-    if (!t.jobs || !t.jobs_dev || !t.bad || !t.res) return -1;
+    if (!t.jobs || !t.jobs_dev || !t.bad || (!t.res && !t.rows_res)) return -1;
     if (hipMemcpyAsync(t.jobs_dev, t.jobs, (size_t)t.njobs * sizeof(JsonStringJob), hipMemcpyHostToDevice, s) != hipSuccess)
         return -1;
     if (hipMemsetAsync(t.bad, 0xFF, (size_t)t.njobs * sizeof(uint32_t), s) != hipSuccess) return -1;
@@ -659,6 +1049,25 @@ int LaunchJsonStringValidate(const JsonStringTables& t, hipStream_t s) {
     hipLaunchKernelGGL(jstr_utf8_kernel, dim3(t.nchunks), dim3(kJstrThreads), 0, s, t.jobs_dev, t.njobs, t.bad);
     if (!jstr_launched()) return -1;
     hipLaunchKernelGGL(jstr_utf8_publish_kernel, dim3((t.njobs + 63) / 64), dim3(64), 0, s, t.bad, t.njobs, t.res);
+    return jstr_launched() ? 0 : -1;
+}
+
+int LaunchJsonStringUnescapeRows(const JsonStringTables& t, hipStream_t s) {
+    if (t.njobs <= 0 || t.nchunks == 0) return 0;
+    if (!t.prefix || !t.ok || !t.info || !t.state || !t.rows_res || jstr_begin(t, s) != 0) return -1;
+    // the second size table, behind the first
+    if (hipMemsetAsync(t.prefix + t.nchunks + 1, 0, ((size_t)t.nchunks + 1) * sizeof(uint32_t), s) != hipSuccess) return -1;
+    const dim3 threads(kJstrThreads), chunks(t.nchunks);
+    hipLaunchKernelGGL(jstr_rows_scan_kernel, chunks, threads, 0, s, t.jobs_dev, t.njobs, t.info);
+    if (!jstr_launched()) return -1;
+    hipLaunchKernelGGL(jstr_rows_carry_kernel, dim3(t.njobs), threads, 0, s, t.jobs_dev, t.info, t.prefix, t.nchunks, t.state);
+    if (!jstr_launched()) return -1;
+    if (LaunchPbRunPrefix(t.prefix, 2 * ((int)t.nchunks + 1), s) != 0) return -1;
+    hipLaunchKernelGGL(jstr_rows_verdict_kernel, dim3((t.njobs + 63) / 64), dim3(64), 0, s, t.jobs_dev, t.njobs, t.prefix,
+                       t.nchunks, t.state, t.ok, t.rows_res);
+    if (!jstr_launched()) return -1;
+    hipLaunchKernelGGL(jstr_rows_place_kernel, chunks, threads, 0, s, t.jobs_dev, t.njobs, t.info, t.prefix, t.nchunks, t.ok,
+                       t.rows_res);
     return jstr_launched() ? 0 : -1;
 }
 

@@ -1,15 +1,20 @@
 // JSON string bodies that live in device memory (gpu/json_string_kernels.hip):
-// escape, unescape and the UTF-8 verdict, HBM -> HBM. A handler that holds text
+// escape, unescape, the text of an array of strings back into bytes and row
+// ends, and the UTF-8 verdict, HBM -> HBM. A handler that holds text
 // in HBM (a string field found by DevicePayloadField, the rows DeviceSplitRows
 // produced for a repeated string, a prompt or completion buffer) turns it into
 // the body of a JSON string, or a body back into text, without a trip to the
 // host; the reference goes through rapidjson's Writer and Reader on the host.
-// The rules are base/json_string.h; json::EscapeStringBody, EscapeStringRows,
-// UnescapeStringBody and Utf8FirstBad (json/json.h) are the host twins.
-// Host-resident strings stay with those: there is no staged path through the
-// device and no pb2json / json2pb hook.
+// The rules are base/json_string.h and base/json_string_rows.h;
+// json::EscapeStringBody, EscapeStringRows, UnescapeStringBody,
+// UnescapeStringRows and Utf8FirstBad (json/json.h) are the host twins. A
+// repeated string goes both ways: DeviceEscapeJsonStrings with row_ends writes
+// "r0","r1",..., DeviceUnescapeJsonStringRows turns that text, or the
+// ["r0","r1",...] a peer sends, back into (bytes, row_ends), the pair
+// DeviceBuildRows takes. Host-resident strings stay with the twins: there is
+// no staged path through the device and no pb2json / json2pb hook.
 //
-// Codes of all three entries: 0 done; 1 see each entry, first_bad is set;
+// Codes of all entries: 0 done; 1 see each entry, first_bad is set;
 // 2 refused before any launch (a null pointer where bytes are to be read or
 // written, n above 2^32 - 2 or a worst-case output above 2^32 - 1, src and dst
 // ranges that overlap, row_ends that is not 4-byte aligned, rows without
@@ -23,6 +28,7 @@
 
 #include <cstdint>
 
+#include "base/json_string_rows.h"
 #include "gpu/kernels.h"
 
 namespace mrpc {
@@ -65,6 +71,36 @@ struct DeviceJsonUnescapeJob {
     int err = 0;             // 1: not for the device, json::Reader decides
 };
 int DeviceUnescapeJsonStrings(DeviceJsonUnescapeJob* jobs, int njobs, int device);
+
+// The worst cases of DeviceUnescapeJsonStringRows for a text of n bytes: n - 2
+// decoded bytes, (n + 1) / 3 strings.
+constexpr uint64_t JsonStringRowsMaxBytes(uint64_t n) { return json_string_rows::JsonStringRowsMaxBytes(n); }
+constexpr uint64_t JsonStringRowsMaxRows(uint64_t n) { return json_string_rows::JsonStringRowsMaxRows(n); }
+
+// "r0","r1",... or ["r0","r1",...] (base/json_string_rows.h has the grammar)
+// -> the decoded bytes of all strings at dst and row_ends[r], the bytes in
+// strings 0..r: the inverse of an escape job with row_ends. Codes as above,
+// with these particulars. 1: the text is not for the device (json::Reader
+// decides), first_bad is the offset at which a parser reading from the left
+// cannot go on; len, rows and depth are 0. 2 also: a null dst with cap > 0, a
+// null row_ends with row_cap > 0, dst or row_ends overlapping src or each
+// other. 3: more than cap bytes or more than row_cap strings, found on the
+// device since both depend on the data; len and rows say what the text holds.
+// 4: the source changed between the passes. With 1 and 3 dst and row_ends are
+// untouched, and no store goes beyond either capacity. n == 0 is code 0, no
+// rows, nothing written, no launch.
+struct DeviceJsonStringRowsJob {
+    const void* src = nullptr;  // device, any alignment
+    uint64_t n = 0;             // at most 2^32 - 2
+    void* dst = nullptr;        // decoded bytes, any alignment; must not overlap src
+    uint64_t cap = 0;           // JsonStringRowsMaxBytes(n) always suffices
+    void* row_ends = nullptr;   // uint32[row_cap], 4-byte aligned
+    uint64_t row_cap = 0;       // JsonStringRowsMaxRows(n) always suffices
+    uint64_t len = 0, rows = 0, first_bad = 0;  // out
+    uint32_t depth = 0;                         // out: 1 when the text is bracketed
+    int err = 0;
+};
+int DeviceUnescapeJsonStringRows(DeviceJsonStringRowsJob* jobs, int njobs, int device);
 
 struct DeviceUtf8Job {
     const void* src = nullptr;

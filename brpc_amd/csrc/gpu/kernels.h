@@ -757,18 +757,61 @@ int LaunchBase64Decode(const Base64Job* jobs, int njobs, uint32_t nblocks, JsonN
 //                     it (up to 3 bytes beyond), a continuation byte from up to
 //                     3 bytes before; lowest offender by atomicMin; then a
 //                     lane per job publishes
+//   rows      the text of a JSON array of strings ("r0","r1",.. or ["r0",..],
+//             base/json_string_rows.h) -> the decoded bytes and row ends. Two
+//             facts cross a chunk's edge: the backslash parity, as above, and
+//             whether the edge lies inside a string. A chunk is entered
+//             outside a string, inside one after an even backslash run, or
+//             inside after an odd one.
+//             scan    a workgroup per chunk, for each of the three entries: the
+//                     quotes no escape covers from the starter masks, the
+//                     in-string mask as their prefix-xor (within a lane's 16
+//                     bits, by ballot parity across the wave, then across the
+//                     four waves), and from it the decoded size, the closing
+//                     quotes, the lowest offender a chunk can decide alone (a
+//                     bad escape inside, a byte outside that is no token, a
+//                     token its predecessor inside the chunk does not allow),
+//                     the kind and offset of the first token outside (only the
+//                     chunk before knows its predecessor), the first ']'
+//                     outside, and the exit: inside (even / odd), or outside
+//                     with the kind of the last token, "none" when all of the
+//                     chunk outside strings is whitespace. A chunk with neither
+//                     quote nor backslash (nor a backslash in the 16 bytes
+//                     before) is all copy when entered inside and all
+//                     punctuation when entered outside
+//             carry   a workgroup per job composes the chunks' maps over seven
+//                     states (outside after START [ "close , ], inside even /
+//                     odd), picks every chunk's entry, judges its first token
+//                     against the true predecessor, writes the two size tables
+//                     (bytes, closing quotes) and the job's lowest offender,
+//                     first ']', depth and final state. No lane reads
+//                     backwards through the text: the predecessor travels in
+//                     the state
+//             prefix  LaunchPbRunPrefix over both tables at once
+//             verdict a lane per job: a ']' at depth 0, the end rule, cap and
+//                     row_cap (err 3), ok[job], the result words
+//             place   a workgroup per chunk with its entry: the bytes inside
+//                     strings are compacted into an LDS image and leave with
+//                     16-byte stores; the lane that holds the k-th closing
+//                     quote writes row_ends[k] = the bytes before the chunk +
+//                     the decoded bytes before that quote in the chunk
 // res is device-writable pinned host memory; everything else device memory.
 constexpr uint32_t kJsonStringChunkBytes = 4096;
 constexpr uint32_t kJsonStringNone = 0xFFFFFFFFu;
 constexpr uint32_t kJsonStringBlockRows = 256;
 constexpr uint32_t kJsonStringGroupBytes = 64;
 constexpr uint32_t kJsonStringInfoWords = 6;  // per chunk: size, bad for carry-in 0 / 1, the map, the carry-in
+// rows, per chunk: for each of the three entries size, closing quotes, lowest
+// offender, first token, first ']', exit; then the entry state the carry chose
+constexpr uint32_t kJsonStringRowsEntryWords = 6;
+constexpr uint32_t kJsonStringRowsInfoWords = 3 * kJsonStringRowsEntryWords + 2;
+constexpr uint32_t kJsonStringRowsStateWords = 4;  // per job: lowest offender, final state, depth, first ']'
 struct JsonStringJob {
     const uint8_t* src;
     uint8_t* dst;              // null for validate
-    const uint32_t* row_ends;  // escape: null for a single string
+    const uint32_t* row_ends;  // escape: null for a single string. unescape rows: the row ends to write
     uint64_t cap;
-    uint32_t n, rows;
+    uint32_t n, rows;          // unescape rows: rows is row_cap
     uint32_t quote;                 // escape without rows: 1 = surrounding quotes
     uint32_t first_chunk, nchunks;  // nchunks = ceil(n / kJsonStringChunkBytes), may be 0
     uint32_t first_rblock;          // ceil(rows / kJsonStringBlockRows) row blocks
@@ -780,21 +823,29 @@ struct JsonStringResult {
     uint32_t first_bad;  // with err 1
     int32_t err;         // 0, 1, 3, 4 (the source changed between two passes; dst may be partly written)
 };
+struct JsonStringRowsResult {
+    uint64_t len;  // decoded bytes (with err 3: what the text holds)
+    uint32_t rows, first_bad, depth;
+    int32_t err;  // 0, 1, 3, 4
+};
 struct JsonStringTables {
     const JsonStringJob* jobs = nullptr;  // pinned host
     int njobs = 0;
     JsonStringJob* jobs_dev = nullptr;    // njobs
     uint32_t nchunks = 0, nrblocks = 0, ngroups = 0;  // of all jobs
-    uint32_t* prefix = nullptr;  // nchunks + 1 (escape, unescape)
+    uint32_t* prefix = nullptr;  // nchunks + 1 (escape, unescape), 2 * (nchunks + 1) (unescape rows)
     uint32_t* groups = nullptr;  // ngroups (escape with rows)
-    uint32_t* info = nullptr;    // nchunks * kJsonStringInfoWords (unescape)
+    uint32_t* info = nullptr;    // nchunks * kJsonStringInfoWords (unescape), * kJsonStringRowsInfoWords (rows)
     uint32_t* bad = nullptr;     // njobs
     int32_t* ok = nullptr;       // njobs (escape, unescape)
+    uint32_t* state = nullptr;   // njobs * kJsonStringRowsStateWords (unescape rows)
     JsonStringResult* res = nullptr;  // njobs, pinned host
+    JsonStringRowsResult* rows_res = nullptr;  // njobs, pinned host (unescape rows, in place of res)
 };
 int LaunchJsonStringEscape(const JsonStringTables& t, hipStream_t s);
 int LaunchJsonStringUnescape(const JsonStringTables& t, hipStream_t s);
 int LaunchJsonStringValidate(const JsonStringTables& t, hipStream_t s);
+int LaunchJsonStringUnescapeRows(const JsonStringTables& t, hipStream_t s);
 
 // scratch must hold JsonIndexScratchBytes(n).
 size_t JsonIndexScratchBytes(uint64_t n);

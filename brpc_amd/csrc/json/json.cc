@@ -11,6 +11,7 @@
 
 #include "base/decimal_to_double.h"
 #include "base/json_string.h"
+#include "base/json_string_rows.h"
 #include "base/number_text.h"
 
 namespace mrpc {
@@ -192,6 +193,24 @@ int UnescapeStringBody(const char* body, size_t n, std::string* out, uint64_t* f
         p += span;
     }
     return 0;
+}
+
+int UnescapeStringRows(const char* text, size_t n, StringRows* out) {
+    out->bytes.clear();
+    out->row_ends.clear();
+    out->depth = 0;
+    out->first_bad = 0;
+    out->bytes.reserve(json_string_rows::JsonStringRowsMaxBytes(n));
+    const int rc = json_string_rows::WalkStringRows(
+        [&](uint64_t k) { return (uint8_t)text[k]; }, n, [&](uint64_t from, uint64_t len) { out->bytes.append(text + from, len); },
+        [&](const char* p, uint32_t len) { out->bytes.append(p, len); },
+        [&] { out->row_ends.push_back((uint32_t)out->bytes.size()); }, &out->depth, &out->first_bad);
+    if (rc != 0) {
+        out->bytes.clear();
+        out->row_ends.clear();
+        out->depth = 0;
+    }
+    return rc;
 }
 
 size_t Utf8FirstBad(const char* s, size_t n) {

@@ -246,6 +246,20 @@ bool EscapeStringRows(const char* bytes, const uint32_t* row_ends, size_t rows, 
 // (the reader is looser there, or refuses): *first_bad (if given) is the offset
 // of the offending backslash or quote and *out is as it was.
 int UnescapeStringBody(const char* body, size_t n, std::string* out, uint64_t* first_bad = nullptr);
+// The host twin of gpu::DeviceUnescapeJsonStringRows: the inverse of
+// EscapeStringRows. `text` is "r0","r1",... (depth 0) or ["r0","r1",...]
+// (depth 1), JSON whitespace wherever JSON allows it; the grammar and the
+// offsets of refusal are base/json_string_rows.h, one sequential walk. 0: done,
+// bytes holds the decoded strings one after the other, row_ends[r] the bytes
+// in strings 0..r (empty text, whitespace and "[ ]": no row). 1: not decided
+// here (json::Reader decides): first_bad is set, everything else empty and 0.
+struct StringRows {
+    std::string bytes;
+    std::vector<uint32_t> row_ends;
+    uint32_t depth = 0;
+    uint64_t first_bad = 0;
+};
+int UnescapeStringRows(const char* text, size_t n, StringRows* out);
 // The first offset at which no well-formed UTF-8 sequence starts on the walk
 // from 0 (what Python reports as UnicodeDecodeError.start), n when the text
 // is well-formed.

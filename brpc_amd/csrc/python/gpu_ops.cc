@@ -611,6 +611,39 @@ void bind_gpu_ops(py::module_& g) {
         for (const gpu::DeviceJsonUnescapeJob& j : jobs) out.append(py::make_tuple(j.len, j.err, j.first_bad));
         return out;
     }, py::arg("srcs"), py::arg("ns"), py::arg("dsts"), py::arg("caps"), py::arg("device") = 0);
+    // The text of an array of strings -> decoded bytes at dsts[i] and uint32 row
+    // ends at ends[i]: [(len, rows, depth, err, first_bad)]. err 3: len and rows
+    // say what the text holds.
+    g.def("device_json_unescape_rows", [](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& ns,
+                                          const std::vector<uintptr_t>& dsts, const std::vector<uint64_t>& caps,
+                                          const std::vector<uintptr_t>& ends, const std::vector<uint64_t>& row_caps,
+                                          int device) {
+        if (srcs.size() != ns.size() || dsts.size() != ns.size() || caps.size() != ns.size() || ends.size() != ns.size() ||
+            row_caps.size() != ns.size())
+            throw std::invalid_argument("size mismatch");
+        std::vector<gpu::DeviceJsonStringRowsJob> jobs(ns.size());
+        for (size_t i = 0; i < ns.size(); ++i) {
+            jobs[i].src = (const void*)srcs[i];
+            jobs[i].n = ns[i];
+            jobs[i].dst = (void*)dsts[i];
+            jobs[i].cap = caps[i];
+            jobs[i].row_ends = (void*)ends[i];
+            jobs[i].row_cap = row_caps[i];
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceUnescapeJsonStringRows(jobs.data(), (int)jobs.size(), device);
+        }
+        check(rc, "device_json_unescape_rows");
+        py::list out;
+        for (const gpu::DeviceJsonStringRowsJob& j : jobs)
+            out.append(py::make_tuple(j.len, j.rows, j.depth, j.err, j.first_bad));
+        return out;
+    }, py::arg("srcs"), py::arg("ns"), py::arg("dsts"), py::arg("caps"), py::arg("ends"), py::arg("row_caps"),
+       py::arg("device") = 0);
+    g.def("json_string_rows_max_bytes", [](uint64_t n) { return gpu::JsonStringRowsMaxBytes(n); });
+    g.def("json_string_rows_max_rows", [](uint64_t n) { return gpu::JsonStringRowsMaxRows(n); });
     g.def("device_utf8_validate", [](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& ns, int device) {
         if (srcs.size() != ns.size()) throw std::invalid_argument("size mismatch");
         std::vector<gpu::DeviceUtf8Job> jobs(ns.size());

@@ -780,15 +780,64 @@ PYBIND11_MODULE(_native, m) {
         if (PyBytes_AsStringAndSize(data.ptr(), &p, &n) != 0) throw py::error_already_set();
         return json::Utf8FirstBad(p, (size_t)n);
     });
+    // json_unescape_rows: the twin of the device's rows unescaper over the text
+    // of an array of strings, (bytes, row_ends list, depth), or (None,
+    // first_bad) where it leaves the text to json::Reader.
+    m.def("json_unescape_rows", [](py::bytes text) -> py::tuple {
+        char* p = nullptr;
+        Py_ssize_t n = 0;
+        if (PyBytes_AsStringAndSize(text.ptr(), &p, &n) != 0) throw py::error_already_set();
+        json::StringRows rows;
+        if (json::UnescapeStringRows(p, (size_t)n, &rows) != 0) return py::make_tuple(py::none(), rows.first_bad);
+        py::list ends;
+        for (uint32_t e : rows.row_ends) ends.append(e);
+        return py::make_tuple(py::bytes(rows.bytes), ends, rows.depth);
+    });
+    // What json::Reader makes of the text of an array of strings (a text whose
+    // first byte that is no whitespace is not '[' is bracketed first): the list
+    // of bytes, or None when it refuses or an element is no string.
+    m.def("json_reader_string_array", [](py::bytes text) -> py::object {
+        std::string t = (std::string)text;
+        const size_t first = t.find_first_not_of(" \t\n\r");
+        if (first == std::string::npos || t[first] != '[') t = "[" + t + "]";
+        json::Value v;
+        if (!json::Parse(t, &v) || !v.is_array()) return py::none();
+        py::list out;
+        for (const json::Value& e : v.array()) {
+            if (!e.is_string()) return py::none();
+            out.append(py::bytes(e.as_string()));
+        }
+        return out;
+    });
     // The twins between raw buffers (pinned host memory of a benchmark), the
     // GIL released: op 0 escape (quoted; with row_ends the rows form), 1
-    // unescape, 2 validate. Returns the bytes written at dst (validate: the
-    // first bad offset), -1 when the twin refuses or dst is too small.
+    // unescape, 2 validate, 3 unescape rows (row_ends receives up to `rows`
+    // uint32), 4 the same through json::Reader and a concatenation, what a
+    // handler had before the twin. Returns the bytes written at dst (validate:
+    // the first bad offset), -1 when the twin refuses or dst is too small.
     m.def("json_string_twin", [](int op, uintptr_t src, size_t n, uintptr_t dst, size_t cap, uintptr_t row_ends,
                                  size_t rows) -> int64_t {
         py::gil_scoped_release nogil;
         const char* s = reinterpret_cast<const char*>(src);
         if (op == 2) return (int64_t)json::Utf8FirstBad(s, n);
+        if (op == 3 || op == 4) {
+            json::StringRows got;
+            if (op == 3) {
+                if (json::UnescapeStringRows(s, n, &got) != 0) return -1;
+            } else {
+                json::Value v;
+                if (!json::Parse(s, n, &v) || !v.is_array()) return -1;
+                for (const json::Value& e : v.array()) {
+                    if (!e.is_string()) return -1;
+                    got.bytes += e.as_string();
+                    got.row_ends.push_back((uint32_t)got.bytes.size());
+                }
+            }
+            if (got.bytes.size() > cap || got.row_ends.size() > rows) return -1;
+            memcpy(reinterpret_cast<char*>(dst), got.bytes.data(), got.bytes.size());
+            memcpy(reinterpret_cast<char*>(row_ends), got.row_ends.data(), got.row_ends.size() * 4);
+            return (int64_t)got.bytes.size();
+        }
         std::string out;
         if (op == 0 && row_ends) {
             if (!json::EscapeStringRows(s, reinterpret_cast<const uint32_t*>(row_ends), rows, &out)) return -1;

@@ -382,6 +382,70 @@ def json_unescape_string(text):
     return out[:length]
 
 
+def _string_rows_tensors(rows, dev):
+    data = b"".join(rows)
+    ends, total = [], 0
+    for r in rows:
+        total += len(r)
+        ends.append(total)
+    values = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data \
+        else torch.empty(0, dtype=torch.uint8, device=dev)
+    return values, torch.tensor(ends, dtype=torch.int32).to(dev)
+
+
+def json_unescape_string_rows(text, max_bytes=None, max_rows=None):
+    """uint8 device tensor holding the text of an array of JSON strings,
+    ``"r0","r1",...,"rk"`` or ``["r0","r1",...,"rk"]`` with JSON whitespace
+    wherever JSON allows it -> ``(bytes, row_ends)``: a uint8 device tensor of
+    the decoded strings one after the other and an int32 one with
+    ``row_ends[r]`` the bytes in strings 0..r. The inverse of
+    ``json_escape_string(data, row_ends)``, and what
+    ``pb_build_rows(number, bytes, row_ends, "bytes")`` takes for a ``repeated
+    string``. The text never leaves HBM
+    (``gpu::DeviceUnescapeJsonStringRows``); empty text, whitespace and ``[ ]``
+    give no rows. The bytes are not checked for UTF-8: run ``utf8_validate``
+    on them (a concatenation can validate where a row alone would not).
+
+    The outputs are sized for the worst case (``len(text) - 2`` bytes,
+    ``(len(text) + 1) // 3`` rows) unless ``max_bytes`` / ``max_rows`` bound
+    them (ValueError naming what the text takes when it holds more). A text
+    the device leaves to the host (a lone surrogate, a bad escape, anything
+    that is not an array of strings) is fetched and given to the reader
+    (``native.json_reader_string_array``): its result is returned as device
+    tensors, or ValueError raised naming the offset the device reported.
+
+    The coder runs on a pool stream, not on torch's: the caller's current
+    stream is synchronized before the call, and both tensors are complete
+    when this returns."""
+    t = _flat_bytes(text, "text")
+    dev = t.device
+    n = t.numel()
+    worst_bytes = native.gpu.json_string_rows_max_bytes(n)
+    worst_rows = native.gpu.json_string_rows_max_rows(n)
+    cap = worst_bytes if max_bytes is None else min(int(max_bytes), worst_bytes)
+    row_cap = worst_rows if max_rows is None else min(int(max_rows), worst_rows)
+    out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+    ends = torch.empty(max(row_cap, 1), dtype=torch.int32, device=dev)
+    if n == 0:
+        return out[:0], ends[:0]
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (length, rows, _, err, first_bad), = native.gpu.device_json_unescape_rows(
+            [t.data_ptr()], [n], [out.data_ptr() if cap else 0], [cap], [ends.data_ptr() if row_cap else 0], [row_cap],
+            dev.index or 0)
+    if err == 1:
+        lax = native.json_reader_string_array(bytes(t.cpu().numpy()))
+        if lax is None:
+            raise ValueError("json_unescape_string_rows: not an array of JSON strings (offset %d)" % first_bad)
+        return _string_rows_tensors(lax, dev)
+    if err == 3:
+        raise ValueError("json_unescape_string_rows: max_bytes=%d, max_rows=%d is too small (the text takes %d bytes "
+                         "in %d rows)" % (cap, row_cap, length, rows))
+    if err:
+        raise ValueError("json_unescape_string_rows: " + _STRING_ERRORS.get(err, "code %d" % err))
+    return out[:length], ends[:rows]
+
+
 def utf8_validate(data):
     """uint8 device tensor -> None when it is well-formed UTF-8 (the rule a
     protobuf ``string`` and a JSON text carry), else the first offset at which
