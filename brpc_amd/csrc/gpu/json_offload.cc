@@ -16,6 +16,7 @@
 
 #include "base/decimal_to_double.h"
 #include "base/flags.h"
+#include "base/number_print.h"
 #include "base/shortest_double.h"
 #include "base/time.h"
 #include "gpu/gpu.h"
@@ -234,6 +235,88 @@ int PrintFloatsOnDevice(const void* values, size_t n, uint32_t kind, std::string
     job.cap = cap;
     if (DevicePrintFloatArrays(&job, 1, device) != 0 || job.err != 0 || job.len > cap) return -1;
     out->assign(text.p, (size_t)job.len);
+    return 0;
+}
+
+uint64_t NumberPrintWorstCaseBytes(uint32_t kind, uint64_t count, uint64_t rows) {
+    return number_print::WorstCaseBytes(kind, count, rows);
+}
+
+uint32_t JsonNumberPrintChunkElems() { return kJsonNumberPrintChunkElems; }
+
+int DevicePrintNumbers(DeviceNumberPrintJob* jobs, int n, int device) {
+    namespace np = number_print;
+    if (n <= 0) return 0;
+    if (!jobs || device < 0) return -1;
+    // refuse what must not reach a kernel; count the chunks and row blocks of the rest
+    uint64_t nchunks = 0, nrow_blocks = 0;
+    bool any_float = false;
+    std::vector<int> live;  // the jobs that go to the device, in order
+    auto overlaps = [](const void* a, uint64_t an, const void* b, uint64_t bn) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return an > 0 && bn > 0 && x < y + bn && y < x + an;
+    };
+    for (int i = 0; i < n; ++i) {
+        DeviceNumberPrintJob& j = jobs[i];
+        j.len = 0;
+        j.first_bad = np::kNone;
+        j.err = 0;
+        if (!np::KindValid(j.kind) || (j.row_ends == nullptr) != (j.rows == 0)) {
+            j.err = 2;
+            continue;
+        }
+        if (j.count == 0 && !j.row_ends && !j.brackets) continue;
+        const uint64_t eb = np::ElemBytes(j.kind);
+        if ((!j.src && j.count > 0) || !j.dst || ((uintptr_t)j.src & (eb - 1)) != 0 || ((uintptr_t)j.row_ends & 3) != 0 ||
+            np::WorstCaseBytes(j.kind, j.count, j.rows) > 0xFFFFFFFFull ||
+            overlaps(j.dst, j.cap, j.src, j.count * eb) || overlaps(j.dst, j.cap, j.row_ends, j.rows * 4)) {
+            j.err = 2;
+            continue;
+        }
+        nchunks += std::max<uint64_t>(1, (j.count + kJsonNumberPrintChunkElems - 1) / kJsonNumberPrintChunkElems);
+        nrow_blocks += (j.rows + kJsonNumberPrintChunkElems - 1) / kJsonNumberPrintChunkElems;
+        any_float |= np::KindIsFloat(j.kind);
+        live.push_back(i);
+    }
+    if (live.empty()) return 0;
+    if (nchunks > 0x3FFFFFFFull || nrow_blocks > 0x3FFFFFFFull) return -1;  // one grid each; the tables are indexed with int
+    const int nlive = (int)live.size();
+    const size_t jobs_bytes = live.size() * sizeof(JsonNumberPrintJob);
+    PinnedBlock tables(jobs_bytes + live.size() * sizeof(JsonNumberPrintResult));
+    HbmBlock words((size_t)(nchunks + 1 + live.size()) * sizeof(uint32_t), device);  // the prefix, then bad[]
+    HbmBlock digits(any_float ? (size_t)nchunks * kJsonNumberPrintChunkElems * sizeof(shortest_double::Decimal) : 16,
+                    device);
+    if (!tables || !words || !digits) return -1;
+    JsonNumberPrintJob* tj = tables.as<JsonNumberPrintJob>();
+    JsonNumberPrintResult* tr = reinterpret_cast<JsonNumberPrintResult*>(tables.p + jobs_bytes);
+    uint32_t chunk = 0, row_block = 0;
+    for (int k = 0; k < nlive; ++k) {
+        const DeviceNumberPrintJob& j = jobs[live[k]];
+        const uint32_t nc = (uint32_t)std::max<uint64_t>(
+            1, (j.count + kJsonNumberPrintChunkElems - 1) / kJsonNumberPrintChunkElems);
+        const uint32_t nrb = (uint32_t)((j.rows + kJsonNumberPrintChunkElems - 1) / kJsonNumberPrintChunkElems);
+        const uint32_t form = j.row_ends ? np::kNested : j.brackets ? np::kBracketed : np::kBare;
+        tj[k] = JsonNumberPrintJob{j.src, j.row_ends, static_cast<uint8_t*>(j.dst), j.cap, (uint32_t)j.count,
+                                   (uint32_t)j.rows, j.kind, form, chunk, nc, row_block, nrb};
+        tr[k] = JsonNumberPrintResult{0, np::kNone, 0};
+        chunk += nc;
+        row_block += nrb;
+    }
+    JsonNumberPrintTables t;
+    t.jobs = tj;
+    t.njobs = nlive;
+    t.nchunks = chunk;
+    t.nrow_blocks = row_block;
+    t.prefix = words.as<uint32_t>();
+    t.bad = words.as<uint32_t>() + nchunks + 1;
+    t.digits = any_float ? digits.p : nullptr;
+    t.res = tr;
+    if (RunOnPoolStream(device, [&](hipStream_t s) { return LaunchJsonNumberPrint(t, s); }) != 0) return -1;
+    for (int k = 0; k < nlive; ++k) {
+        jobs[live[k]].len = tr[k].len;
+        jobs[live[k]].first_bad = tr[k].first_bad;
+        jobs[live[k]].err = tr[k].err;
+    }
     return 0;
 }
 

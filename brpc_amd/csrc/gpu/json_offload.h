@@ -155,6 +155,56 @@ int DeviceParseNumberText(DeviceNumberTextJob* jobs, int n, int device);
 // Bytes of text one workgroup takes (tests aim at its edges).
 uint32_t JsonTextChunkBytes();
 
+// ---- number arrays and nested number rows as JSON text, the inverse of
+// DeviceParseNumberText: `count` elements of one kind plus an optional table
+// of row ends (the pair DeviceParseNumberText, DeviceSplitRows and
+// DeviceBuildRows use: row_ends[r] = the elements in rows 0..r) become
+//   row_ends null, brackets false   v,v,...,v
+//   row_ends null, brackets true    [v,v,...,v]          "[]" for count 0
+//   row_ends given                  [[v,..],[v,..],..]   brackets ignored
+// with no whitespace. Kinds: gpu::PbRunKind 0..6 (int32 and sint32, uint32,
+// int64 and sint64, uint64 print as the decimal number of their type, never
+// as a wire form; bool reads one byte per element, nonzero prints true) and
+// kJsonFloat32 / kJsonFloat64, printed exactly as DevicePrintFloatArrays
+// prints them. Rows are not empty, as DeviceParseNumberText refuses an empty
+// row. json::FormatNumberRows is the host twin: the same rules
+// (base/number_print.h), the same bytes, the same verdicts.
+struct DeviceNumberPrintJob {
+    const void* src = nullptr;  // device or pinned host; naturally aligned (1 / 4 / 8 bytes)
+    uint64_t count = 0;         // elements
+    uint32_t kind = 0;
+    const uint32_t* row_ends = nullptr;  // device or pinned host, `rows` entries; the host never reads it
+    uint64_t rows = 0;
+    bool brackets = false;
+    void* dst = nullptr;  // device-writable, cap bytes
+    uint64_t cap = 0;
+    uint64_t len = 0;  // out: text size (with err 3: the size it needs)
+    // out, with err 1: the lowest row r with row_ends[r] <= row_ends[r - 1]
+    // (row_ends[-1] = 0), row_ends[r] > count, or r the last row and
+    // row_ends[r] != count. Found on the device.
+    uint32_t first_bad = 0xFFFFFFFFu;
+    // out: 0 printed; 1 bad row_ends (dst untouched); 2 refused before any
+    // launch (a null src where elements are read, a null dst where bytes are
+    // written, a kind there is not, a src not naturally aligned, a row_ends
+    // not 4-byte aligned, rows without row_ends, row_ends without rows, a dst
+    // that overlaps src or row_ends, a worst case above 2^32 - 1 bytes); 3
+    // longer than cap (dst untouched); 4 the source changed between the
+    // passes: a chunk's text was not the size measured for it (nothing of
+    // that chunk written)
+    int err = 0;
+};
+// Most bytes the text of `count` elements in `rows` rows (0: a flat form) can
+// take; always suffices as a cap. 0 for a kind there is not.
+uint64_t NumberPrintWorstCaseBytes(uint32_t kind, uint64_t count, uint64_t rows);
+// All jobs share one launch sequence (size, rows, prefix, place) on a pool
+// stream and one fiber-friendly wait; the host reads nothing but the result
+// words. Returns -1 only on a device error; per-job codes in jobs[i].err. A
+// flat job of count 0 without brackets writes nothing and launches nothing
+// (len 0, err 0).
+int DevicePrintNumbers(DeviceNumberPrintJob* jobs, int n, int device);
+// Elements one workgroup takes, and rows (tests aim at its edges).
+uint32_t JsonNumberPrintChunkElems();
+
 struct GpuJsonStats {
     // json2pb number arrays (floats) parsed on the device; fallbacks: arrays the device declined
     int64_t number_arrays = 0, number_elems = 0, number_array_fallbacks = 0, number_redo_elems = 0;

@@ -567,6 +567,70 @@ struct JsonFloatTables {
 };
 int LaunchJsonFloatPrint(const JsonFloatTables& t, hipStream_t s);
 
+// JSON number arrays and nested number rows
+// (gpu/json_number_print_kernels.hip): `count` elements of one kind in device
+// (or pinned host) memory, PbRunKind 0..6 or JSON_FLOAT32 / JSON_FLOAT64,
+// become "v,v,...,v", "[v,v,...,v]" or, with a table of row ends (row_ends[r]
+// = the elements in rows 0..r, no row empty), "[[v,..],[v,..],..]" in device
+// memory: the inverse of LaunchJsonNumberText. The rules, the punctuation
+// among them, are base/number_print.h, the code json::FormatNumberRows runs.
+// The elements are cut into chunks of kJsonNumberPrintChunkElems, a lane per
+// element, and the row ends into blocks of as many rows, a lane per row; a
+// chunk's text holds the punctuation in front of each of its elements ("[[",
+// "," or "],[") and, behind the job's last element, its "]]". All jobs share
+// four launches on one stream, ordered by the launches alone:
+//   size    a workgroup per chunk: each element's text size (a float's digits
+//           are kept as a 16-byte Decimal in digits[chunk * 256 + lane], as
+//           the float printer keeps them; integers and bools keep nothing)
+//           plus its punctuation; the chunk's sum goes to prefix[chunk]
+//           (prefix: device memory, nchunks + 1 entries; the last gets 0).
+//           The row starts inside a chunk are found by one lower-bound search
+//           of row_ends for the chunk's first element, the same in every
+//           lane, and a look at the <= 256 entries from there on, which are
+//           all that can fall into the chunk when the table ascends. The
+//           first chunk of a job also sets bad[job] to 0xFFFFFFFF.
+//   rows    a workgroup per row block: row r is bad when row_ends[r] <=
+//           row_ends[r - 1], row_ends[r] > count, or r is the last row and
+//           row_ends[r] != count; atomicMin of r into bad[job]. Not launched
+//           when no job has rows.
+//   prefix  LaunchPbRunPrefix scans the sizes
+//   place   a workgroup per chunk: a job with a bad row (err 1, first_bad) or
+//           longer than its cap (err 3, len the size needed) is marked by its
+//           first chunk and gets nothing written; else the chunk's text is
+//           laid out in LDS and leaves with 16-byte stores at dst +
+//           (prefix[chunk] - prefix[first]). A chunk whose text is not the
+//           size the size pass measured writes nothing and marks err 4.
+// A job has at least one chunk: "[]" is a chunk of no elements. Nothing is
+// quadratic: a lane reads its element, at most one row end in the chunk
+// passes and two in the rows pass, and the search is logarithmic in rows.
+constexpr uint32_t kJsonNumberPrintChunkElems = 256;
+struct JsonNumberPrintJob {
+    const void* src;           // device-readable, naturally aligned; null only with count 0
+    const uint32_t* row_ends;  // device-readable; null unless form 2
+    uint8_t* dst;              // device-writable, never null
+    uint64_t cap;
+    uint32_t count, rows;
+    uint32_t kind;
+    uint32_t form;  // number_print::Form: 0 bare, 1 bracketed, 2 nested
+    uint32_t first_chunk, nchunks;        // nchunks = max(1, ceil(count / 256))
+    uint32_t first_row_block, nrow_blocks;  // nrow_blocks = ceil(rows / 256)
+};
+struct JsonNumberPrintResult {
+    uint64_t len;        // text size (also with err 3); 0 with err 1
+    uint32_t first_bad;  // 0xFFFFFFFF before the launch; with err 1 the lowest bad row
+    int32_t err;         // zero before the launch; 1, 3 or 4 afterwards when the job failed
+};
+struct JsonNumberPrintTables {
+    const JsonNumberPrintJob* jobs = nullptr;  // device-readable (pinned host)
+    int njobs = 0;
+    uint32_t nchunks = 0, nrow_blocks = 0;
+    uint32_t* prefix = nullptr;  // device memory, nchunks + 1 entries
+    uint32_t* bad = nullptr;     // device memory, njobs entries
+    void* digits = nullptr;      // device memory, nchunks * 256 * 16 bytes; null when no job prints floats
+    JsonNumberPrintResult* res = nullptr;  // device-writable (pinned host), njobs
+};
+int LaunchJsonNumberPrint(const JsonNumberPrintTables& t, hipStream_t s);
+
 // JSON structural index (gpu/json_kernels.hip): out_pos receives, in order,
 // the byte offsets of every unescaped '"' and of every { } [ ] : , outside
 // strings; count_dev the number found (positions past max_out are dropped

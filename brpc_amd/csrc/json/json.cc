@@ -2,6 +2,7 @@
 
 #include <charconv>
 
+#include <algorithm>
 #include <atomic>
 
 #include <cmath>
@@ -12,7 +13,9 @@
 #include "base/decimal_to_double.h"
 #include "base/json_string.h"
 #include "base/json_string_rows.h"
+#include "base/number_print.h"
 #include "base/number_text.h"
+#include "base/shortest_double.h"
 
 namespace mrpc {
 namespace json {
@@ -606,6 +609,56 @@ bool ParseNumberText(const char* text, size_t n, uint32_t mode, NumberText* out,
     }
     out->row_ends.resize(v.rows);
     return true;
+}
+
+int FormatNumberRows(const void* values, uint64_t count, uint32_t kind, const uint32_t* row_ends, uint64_t rows,
+                     bool brackets, std::string* out, uint32_t* first_bad) {
+    namespace np = number_print;
+    namespace sd = shortest_double;
+    if (first_bad) *first_bad = np::kNone;
+    if (!np::KindValid(kind) || (!values && count > 0) || ((uintptr_t)values & (np::ElemBytes(kind) - 1)) != 0 ||
+        (row_ends == nullptr) != (rows == 0) || np::WorstCaseBytes(kind, count, rows) > 0xFFFFFFFFull)
+        return 2;
+    const uint32_t form = row_ends ? np::kNested : brackets ? np::kBracketed : np::kBare;
+    uint32_t prev = 0;
+    for (uint64_t r = 0; r < rows; ++r) {  // in row order, so the first row found wanting is the lowest
+        if (np::RowEndBad(prev, row_ends[r], r, rows, count)) {
+            if (first_bad) *first_bad = (uint32_t)r;
+            return 1;
+        }
+        prev = row_ends[r];
+    }
+    if (count == 0) {
+        if (form == np::kBracketed) out->append("[]");
+        return 0;
+    }
+    const size_t before = out->size();
+    size_t used = before;
+    uint64_t next_row = 0;  // the row whose end is looked for
+    for (uint64_t i = 0; i < count; ++i) {
+        if (out->size() - used < np::kMaxLead + np::kMaxElemChars + np::kMaxTrail)
+            out->resize(used + std::max<size_t>(4096, (count - i) * 8) + np::kMaxLead + np::kMaxElemChars + np::kMaxTrail);
+        char* o = &(*out)[used];
+        bool row_start = false;
+        if (form == np::kNested && i > 0 && row_ends[next_row] == i) {
+            row_start = true;
+            ++next_row;
+        }
+        o += np::FormatLead(form, i == 0, row_start, o);
+        if (kind == np::kBool) {
+            o += np::FormatBool(static_cast<const uint8_t*>(values)[i] != 0, o);
+        } else if (kind == np::kFloat32) {
+            o += sd::FormatJsonDoubleBits(sd::WidenFloatBits(static_cast<const uint32_t*>(values)[i]), o);
+        } else if (kind == np::kFloat64) {
+            o += sd::FormatJsonDoubleBits(static_cast<const uint64_t*>(values)[i], o);
+        } else {
+            o += np::FormatInteger(np::LoadInteger(values, i, kind), o);
+        }
+        o += np::FormatTrail(form, i + 1 == count, o);
+        used = (size_t)(o - out->data());
+    }
+    out->resize(used);
+    return 0;
 }
 
 namespace {

@@ -218,6 +218,22 @@ struct NumberText {
 // Returns err == 0.
 bool ParseNumberText(const char* text, size_t n, uint32_t mode, NumberText* out, bool exact = true,
                      bool nested_ok = true);
+// The host twin of gpu::DevicePrintNumbers (gpu/json_offload.h), the inverse
+// of ParseNumberText: `count` elements of one kind (gpu::PbRunKind 0..6: the
+// integers as the decimal number of their type, a bool byte as true / false;
+// 8 / 9: a float / double as FormatFloatArray prints it) appended to *out as
+//   row_ends null, brackets false   v,v,...,v
+//   row_ends null, brackets true    [v,v,...,v]          ("[]" for count 0)
+//   row_ends given (rows entries)   [[v,..],[v,..],..]   brackets ignored
+// with no whitespace; the rules are base/number_print.h for both. Returns the
+// device's codes: 0 printed; 1 a malformed table of row ends, *first_bad (if
+// given) the lowest row r with row_ends[r] <= row_ends[r - 1], row_ends[r] >
+// count, or r the last row and row_ends[r] != count; 2 refused (a kind there
+// is not, null values with count > 0, values not naturally aligned, rows
+// without row_ends or row_ends without rows, a worst case above 2^32 - 1).
+// Nothing is appended on a code other than 0.
+int FormatNumberRows(const void* values, uint64_t count, uint32_t kind, const uint32_t* row_ends, uint64_t rows,
+                     bool brackets, std::string* out, uint32_t* first_bad = nullptr);
 // Test and benchmark hook: false makes the reader parse number arrays element
 // by element with std::from_chars, as it did before packed numbers (the DOM
 // is the same either way; only storage and speed differ). Default true.

@@ -387,6 +387,48 @@ void bind_gpu_ops(py::module_& g) {
         return out;
     }, py::arg("srcs"), py::arg("counts"), py::arg("kinds"), py::arg("dsts"), py::arg("caps"), py::arg("device") = 0);
     g.def("json_float_worst_case", &gpu::FloatPrintWorstCaseBytes);
+    // Number arrays (kinds 0..6, 8, 9) in device memory -> JSON text at dst
+    // (cap bytes of device memory): "v,..,v", "[v,..,v]" (brackets) or, with
+    // a table of row ends in device memory (row_ends != 0, rows entries),
+    // "[[v,..],[v,..],..]"; all jobs in one launch sequence
+    // (gpu::DevicePrintNumbers): [(len, first_bad, err)] per job; err 0
+    // printed, 1 bad row ends (first_bad the lowest bad row), 2 refused before
+    // any launch, 3 longer than cap (len = the size needed), 4 the source
+    // changed between the passes.
+    g.def("device_json_print_numbers", [](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& counts,
+                                          const std::vector<uint32_t>& kinds, const std::vector<uintptr_t>& row_ends,
+                                          const std::vector<uint64_t>& rows, const std::vector<bool>& brackets,
+                                          const std::vector<uintptr_t>& dsts, const std::vector<uint64_t>& caps,
+                                          int device) {
+        const size_t n = counts.size();
+        if (srcs.size() != n || kinds.size() != n || row_ends.size() != n || rows.size() != n ||
+            brackets.size() != n || dsts.size() != n || caps.size() != n)
+            throw std::invalid_argument("size mismatch");
+        std::vector<gpu::DeviceNumberPrintJob> jobs(n);
+        for (size_t i = 0; i < n; ++i) {
+            jobs[i].src = (const void*)srcs[i];
+            jobs[i].count = counts[i];
+            jobs[i].kind = kinds[i];
+            jobs[i].row_ends = (const uint32_t*)row_ends[i];
+            jobs[i].rows = rows[i];
+            jobs[i].brackets = brackets[i];
+            jobs[i].dst = (void*)dsts[i];
+            jobs[i].cap = caps[i];
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DevicePrintNumbers(jobs.data(), (int)jobs.size(), device);
+        }
+        check(rc, "device_json_print_numbers");
+        py::list out;
+        for (const gpu::DeviceNumberPrintJob& j : jobs) out.append(py::make_tuple(j.len, j.first_bad, j.err));
+        return out;
+    }, py::arg("srcs"), py::arg("counts"), py::arg("kinds"), py::arg("row_ends"), py::arg("rows"),
+       py::arg("brackets"), py::arg("dsts"), py::arg("caps"), py::arg("device") = 0);
+    g.def("json_number_print_worst_case", &gpu::NumberPrintWorstCaseBytes, py::arg("kind"), py::arg("count"),
+          py::arg("rows") = 0);
+    g.def("json_number_print_chunk_elems", &gpu::JsonNumberPrintChunkElems);
     // Host floats / doubles (their memory image) -> the same text through the
     // device (gpu::PrintFloatsOnDevice: pinned stage, one wait).
     g.def("json_print_floats", [](py::bytes values, uint64_t n, uint32_t kind, int device) {

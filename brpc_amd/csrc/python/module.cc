@@ -9,6 +9,7 @@
 #include "base/base64.h"
 #include "base/crc32c.h"
 #include "base/decimal_to_double.h"
+#include "base/number_print.h"
 #include "base/util.h"
 #include "builtin/cpu_profiler.h"
 #include "base/snappy.h"
@@ -665,6 +666,39 @@ PYBIND11_MODULE(_native, m) {
         return py::make_tuple(r.err, r.depth, r.count, r.rows, r.first_bad, py::bytes(r.out), py::bytes(r.classes),
                               r.row_ends);
     }, py::arg("text"), py::arg("mode"), py::arg("exact") = true, py::arg("nested") = true);
+    // The host twin of gpu::DevicePrintNumbers (json::FormatNumberRows):
+    // `values` is the memory image of `count` elements of `kind` (0..6, 8, 9),
+    // row_ends None (a flat form, bracketed or bare), a list, or the memory
+    // image of a uint32 array as bytes (an empty one: row ends without rows)
+    // -> (err, first_bad, text); the text is empty on a code other than 0.
+    m.def("json_format_number_rows", [](py::bytes values, uint64_t count, uint32_t kind, py::object row_ends_obj,
+                                        bool brackets) {
+        std::vector<uint32_t> row_ends;
+        const bool nested = !row_ends_obj.is_none();
+        if (nested && py::isinstance<py::bytes>(row_ends_obj)) {
+            const std::string image = row_ends_obj.cast<std::string>();
+            if (image.size() % 4) throw std::invalid_argument("row_ends must hold whole uint32 entries");
+            row_ends.resize(image.size() / 4);
+            if (!image.empty()) memcpy(row_ends.data(), image.data(), image.size());
+        } else if (nested) {
+            row_ends = row_ends_obj.cast<std::vector<uint32_t>>();
+        }
+        const std::string data = values;
+        // a kind there is not is the twin's to refuse
+        if (number_print::KindValid(kind) && data.size() / number_print::ElemBytes(kind) < count)
+            throw std::invalid_argument("values must hold count elements");
+        // a std::string's buffer need not be aligned for 8-byte elements
+        std::vector<uint64_t> aligned(data.size() / 8 + 1);
+        memcpy(aligned.data(), data.data(), data.size());
+        const size_t rows = row_ends.size();
+        row_ends.push_back(0);  // data() of an empty table is still a table
+        std::string text;
+        uint32_t first_bad = 0;
+        const int err = json::FormatNumberRows(aligned.data(), count, kind, nested ? row_ends.data() : nullptr, rows,
+                                               brackets, &text, &first_bad);
+        return py::make_tuple(err, first_bad, py::bytes(text));
+    }, py::arg("values"), py::arg("count"), py::arg("kind"), py::arg("row_ends") = py::none(),
+       py::arg("brackets") = true);
     // The host twin of gpu::DeviceBuildRows (pb::SerializeRows): `values`
     // holds the elements of all rows in the kind's vector layout, row_ends[r]
     // the elements in rows 0..r (a list, or the memory image of a uint32

@@ -2,6 +2,8 @@
 http+json bodies (the reference parses them on the CPU through rapidjson,
 src/json2pb/json_to_pb.cpp). Returns the byte offsets of every unescaped
 quote and of every ``{ } [ ] : ,`` outside strings, in order."""
+import re
+
 import torch
 
 from ..native import native
@@ -91,6 +93,7 @@ def json_print_floats(values):
 
 
 _PARSE_MODES = {torch.float64: 1, torch.float32: 2}
+_INT_RANGES = {torch.int32: (-(1 << 31), (1 << 31) - 1), torch.int64: (-(1 << 63), (1 << 63) - 1)}
 _REDO_CAP = 64
 
 
@@ -106,14 +109,17 @@ def _redo_text(t, offset):
         size *= 2
 
 
-def _parse_number_text(name, text, dtype, max_elems, nested):
+def _parse_number_text(name, text, dtype, max_elems, nested, ints=False):
     """One call of gpu::DeviceParseNumberText on `text`: (values, depth,
-    row_ends or None). The redo elements are repaired from their offsets."""
+    row_ends or None). The redo elements are repaired from their offsets.
+    ints: the `numbers` mode, every element checked to be an integer of
+    `dtype`."""
     require_gpu_tensor(text, "text")
     if text.dtype != torch.uint8:
         raise TypeError("text must be uint8")
-    if dtype not in _PARSE_MODES:
-        raise TypeError("dtype must be float32 or float64, not %s" % dtype)
+    if dtype not in (_INT_RANGES if ints else _PARSE_MODES):
+        raise TypeError("dtype must be %s, not %s" % ("int32 or int64" if ints else "float32 or float64", dtype))
+    mode = 0 if ints else _PARSE_MODES[dtype]
     dev = text.device
     t = text.contiguous().view(-1)
     n = t.numel()
@@ -124,7 +130,9 @@ def _parse_number_text(name, text, dtype, max_elems, nested):
     # an element and its comma take two bytes at least; a row "[v]," four
     cap = (n + 1) // 2 if max_elems is None else int(max_elems)
     row_cap = min(n // 4 + 1, cap) if nested else 0
-    out = torch.empty(max(cap, 1), dtype=dtype, device=dev)
+    # numbers mode: 8 bytes of payload per element and a class byte
+    out = torch.empty(max(cap, 1), dtype=torch.int64 if ints else dtype, device=dev)
+    classes = torch.zeros(max(cap, 1) if ints else 0, dtype=torch.uint8, device=dev)
     row_ends = torch.empty(max(row_cap, 1), dtype=torch.int32, device=dev) if nested else None
     redo_cap = _REDO_CAP
     with torch.cuda.device(dev):
@@ -132,7 +140,7 @@ def _parse_number_text(name, text, dtype, max_elems, nested):
         while True:
             redo = torch.empty(2 * redo_cap, dtype=torch.int32, device=dev)
             (err, depth, count, rows, n_redo, first_bad), = native.gpu.device_json_parse_text(
-                [t.data_ptr()], [n], [_PARSE_MODES[dtype]], [out.data_ptr()], [0], [cap],
+                [t.data_ptr()], [n], [mode], [out.data_ptr()], [classes.data_ptr() if ints else 0], [cap],
                 [row_ends.data_ptr() if nested else 0], [row_cap], [redo.data_ptr()], [redo_cap], dev.index or 0)
             if err != 3:
                 break
@@ -143,13 +151,71 @@ def _parse_number_text(name, text, dtype, max_elems, nested):
         raise ValueError("%s: more than max_elems=%d elements (the text holds %d)" % (name, cap, count))
     if err:
         raise ValueError("%s: refused (bad arguments, code %d)" % (name, err))
-    if n_redo:
+    if ints:
+        pairs = (redo[:2 * n_redo].view(-1, 2).cpu().to(torch.int64) & 0xFFFFFFFF).tolist()
+        _check_ints(name, t, dtype, out[:count], classes[:count], pairs)
+        if dtype != torch.int64:
+            return out[:count].to(dtype), depth, (row_ends[:rows] if depth == 2 else None)
+    elif n_redo:
         pairs = redo[:2 * n_redo].view(-1, 2).cpu().to(torch.int64) & 0xFFFFFFFF
         vals = [native.json_parse_double(_redo_text(t, off)) for off in pairs[:, 1].tolist()]
         out[pairs[:, 0].to(dev)] = torch.tensor(vals, dtype=torch.float64).to(dtype).to(dev)  # narrowed on the host
     # the worst case is many times the result: do not pin it behind a view
     values = out[:count] if 2 * count >= out.numel() else out[:count].clone()
     return values, depth, (row_ends[:rows] if depth == 2 else None)
+
+
+_INTEGER_TEXT = re.compile(rb"-?(0|[1-9][0-9]*)\Z")
+
+
+def _check_ints(name, t, dtype, payload, classes, redo_pairs):
+    """The int64 payloads and class bytes of a numbers-mode parse: ValueError
+    naming the lowest element that is not an integer of `dtype`. The redo
+    elements are classed, and the integers among them filled in, from their
+    text."""
+    lo, hi = _INT_RANGES[dtype]
+    if redo_pairs:
+        idx, vals, cls = [], [], []
+        for i, off in redo_pairs:
+            piece = _redo_text(t, off)
+            v = int(piece) if _INTEGER_TEXT.match(piece) else None
+            c = 2 if v is None or v >= 1 << 64 or v < -(1 << 63) else (1 if v >= 1 << 63 else 0)
+            idx.append(i)
+            vals.append(v if c == 0 else 0)
+            cls.append(c)
+        at = torch.tensor(idx, dtype=torch.int64, device=payload.device)
+        payload[at] = torch.tensor(vals, dtype=torch.int64, device=payload.device)
+        classes[at] = torch.tensor(cls, dtype=torch.uint8, device=payload.device)
+    wrong = classes != 0
+    if dtype == torch.int32:
+        wrong |= (payload < lo) | (payload > hi)
+    first = torch.nonzero(wrong).view(-1)[:1]
+    if first.numel():
+        i = int(first[0])
+        c = int(classes[i])
+        why = ("is not an integer" if c == 2 else "is above INT64_MAX" if c == 1 else "does not fit int32")
+        raise ValueError("%s: element %d %s" % (name, i, why))
+
+
+def _shape_rows(name, values, depth, row_ends, ragged):
+    """What the row parsers return for the (values, depth, row_ends) of one
+    nested parse: a 2-D tensor, or (values, int64 row_ends) when ragged."""
+    if depth != 2:
+        if values.numel():
+            raise ValueError(name + ": the text is not an array of arrays")
+        row_ends = torch.empty(0, dtype=torch.int32, device=values.device)
+    if ragged:
+        return values, row_ends.to(torch.int64)
+    rows = row_ends.numel()
+    if rows == 0:
+        return values.view(0, 0)
+    ends = row_ends.cpu().to(torch.int64)
+    sizes = torch.diff(ends, prepend=torch.zeros(1, dtype=torch.int64))
+    odd = torch.nonzero(sizes != sizes[0]).view(-1)
+    if odd.numel():
+        r = int(odd[0])
+        raise ValueError("%s: row %d has %d elements, row 0 has %d" % (name, r, int(sizes[r]), int(sizes[0])))
+    return values.view(rows, int(sizes[0]))
 
 
 def json_parse_floats(text, dtype=torch.float64, max_elems=None):
@@ -182,7 +248,8 @@ def json_parse_float_rows(text, dtype=torch.float64, ragged=False, max_elems=Non
     float64 / float32 device tensor, one row per inner array: the batch shape
     of http+json model APIs, parsed in HBM by the same single call as
     ``json_parse_floats`` (the device finds the row boundaries too). It
-    round-trips with ``json_print_floats`` applied per row.
+    round-trips with ``json_print_numbers``, which prints the rows back in
+    one call.
 
     Rows of different lengths raise ValueError naming the first row that
     differs from row 0; with ``ragged=True`` the result is ``(values,
@@ -190,22 +257,117 @@ def json_parse_float_rows(text, dtype=torch.float64, ragged=False, max_elems=Non
     number of elements in rows 0..r. ``[ ]`` is a tensor of shape (0, 0)."""
     name = "json_parse_float_rows"
     values, depth, row_ends = _parse_number_text(name, text, dtype, max_elems, True)
-    if depth != 2:
-        if values.numel():
-            raise ValueError(name + ": the text is not an array of arrays")
-        row_ends = torch.empty(0, dtype=torch.int32, device=values.device)
-    if ragged:
-        return values, row_ends.to(torch.int64)
-    rows = row_ends.numel()
-    if rows == 0:
-        return values.view(0, 0)
-    ends = row_ends.cpu().to(torch.int64)
-    sizes = torch.diff(ends, prepend=torch.zeros(1, dtype=torch.int64))
-    odd = torch.nonzero(sizes != sizes[0]).view(-1)
-    if odd.numel():
-        r = int(odd[0])
-        raise ValueError("%s: row %d has %d elements, row 0 has %d" % (name, r, int(sizes[r]), int(sizes[0])))
-    return values.view(rows, int(sizes[0]))
+    return _shape_rows(name, values, depth, row_ends, ragged)
+
+
+def json_parse_ints(text, dtype=torch.int64, max_elems=None):
+    """uint8 device tensor of JSON text ``v,v,...,v`` or ``[v,v,...]`` -> int64
+    / int32 device tensor, the inverse of ``json_print_numbers`` on integers:
+    ``json_parse_floats`` in the parser's ``numbers`` mode, which keeps an
+    integer literal as its int64 instead of making a double of it. The text
+    never leaves HBM.
+
+    Raises ValueError naming the lowest element that is not an integer of
+    ``dtype``: one with a fraction or an exponent (1.5, 1e3), one above
+    INT64_MAX, or with ``dtype=torch.int32`` one outside int32; and, as
+    ``json_parse_floats``, the first element that is not a JSON number. The
+    elements a device lane does not decide (a 25-digit integer) are fetched as
+    text and judged on the host.
+
+    Stream discipline and ``max_elems`` as in ``json_parse_floats``."""
+    return _parse_number_text("json_parse_ints", text, dtype, max_elems, False, ints=True)[0]
+
+
+def json_parse_int_rows(text, dtype=torch.int64, ragged=False, max_elems=None):
+    """uint8 device tensor of JSON text ``[[v,...],[v,...],...]`` of integers
+    -> a 2-D int64 / int32 device tensor, or ``(values, row_ends)`` with
+    ``ragged=True``: ``json_parse_float_rows`` for token ids, labels and
+    masks. It round-trips with ``json_print_numbers``. Refusals as in
+    ``json_parse_ints``."""
+    name = "json_parse_int_rows"
+    values, depth, row_ends = _parse_number_text(name, text, dtype, max_elems, True, ints=True)
+    return _shape_rows(name, values, depth, row_ends, ragged)
+
+
+_NUMBER_KINDS = {torch.int32: 0, torch.int64: 3, torch.bool: 6, torch.float32: 8, torch.float64: 9}
+for _name, _kind in (("uint32", 1), ("uint64", 4)):  # where this torch has them
+    if hasattr(torch, _name):
+        _NUMBER_KINDS[getattr(torch, _name)] = _kind
+
+
+def json_print_numbers(values, row_ends=None, brackets=True):
+    """Device tensor of numbers -> uint8 device tensor of JSON text, the
+    inverse of ``json_parse_float_rows`` / ``json_parse_int_rows``
+    (``gpu::DevicePrintNumbers``); neither the values nor the row ends leave
+    HBM, and the device checks the row ends itself.
+
+    * 1-D ``values``, ``row_ends=None``: ``[v,v,...,v]``, or ``v,v,...,v``
+      with ``brackets=False``.
+    * ``row_ends`` (1-D int32 / int64 device tensor, ``row_ends[r]`` = the
+      elements in rows 0..r, as ``json_parse_float_rows(..., ragged=True)``
+      and ``pb_build_rows`` have it): ``[[v,..],[v,..],..]`` over the
+      flattened values. Rows are not empty. No rows and no values: ``[]``.
+    * 2-D ``values``, ``row_ends=None``: equal rows, one per ``values[r]``.
+
+    int32 / int64 (uint32 / uint64 where torch has them) print as decimal
+    integers, bool as ``true`` / ``false``, float32 / float64 exactly as
+    ``json_print_floats`` prints them. No whitespace is written.
+
+    Raises ValueError naming the lowest bad row when ``row_ends`` does not
+    ascend strictly to ``values.numel()``.
+
+    Stream discipline as in ``json_print_floats``: the printer runs on a pool
+    stream, the caller's current stream is synchronized before the call, and
+    the text is complete when this returns."""
+    name = "json_print_numbers"
+    if isinstance(values, torch.Tensor):
+        values = values.contiguous()  # a transposed batch or a slice of one is welcome
+    require_gpu_tensor(values, "values")
+    if values.dtype not in _NUMBER_KINDS:
+        raise TypeError("values must be one of %s, not %s"
+                        % (", ".join(str(d) for d in _NUMBER_KINDS), values.dtype))
+    dev = values.device
+    kind = _NUMBER_KINDS[values.dtype]
+    if row_ends is None and values.dim() == 2:
+        rows, cols = values.shape
+        if rows and not cols:
+            raise ValueError(name + ": rows must not be empty")
+        row_ends = torch.arange(1, rows + 1, dtype=torch.int64, device=dev) * cols
+    elif row_ends is None and values.dim() != 1:
+        raise ValueError(name + ": values must be 1-D, or 2-D without row_ends")
+    t = values.view(-1)
+    n = t.numel()
+    ends = None
+    if row_ends is not None:
+        if isinstance(row_ends, torch.Tensor):
+            row_ends = row_ends.contiguous()
+        require_gpu_tensor(row_ends, "row_ends")
+        if row_ends.dim() != 1 or row_ends.device != dev or row_ends.dtype not in (torch.int32, torch.int64):
+            raise TypeError("row_ends must be a 1-D int32 or int64 tensor on the device of values")
+        if row_ends.numel() == 0 and n:
+            raise ValueError(name + ": %d values in no rows" % n)
+        if row_ends.numel():
+            # as uint32: what does not fit becomes an end the device refuses
+            ends = row_ends if row_ends.dtype == torch.int32 else row_ends.clamp(0, 0xFFFFFFFF).to(torch.int32)
+        else:
+            brackets = True
+    nrows = ends.numel() if ends is not None else 0
+    if n == 0 and ends is None and not brackets:
+        return torch.empty(0, dtype=torch.uint8, device=dev)
+    cap = native.gpu.json_number_print_worst_case(kind, n, nrows)
+    if cap >= 1 << 32:
+        raise ValueError(name + " handles outputs below 4 GiB")
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (length, first_bad, err), = native.gpu.device_json_print_numbers(
+            [t.data_ptr() if n else 0], [n], [kind], [ends.data_ptr() if nrows else 0], [nrows], [bool(brackets)],
+            [out.data_ptr()], [cap], dev.index or 0)
+    if err == 1:
+        raise ValueError("%s: row_ends[%d] does not ascend strictly to the %d values" % (name, first_bad, n))
+    if err:
+        raise ValueError(name + ": " + PRINT_ERRORS.get(err, "code %d" % err))
+    return out[:length]
 
 
 def base64_encode(data):
