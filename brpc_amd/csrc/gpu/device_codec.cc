@@ -6,6 +6,7 @@
 
 #include "base/buf.h"
 #include "base/flags.h"
+#include "base/pb_records.h"
 #include "base/pb_rows.h"
 #include "base/pool.h"
 #include "gpu/codec_batch.h"
@@ -35,6 +36,7 @@ std::atomic<int64_t> g_encodes{0}, g_enc_bytes{0}, g_enc_out{0}, g_decodes{0}, g
 std::atomic<int64_t> g_built{0}, g_built_fields{0}, g_built_bytes{0}, g_build_err{0};
 std::atomic<int64_t> g_built_row_jobs{0}, g_built_rows{0}, g_built_row_bytes{0};
 std::atomic<int64_t> g_split_row_jobs{0}, g_split_rows{0};
+std::atomic<int64_t> g_built_record_jobs{0}, g_built_records{0}, g_built_record_bytes{0};
 
 uint32_t varint_len(uint64_t v) {
     uint32_t n = 1;
@@ -584,6 +586,183 @@ int BuildDeviceRows(const DeviceRowsJob& job, Buf* out, int device) {
 
 namespace {
 
+static_assert(kDeviceRecordMaxColumns == pb_records::kRecordMaxColumns, "one column limit");
+
+// The job as the rules see it; false when it has no column table to look at.
+bool records_view(const DeviceRecordsJob& j, pb_records::Column* cols, pb_records::Job* out) {
+    if (!j.columns || j.ncols < 1 || j.ncols > kDeviceRecordMaxColumns) return false;
+    for (uint32_t c = 0; c < j.ncols; ++c) {
+        const DeviceRecordColumn& in = j.columns[c];
+        cols[c].inner = in.inner;
+        cols[c].kind = in.kind;
+        cols[c].src = in.src;
+        cols[c].count = in.count;
+        cols[c].row_ends = in.row_ends;
+    }
+    out->number = j.number;
+    out->columns = cols;
+    out->ncols = j.ncols;
+    out->rows = j.rows;
+    return true;
+}
+
+// What the host can check of a records job without reading device memory.
+bool records_job_ok(const DeviceRecordsJob& j) {
+    pb_records::Column cols[pb_records::kRecordMaxColumns];
+    pb_records::Job view;
+    if (!records_view(j, cols, &view) || pb_records::WorstCaseBytes(view) == 0 || !j.dst) return false;
+    for (uint32_t c = 0; c < j.ncols; ++c) {
+        const DeviceRecordColumn& col = j.columns[c];
+        if (((uintptr_t)col.row_ends & 3) != 0) return false;
+        if (col.count > 0 && (!col.src || ((uintptr_t)col.src & (pb_rows::SourceBytes(col.kind) - 1)) != 0)) return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+uint64_t DeviceRecordsWorstCaseBytes(const DeviceRecordsJob& job) {
+    pb_records::Column cols[pb_records::kRecordMaxColumns];
+    pb_records::Job view;
+    return records_view(job, cols, &view) ? pb_records::WorstCaseBytes(view) : 0;
+}
+
+// On a pool stream of its own, as DeviceBuildRows and for its reason.
+int DeviceBuildRecords(DeviceRecordsJob* jobs, int n, int device) {
+    if (n <= 0) return 0;
+    if (!jobs || device < 0) return -1;
+    std::vector<int> live;  // the jobs that go to the device, in order
+    uint64_t nchunks = 0, nrblocks = 0, ngroups = 0, nrows = 0, ncolrows = 0, ncols = 0;
+    for (int i = 0; i < n; ++i) {
+        DeviceRecordsJob& j = jobs[i];
+        j.len = 0;
+        j.first_bad = j.bad_column = 0xFFFFFFFFu;
+        j.err = 0;
+        if (!records_job_ok(j)) {
+            j.err = 2;
+            g_build_err.fetch_add(1, std::memory_order_relaxed);
+            continue;
+        }
+        for (uint32_t c = 0; c < j.ncols; ++c) {
+            const DeviceRecordColumn& col = j.columns[c];
+            nchunks += (col.count + kPbRowsChunkElems - 1) / kPbRowsChunkElems;
+            if (pb_rows::IsVarintKind(col.kind)) ngroups += col.count / kPbRowsGroupElems + 2;
+        }
+        nrblocks += (j.rows + kPbRowsBlockRows - 1) / kPbRowsBlockRows;
+        nrows += j.rows;
+        ncolrows += j.rows * j.ncols;
+        ncols += j.ncols;
+        live.push_back(i);
+    }
+    if (live.empty()) return 0;
+    // one grid per pass, 32-bit table indices
+    if (nchunks > 0x7FFFFFFFull || nrblocks > 0x7FFFFFFFull || ngroups > 0x7FFFFFFFull || ncolrows > 0x7FFFFFFFull) {
+        return -1;
+    }
+    const size_t nlive = live.size();
+    // the most aligned first: jobs, columns and offender words are all 8-byte
+    const size_t jobs_bytes = nlive * sizeof(PbRecordsJob), cols_bytes = (size_t)ncols * sizeof(PbRowsJob);
+    PinnedBlock tables(jobs_bytes + cols_bytes + nlive * sizeof(PbRecordsResult));
+    const size_t words = (size_t)ngroups + (size_t)nrows + 2 * (size_t)ncolrows + (size_t)nrblocks + nlive;
+    HbmBlock scratch(jobs_bytes + cols_bytes + nlive * sizeof(uint64_t) + words * sizeof(uint32_t), device);
+    if (!tables || !scratch) return -1;
+    PbRecordsJob* tj = tables.as<PbRecordsJob>();
+    PbRowsJob* tc = reinterpret_cast<PbRowsJob*>(tj + nlive);
+    PbRecordsResult* tr = reinterpret_cast<PbRecordsResult*>(tc + ncols);
+    PbRecordsTables t;
+    for (size_t k = 0; k < nlive; ++k) {
+        const DeviceRecordsJob& j = jobs[live[k]];
+        PbRecordsJob& o = tj[k];
+        o.dst = static_cast<uint8_t*>(j.dst);
+        o.cap = j.cap;
+        o.rows = (uint32_t)j.rows;
+        o.number = j.number;
+        o.ncols = j.ncols;
+        o.first_col = (uint32_t)t.ncols;
+        o.first_rblock = t.nrblocks;
+        o.first_row = t.nrows;
+        for (uint32_t c = 0; c < j.ncols; ++c) {
+            const DeviceRecordColumn& in = j.columns[c];
+            PbRowsJob& col = tc[t.ncols++];
+            col.src = in.src;
+            col.row_ends = in.row_ends;
+            col.dst = o.dst;
+            col.cap = o.cap;
+            col.count = (uint32_t)in.count;
+            col.rows = o.rows;
+            col.number = j.number;
+            col.inner = in.inner;
+            col.kind = in.kind;
+            col.first_chunk = t.nchunks;
+            col.nchunks = (uint32_t)((in.count + kPbRowsChunkElems - 1) / kPbRowsChunkElems);
+            col.first_rblock = (uint32_t)k;  // a column's: its record job
+            col.first_row = t.ncolrows;
+            col.first_group = t.ngroups;
+            t.nchunks += col.nchunks;
+            t.ncolrows += o.rows;
+            if (pb_rows::IsVarintKind(in.kind)) t.ngroups += col.count / kPbRowsGroupElems + 2;
+        }
+        t.nrblocks += (uint32_t)((j.rows + kPbRowsBlockRows - 1) / kPbRowsBlockRows);
+        t.nrows += o.rows;
+        tr[k] = PbRecordsResult{0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0};
+    }
+    t.jobs = tj;
+    t.njobs = (int)nlive;
+    t.cols = tc;
+    t.jobs_dev = scratch.as<PbRecordsJob>();
+    t.cols_dev = reinterpret_cast<PbRowsJob*>(t.jobs_dev + nlive);
+    t.bad = reinterpret_cast<unsigned long long*>(t.cols_dev + t.ncols);
+    t.groups = reinterpret_cast<uint32_t*>(t.bad + nlive);
+    t.row_size = t.groups + t.ngroups;
+    t.col_pay = t.row_size + t.nrows;
+    t.col_delta = t.col_pay + t.ncolrows;
+    t.block_off = t.col_delta + t.ncolrows;
+    t.res = tr;
+    if (RunOnPoolStream(device, [&](hipStream_t s) { return LaunchPbRecordsBuild(t, s); }) != 0) return -1;
+    for (size_t k = 0; k < nlive; ++k) {
+        DeviceRecordsJob& j = jobs[live[k]];
+        j.len = tr[k].len;
+        j.err = tr[k].err;
+        if (j.err == 1) {
+            j.first_bad = tr[k].first_bad;
+            j.bad_column = tr[k].bad_column;
+        }
+        if (j.err) {
+            g_build_err.fetch_add(1, std::memory_order_relaxed);
+            continue;
+        }
+        g_built_record_jobs.fetch_add(1, std::memory_order_relaxed);
+        g_built_records.fetch_add((int64_t)j.rows, std::memory_order_relaxed);
+        g_built_record_bytes.fetch_add((int64_t)j.len, std::memory_order_relaxed);
+    }
+    return 0;
+}
+
+int BuildDeviceRecords(const DeviceRecordsJob& job, Buf* out, int device) {
+    const uint64_t worst = DeviceRecordsWorstCaseBytes(job);
+    if (!out || worst == 0) {
+        g_build_err.fetch_add(1, std::memory_order_relaxed);
+        return 2;
+    }
+    const size_t cap = (size_t)std::max<uint64_t>(worst, 16);
+    HbmBlock dst(cap, device);
+    if (!dst) return -1;
+    DeviceRecordsJob j = job;
+    j.dst = dst.p;
+    j.cap = cap;
+    const int rc = DeviceBuildRecords(&j, 1, device);
+    if (rc != 0 || j.err != 0) return rc != 0 ? -1 : j.err;
+    ArenaBlock* a = new ArenaBlock{cap, device};
+    if (AppendDevice(out, dst.p, (size_t)j.len, device, free_arena_block, a) != 0) {
+        delete a;
+        return -1;
+    }
+    dst.release();  // the Buf block owns it now
+    return 0;
+}
+
+namespace {
+
 static_assert(kDeviceSplitMaxBytes < (1ull << 28), "the splitter's offender word and row table hold 28-bit offsets");
 
 bool split_job_ok(const DeviceRowsSplitJob& j) {
@@ -711,6 +890,9 @@ DeviceCodecStats GetDeviceCodecStats() {
     s.built_row_jobs = g_built_row_jobs.load();
     s.built_rows = g_built_rows.load();
     s.built_row_bytes = g_built_row_bytes.load();
+    s.built_record_jobs = g_built_record_jobs.load();
+    s.built_records = g_built_records.load();
+    s.built_record_bytes = g_built_record_bytes.load();
     s.built_messages = g_built.load();
     s.built_fields = g_built_fields.load();
     s.built_bytes = g_built_bytes.load();

@@ -149,7 +149,7 @@ int DeviceEncodePackedRuns(DevicePackedEncodeRun* runs, int n, int device);
 // `rows` is number 4, inner 2, kind 8; `blobs` is number 5, inner 0, kind
 // bytes. The wire rules (and the empty-row rules) are base/pb_rows.h;
 // pb::SerializeRows (pb/rows.h) is the host twin. Sub-messages with several
-// fields and rows of rows are not built.
+// fields are DeviceBuildRecords below; rows of rows are not built.
 //
 // The output is a sequence of occurrences of one field, which is a valid
 // message by itself; protobuf concatenation is merge, so a caller composes
@@ -188,6 +188,63 @@ int DeviceBuildRows(DeviceRowsJob* jobs, int n, int device);
 // the worst-case size and appends exactly their bytes to *out as one DEVICE
 // block, as BuildDeviceMessage does. 0, a DeviceRowsJob::err code, or -1.
 int BuildDeviceRows(const DeviceRowsJob& job, Buf* out, int device);
+
+// ---- records: a batch whose elements are sub-messages with several fields,
+// each field a column in device memory:
+//   message Example { repeated int64 input_ids = 1 [packed = true];
+//                     repeated float weights   = 2 [packed = true];
+//                     optional int32 label     = 3;
+//                     optional bytes blob      = 4; }
+//   message Batch   { optional string model = 1; repeated Example examples = 4; }
+// `examples` is number 4 with four columns: two packed ones and a bytes one,
+// each a flat array plus row ends as in DeviceRowsJob, and a scalar one (no
+// row ends, one element per record, always written). The wire rules are
+// base/pb_records.h; pb::SerializeRecords (pb/records.h) is the host twin. A
+// job of one packed or one bytes column is DeviceBuildRows' output byte for
+// byte. As there, the output is a valid message by itself and composes with
+// a BuildDeviceMessage block by concatenation. Only the build side exists:
+// DeviceSplitRows answers 6 for such records (with inner 0 and kind bytes it
+// returns each record's sub-message), and the host parser takes them.
+constexpr uint32_t kDeviceRecordMaxColumns = 8;
+struct DeviceRecordColumn {
+    uint32_t inner = 0;  // the field inside the record, 1 .. 2^29-1; numbers may repeat
+    uint32_t kind = 0;   // as DeviceRowsJob; bytes needs row_ends
+    const void* src = nullptr;           // device; count elements, naturally aligned for the kind
+    uint64_t count = 0;
+    const uint32_t* row_ends = nullptr;  // device, 4-byte aligned, rows entries; null: a scalar column, count == rows
+};
+struct DeviceRecordsJob {
+    uint32_t number = 0;  // the repeated field, 1 .. 2^29-1
+    const DeviceRecordColumn* columns = nullptr;  // host; written into every record in this order
+    uint32_t ncols = 0;                           // 1 .. kDeviceRecordMaxColumns
+    uint64_t rows = 0;                            // >= 1
+    void* dst = nullptr;                          // device, any alignment
+    uint64_t cap = 0;
+    uint64_t len = 0;  // out: serialized size (with err 3: the size it needs)
+    // out, with err 1: the lowest row at which a column's row_ends decreases
+    // (or, at rows - 1, does not end at that column's count), and the lowest
+    // column that offends there
+    uint32_t first_bad = 0xFFFFFFFFu, bad_column = 0xFFFFFFFFu;
+    // out: 0 built; 1 bad table, found on the device (the host never reads a
+    // table); 2 refused before any launch (a null pointer with a nonzero
+    // size, a misaligned src or row_ends, a bad number / inner / kind, bytes
+    // without row_ends, ncols 0 or above 8, a scalar column whose count is
+    // not rows, a worst case of 0); 3 longer than cap; 4 a source or table
+    // changed between passes. With 1 and 3 dst is untouched; no store ever
+    // goes beyond cap.
+    int err = 0;
+};
+// Host only: the bytes a destination needs for any values; 0 when the job
+// would be refused for its fields, columns, rows or sizes.
+uint64_t DeviceRecordsWorstCaseBytes(const DeviceRecordsJob& job);
+// All jobs share one sequence of launches on a pool stream and one wait.
+// Returns -1 only on a device error; per-job codes in jobs[i].err.
+int DeviceBuildRecords(DeviceRecordsJob* jobs, int n, int device);
+// Builds job's records (its dst / cap are ignored) into a fresh arena block
+// of the worst-case size and appends exactly their bytes to *out as one
+// DEVICE block, as BuildDeviceRows does. 0, a DeviceRecordsJob::err code, or
+// -1.
+int BuildDeviceRecords(const DeviceRecordsJob& job, Buf* out, int device);
 
 // ---- and back: a message in device memory that holds such rows (what
 // DeviceBuildRows wrote, or any sender's `repeated Row rows = N`, other
@@ -236,6 +293,7 @@ struct DeviceCodecStats {
     int64_t built_messages = 0, built_fields = 0, built_bytes = 0, build_errors = 0;
     int64_t built_row_jobs = 0, built_rows = 0, built_row_bytes = 0;  // failed row jobs count in build_errors
     int64_t split_row_jobs = 0, split_rows = 0;                       // DeviceSplitRows jobs that ended with code 0
+    int64_t built_record_jobs = 0, built_records = 0, built_record_bytes = 0;  // failed ones count in build_errors
 };
 DeviceCodecStats GetDeviceCodecStats();
 

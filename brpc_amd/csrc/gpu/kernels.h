@@ -406,6 +406,75 @@ struct PbRowsTables {
 };
 int LaunchPbRowsBuild(const PbRowsTables& t, hipStream_t s);
 
+// Record builder: several columns in device memory become the occurrences of
+// one repeated sub-message with several fields (base/pb_records.h has the
+// wire rules; pb::SerializeRecords is the host twin). A column is a
+// PbRowsJob: ragged columns bring a table of row ends, a scalar column has
+// none and element r belongs to record r. The seven launches are the row
+// builder's, over columns where it goes over jobs:
+//   init     copies the job and column tables to device memory, resets each
+//            job's offender word and zeroes the tail groups of each varint
+//            column
+//   size     the row builder's kernel over the column table: one grid over
+//            the chunks of every column of every job
+//   prefix   LaunchPbRunPrefix over groups[]
+//   measure  a lane per record, 256 to a workgroup: for each column the
+//            payload bytes as the difference of two byte prefixes, into
+//            col_pay[] and (the bytes before the row's first element)
+//            col_delta[]; the record's size, header and field headers
+//            included, into row_size[] and the workgroup's sum into
+//            block_off[]. A column whose row end lies before its start, or
+//            whose last end is not its count, goes into bad[] through one
+//            atomic min on row << 4 | column: the lowest row, then the lowest
+//            column
+//   prefix   LaunchPbRunPrefix over block_off[]
+//   heads    a lane per record: row 0's lane writes the job's result; a job
+//            that is malformed (err 1) or longer than its cap (err 3) gets
+//            nothing written here or later. Else the record's header and
+//            every field's header (for a scalar column: its tag) are written
+//            at their offsets and col_delta[] becomes the distance from
+//            "bytes before element e" to "offset of element e in dst"
+//   place    the row builder's place pass (same code) over every column's
+//            chunks, each with its column's delta; err 4 as there
+// The job and column tables are device-readable (pinned host) arrays, res a
+// device-writable one; everything else is device memory.
+struct PbRecordsJob {
+    uint8_t* dst;  // any alignment, never null
+    uint64_t cap;
+    uint32_t rows;  // >= 1
+    uint32_t number;
+    uint32_t ncols, first_col;  // its columns in the column table, 1 .. pb_records::kRecordMaxColumns
+    uint32_t first_rblock;      // as PbRowsJob::first_rblock, with block_off entries at first_rblock + k
+    uint32_t first_row;         // in row_size: rows entries
+};
+// A column is a PbRowsJob with: row_ends null for a scalar column (count ==
+// rows), dst / cap / number / rows the job's, first_chunk and first_group
+// counted over all columns of all jobs, first_row its rows entries in col_pay
+// and col_delta, and first_rblock the index of its record job.
+struct PbRecordsResult {
+    uint64_t len;         // serialized size (also when it did not fit)
+    uint32_t first_bad;   // with err 1
+    uint32_t bad_column;  // with err 1
+    int32_t err;          // 0, 1, 3, 4
+};
+struct PbRecordsTables {
+    const PbRecordsJob* jobs = nullptr;
+    int njobs = 0;
+    const PbRowsJob* cols = nullptr;
+    int ncols = 0;                       // of all jobs
+    PbRecordsJob* jobs_dev = nullptr;    // njobs
+    PbRowsJob* cols_dev = nullptr;       // ncols
+    uint32_t nchunks = 0, nrblocks = 0, ngroups = 0, nrows = 0, ncolrows = 0;  // of all jobs
+    uint32_t* groups = nullptr;          // ngroups
+    uint32_t* row_size = nullptr;        // nrows
+    uint32_t* col_pay = nullptr;         // ncolrows: rows entries per column
+    uint32_t* col_delta = nullptr;       // ncolrows
+    uint32_t* block_off = nullptr;       // nrblocks + njobs
+    unsigned long long* bad = nullptr;   // njobs
+    PbRecordsResult* res = nullptr;      // njobs
+};
+int LaunchPbRecordsBuild(const PbRecordsTables& t, hipStream_t s);
+
 // Row splitter, the inverse: a message in device memory whose field `number`
 // repeats once per row becomes the flat array and the row ends again
 // (base/pb_rows.h has the rules, pb::SplitRows is the host twin). Finding the

@@ -20,6 +20,7 @@
 // the lane walks them) and writes its field rows with 16-byte stores.
 #include <hip/hip_runtime.h>
 
+#include "base/pb_records.h"
 #include "base/pb_rows.h"
 #include "gpu/kernels.h"
 #include "gpu/device_pb.h"
@@ -792,15 +793,24 @@ __global__ void __launch_bounds__(kPbRowsBlockRows) pb_rows_heads_kernel(const P
     row_delta[at] = off + hn - row_delta[at];
 }
 
-// res[j].err = 4 below: a source (or row_ends) changed under the builder's
-// hands, seen as a size that no longer matches or a store that would leave
-// the message.
-__global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRowsJob* __restrict__ jobs, int njobs,
-                                                                    const uint32_t* __restrict__ groups,
-                                                                    const uint32_t* __restrict__ block_off,
-                                                                    const uint32_t* __restrict__ row_delta,
-                                                                    const uint32_t* __restrict__ first_bad,
-                                                                    PbRowsResult* __restrict__ res) {
+// Entry r of a table of row ends. A column of the record builder may come
+// without one (kIota): element r is row r.
+template <bool kIota>
+__device__ __forceinline__ uint32_t rows_end_at(const uint32_t* ends, uint64_t r) {
+    if (kIota && !ends) return (uint32_t)r + 1;
+    return ends[r];
+}
+
+// The place pass of one chunk of a job (or of one column of a record job)
+// whose rows were measured and whose message of `total` bytes fits: delta[r]
+// is the distance from "bytes before element e" to "offset of element e in
+// dst" for row r. *err = 4 below: a source (or row_ends) changed under the
+// builder's hands, seen as a size that no longer matches or a store that
+// would leave the message.
+template <bool kIota>
+__device__ __forceinline__ void rows_place_chunk(const PbRowsJob& job, uint32_t chunk, uint32_t total,
+                                                 const uint32_t* __restrict__ groups,
+                                                 const uint32_t* __restrict__ delta, int32_t* err) {
     __shared__ u32x4 image16[kMsgImage16];
     // few rows: the position of every element in the image (and the total);
     // many rows: the row of every element, relative to the chunk's first
@@ -808,13 +818,8 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
     __shared__ uint32_t wave_tot[kRowsRounds][kRunThreads / 64];
     __shared__ uint32_t wave_max[kRunThreads / 64];
     uint8_t* image = reinterpret_cast<uint8_t*>(image16);
-    const int j = wg::job_of<&PbRowsJob::first_chunk>(jobs, njobs, blockIdx.x);
-    const PbRowsJob job = jobs[j];
-    if (first_bad[j] != kNoRow) return;
-    const uint32_t total = rows_job_total(job, j, block_off);
-    if (total > job.cap) return;
     const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbRowsChunkElems;
+    const uint32_t cs = chunk * kPbRowsChunkElems;
     const uint32_t n = job.count - cs < kPbRowsChunkElems ? job.count - cs : kPbRowsChunkElems;
     const uint32_t ce = cs + n;
     const uint32_t* ends = job.row_ends;
@@ -822,7 +827,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
     uint32_t lo = 0, hi = job.rows - 1;
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo) / 2;
-        if (ends[mid] > cs) {
+        if (rows_end_at<kIota>(ends, mid) > cs) {
             hi = mid;
         } else {
             lo = mid + 1;
@@ -832,7 +837,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
     hi = job.rows - 1;
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo) / 2;
-        if (ends[mid] >= ce) {
+        if (rows_end_at<kIota>(ends, mid) >= ce) {
             hi = mid;
         } else {
             lo = mid + 1;
@@ -879,10 +884,9 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
         }
     }
     if (bytes != want) {
-        if (t == 0) res[j].err = 4;
+        if (t == 0) *err = 4;
         return;
     }
-    const uint32_t* delta = row_delta + job.first_row;
 
     if (r_hi - r_lo < kRowsFewRows) {
         // the image sits at the 16-byte phase of the chunk's first byte in dst
@@ -913,7 +917,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
         if (t == 0 && varints) aux[n] = bytes;
         __syncthreads();
         for (uint32_t row = r_lo; row <= r_hi; ++row) {
-            uint32_t s = row ? ends[row - 1] : 0, e = ends[row];
+            uint32_t s = row ? rows_end_at<kIota>(ends, row - 1) : 0, e = rows_end_at<kIota>(ends, row);
             s = s > cs ? s : cs;
             e = e < ce ? e : ce;
             if (e <= s) continue;
@@ -921,7 +925,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
             const uint32_t b = varints ? aux[e - cs] : (e - cs) * w;
             const uint32_t off = delta[row] + before_cs + a;
             if (b < a || (uint64_t)off + (b - a) > total) {
-                if (t == 0) res[j].err = 4;
+                if (t == 0) *err = 4;
                 continue;
             }
             uint8_t* d = job.dst + off;
@@ -939,7 +943,7 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
     for (uint32_t i = t; i < n; i += kRunThreads) aux[i] = 0;
     __syncthreads();
     for (uint64_t row = (uint64_t)r_lo + t; row <= r_hi; row += kRunThreads) {
-        const uint32_t s = row ? ends[row - 1] : 0, e = ends[row];
+        const uint32_t s = row ? rows_end_at<kIota>(ends, row - 1) : 0, e = rows_end_at<kIota>(ends, row);
         if (e <= s) continue;
         const uint32_t i = s > cs ? s - cs : 0;
         if (i < n) aux[i] = (uint32_t)(row - r_lo) + 1;
@@ -997,7 +1001,167 @@ __global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRows
             }
         }
     }
-    if (changed) res[j].err = 4;
+    if (changed) *err = 4;
+}
+
+__global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRowsJob* __restrict__ jobs, int njobs,
+                                                                    const uint32_t* __restrict__ groups,
+                                                                    const uint32_t* __restrict__ block_off,
+                                                                    const uint32_t* __restrict__ row_delta,
+                                                                    const uint32_t* __restrict__ first_bad,
+                                                                    PbRowsResult* __restrict__ res) {
+    const int j = wg::job_of<&PbRowsJob::first_chunk>(jobs, njobs, blockIdx.x);
+    const PbRowsJob job = jobs[j];
+    if (first_bad[j] != kNoRow) return;
+    const uint32_t total = rows_job_total(job, j, block_off);
+    if (total > job.cap) return;
+    rows_place_chunk<false>(job, blockIdx.x - job.first_chunk, total, groups, row_delta + job.first_row, &res[j].err);
+}
+
+// ---------------------------------------------------------- record builder
+// Several columns -> the occurrences of one repeated sub-message with several
+// fields (kernels.h: init, size, prefix, measure, prefix, heads, place; the
+// wire rules are base/pb_records.h). A column is a PbRowsJob, so the size
+// pass is the row builder's kernel over the column table and the place pass
+// is its body; what is new is that a row's size sums over its columns and
+// that each column has its own delta.
+constexpr uint64_t kNoRecord = ~0ull;  // the offender key: row << 4 | column
+
+__global__ void __launch_bounds__(64) pb_records_init_kernel(const PbRecordsJob* __restrict__ jobs, int njobs,
+                                                             const PbRowsJob* __restrict__ cols, int ncols,
+                                                             PbRecordsJob* __restrict__ jobs_dev,
+                                                             PbRowsJob* __restrict__ cols_dev,
+                                                             uint32_t* __restrict__ groups,
+                                                             unsigned long long* __restrict__ bad) {
+    const int i = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (i < njobs) {
+        jobs_dev[i] = jobs[i];
+        bad[i] = kNoRecord;
+    }
+    if (i >= ncols) return;
+    const PbRowsJob col = cols[i];
+    cols_dev[i] = col;
+    if (pb_rows::IsVarintKind(col.kind)) {
+        // as pb_rows_init_kernel: the group behind the last element and the
+        // one whose prefix is the total
+        const uint32_t g = col.first_group + col.count / kPbRowsGroupElems;
+        groups[g] = 0;
+        groups[g + 1] = 0;
+    }
+}
+
+__global__ void __launch_bounds__(kPbRowsBlockRows) pb_records_measure_kernel(
+    const PbRecordsJob* __restrict__ jobs, int njobs, const PbRowsJob* __restrict__ cols,
+    const uint32_t* __restrict__ groups, uint32_t* __restrict__ row_size, uint32_t* __restrict__ col_pay,
+    uint32_t* __restrict__ col_delta, uint32_t* __restrict__ block_off, unsigned long long* __restrict__ bad) {
+    __shared__ uint32_t wave_tot[kPbRowsBlockRows / 64];
+    const int j = wg::job_of<&PbRecordsJob::first_rblock>(jobs, njobs, blockIdx.x);
+    const PbRecordsJob job = jobs[j];
+    const uint32_t block = blockIdx.x - job.first_rblock;
+    const uint64_t r64 = (uint64_t)block * kPbRowsBlockRows + threadIdx.x;
+    const uint32_t r = (uint32_t)r64;
+    uint32_t size = 0;
+    if (r64 < job.rows) {
+        uint32_t fields = 0;
+        for (uint32_t c = 0; c < job.ncols; ++c) {
+            const PbRowsJob col = cols[job.first_col + c];
+            const bool scalar = col.row_ends == nullptr;
+            uint32_t s = r, e = r + 1;  // a scalar column: host-checked count == rows
+            if (!scalar) {
+                s = r ? col.row_ends[r - 1] : 0;
+                e = col.row_ends[r];
+                if (e < s || (r + 1 == job.rows && e != col.count)) atomicMin(&bad[j], ((unsigned long long)r << 4) | c);
+                // a malformed table gets nothing written; until then it must
+                // not make a lane read past the source
+                s = s < col.count ? s : col.count;
+                e = e < col.count ? e : col.count;
+                e = e < s ? s : e;
+            }
+            const uint32_t before = rows_bytes_before(col, groups, s);
+            const uint32_t p = rows_bytes_before(col, groups, e) - before;
+            const uint32_t at = col.first_row + r;
+            col_pay[at] = p;
+            col_delta[at] = before;
+            fields += p + pb_records::FieldHeaderBytes(col.inner, col.kind, scalar, p);
+        }
+        size = fields + pb_records::RowHeaderBytes(job.number, fields);
+        row_size[job.first_row + r] = size;
+    }
+    uint32_t sum;
+    wg::block_excl_scan<(int)kPbRowsBlockRows>(size, wave_tot, &sum);
+    if (threadIdx.x == 0) {
+        // the job's blocks, then one entry that becomes its total under the scan
+        const uint32_t at = blockIdx.x + (uint32_t)j;
+        block_off[at] = sum;
+        if ((uint64_t)(block + 1) * kPbRowsBlockRows >= job.rows) block_off[at + 1] = 0;
+    }
+}
+
+__device__ __forceinline__ uint32_t records_job_total(const PbRecordsJob& job, int j, const uint32_t* block_off) {
+    const uint32_t first = job.first_rblock + (uint32_t)j;
+    const uint32_t nblocks = (uint32_t)(((uint64_t)job.rows + kPbRowsBlockRows - 1) / kPbRowsBlockRows);
+    return block_off[first + nblocks] - block_off[first];
+}
+
+__global__ void __launch_bounds__(kPbRowsBlockRows) pb_records_heads_kernel(
+    const PbRecordsJob* __restrict__ jobs, int njobs, const PbRowsJob* __restrict__ cols,
+    const uint32_t* __restrict__ row_size, const uint32_t* __restrict__ col_pay, uint32_t* __restrict__ col_delta,
+    const uint32_t* __restrict__ block_off, const unsigned long long* __restrict__ bad,
+    PbRecordsResult* __restrict__ res) {
+    __shared__ uint32_t wave_tot[kPbRowsBlockRows / 64];
+    const int j = wg::job_of<&PbRecordsJob::first_rblock>(jobs, njobs, blockIdx.x);
+    const PbRecordsJob job = jobs[j];
+    const uint64_t r64 = (uint64_t)(blockIdx.x - job.first_rblock) * kPbRowsBlockRows + threadIdx.x;
+    const bool live = r64 < job.rows;
+    const uint32_t r = (uint32_t)r64;
+    const unsigned long long key = bad[j];
+    const uint32_t total = records_job_total(job, j, block_off);
+    const bool ok = key == kNoRecord && total <= job.cap;
+    if (r64 == 0) {
+        res[j] = PbRecordsResult{total, key != kNoRecord ? (uint32_t)(key >> 4) : kNoRow,
+                                 key != kNoRecord ? (uint32_t)(key & 15) : kNoRow,
+                                 key != kNoRecord ? 1 : (total > job.cap ? 3 : 0)};
+    }
+    if (!ok) return;  // the whole workgroup
+    // the row's offset: the blocks before this one, then the rows before it here
+    uint32_t block_size;
+    uint32_t off = wg::block_excl_scan<(int)kPbRowsBlockRows>(live ? row_size[job.first_row + r] : 0u, wave_tot,
+                                                               &block_size);
+    if (!live) return;
+    off += block_off[blockIdx.x + (uint32_t)j] - block_off[job.first_rblock + (uint32_t)j];
+    // a field's header follows from its payload size alone (an omitted packed
+    // field is one of no byte), so nothing here reads a row end again
+    uint32_t fields = 0;
+    for (uint32_t c = 0; c < job.ncols; ++c) {
+        const PbRowsJob col = cols[job.first_col + c];
+        const uint32_t p = col_pay[col.first_row + r];
+        fields += p + pb_records::FieldHeaderBytes(col.inner, col.kind, col.row_ends == nullptr, p);
+    }
+    const uint32_t hn = pb_records::RowHeaderBytes(job.number, fields);
+    if ((uint64_t)off + hn + fields > total) return;  // nothing leaves the message
+    pb_records::PutRowHeader(job.dst + off, job.number, fields);
+    uint32_t at = off + hn;
+    for (uint32_t c = 0; c < job.ncols; ++c) {
+        const PbRowsJob col = cols[job.first_col + c];
+        const uint32_t p = col_pay[col.first_row + r];
+        at += pb_records::PutFieldHeader(job.dst + at, col.inner, col.kind, col.row_ends == nullptr, p);
+        col_delta[col.first_row + r] = at - col_delta[col.first_row + r];
+        at += p;
+    }
+}
+
+__global__ void __launch_bounds__(kRunThreads) pb_records_place_kernel(
+    const PbRecordsJob* __restrict__ jobs, const PbRowsJob* __restrict__ cols, int ncols,
+    const uint32_t* __restrict__ groups, const uint32_t* __restrict__ block_off,
+    const uint32_t* __restrict__ col_delta, const unsigned long long* __restrict__ bad,
+    PbRecordsResult* __restrict__ res) {
+    const PbRowsJob col = cols[wg::job_of<&PbRowsJob::first_chunk>(cols, ncols, blockIdx.x)];
+    const int j = (int)col.first_rblock;  // a column's: its record job
+    const PbRecordsJob job = jobs[j];
+    if (bad[j] != kNoRecord) return;
+    const uint32_t total = records_job_total(job, j, block_off);
+    if (total > job.cap) return;
+    rows_place_chunk<true>(col, blockIdx.x - col.first_chunk, total, groups, col_delta + col.first_row, &res[j].err);
 }
 
 // ------------------------------------------------------------ row splitter
@@ -1638,6 +1802,38 @@ int LaunchPbRowsBuild(const PbRowsTables& t, hipStream_t s) {
     if (t.nchunks == 0) return 0;
     hipLaunchKernelGGL(pb_rows_place_kernel, dim3(t.nchunks), dim3(kRunThreads), 0, s, t.jobs_dev, t.njobs, t.groups,
                        t.block_off, t.row_delta, t.first_bad, t.res);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int LaunchPbRecordsBuild(const PbRecordsTables& t, hipStream_t s) {
+    if (t.njobs <= 0) return 0;
+    if (!t.jobs || !t.cols || t.ncols <= 0 || !t.jobs_dev || !t.cols_dev || !t.row_size || !t.col_pay ||
+        !t.col_delta || !t.block_off || !t.bad || !t.res || t.nrblocks == 0 || (t.ngroups > 0 && !t.groups) ||
+        t.ngroups > 0x7FFFFFFFu) {
+        return -1;
+    }
+    const int most = t.njobs > t.ncols ? t.njobs : t.ncols;
+    hipLaunchKernelGGL(pb_records_init_kernel, dim3((unsigned)(most + 63) / 64), dim3(64), 0, s, t.jobs, t.njobs, t.cols,
+                       t.ncols, t.jobs_dev, t.cols_dev, t.groups, t.bad);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (t.ngroups > 0) {
+        if (t.nchunks > 0) {
+            hipLaunchKernelGGL(pb_rows_size_kernel, dim3(t.nchunks), dim3(kRunThreads), 0, s, t.cols_dev, t.ncols,
+                               t.groups);
+            if (hipGetLastError() != hipSuccess) return -1;
+        }
+        if (LaunchPbRunPrefix(t.groups, (int)t.ngroups, s) != 0) return -1;
+    }
+    hipLaunchKernelGGL(pb_records_measure_kernel, dim3(t.nrblocks), dim3(kPbRowsBlockRows), 0, s, t.jobs_dev, t.njobs,
+                       t.cols_dev, t.groups, t.row_size, t.col_pay, t.col_delta, t.block_off, t.bad);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (LaunchPbRunPrefix(t.block_off, (int)(t.nrblocks + (uint32_t)t.njobs), s) != 0) return -1;
+    hipLaunchKernelGGL(pb_records_heads_kernel, dim3(t.nrblocks), dim3(kPbRowsBlockRows), 0, s, t.jobs_dev, t.njobs,
+                       t.cols_dev, t.row_size, t.col_pay, t.col_delta, t.block_off, t.bad, t.res);
+    if (hipGetLastError() != hipSuccess) return -1;
+    if (t.nchunks == 0) return 0;
+    hipLaunchKernelGGL(pb_records_place_kernel, dim3(t.nchunks), dim3(kRunThreads), 0, s, t.jobs_dev, t.cols_dev,
+                       t.ncols, t.groups, t.block_off, t.col_delta, t.bad, t.res);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -81,6 +81,10 @@ struct DevBuf {
 typedef std::tuple<uint32_t, uint32_t, uintptr_t, uint64_t> MessageFieldRow;
 // (number, inner, kind, src, count, row_ends, rows, dst, cap) rows of device_build_rows
 typedef std::tuple<uint32_t, uint32_t, uint32_t, uintptr_t, uint64_t, uintptr_t, uint64_t, uintptr_t, uint64_t> RowsJobRow;
+// (inner, kind, src, count, row_ends) columns of device_build_records; row_ends 0: a scalar column
+typedef std::tuple<uint32_t, uint32_t, uintptr_t, uint64_t, uintptr_t> RecordColumnRow;
+// (number, columns, rows, dst, cap) rows of device_build_records
+typedef std::tuple<uint32_t, std::vector<RecordColumnRow>, uint64_t, uintptr_t, uint64_t> RecordsJobRow;
 std::vector<gpu::DeviceMessageField> message_fields(const std::vector<MessageFieldRow>& rows) {
     std::vector<gpu::DeviceMessageField> fs(rows.size());
     for (size_t i = 0; i < rows.size(); ++i) {
@@ -90,6 +94,17 @@ std::vector<gpu::DeviceMessageField> message_fields(const std::vector<MessageFie
         fs[i].count = std::get<3>(rows[i]);
     }
     return fs;
+}
+std::vector<gpu::DeviceRecordColumn> record_columns(const std::vector<RecordColumnRow>& rows) {
+    std::vector<gpu::DeviceRecordColumn> cs(rows.size());
+    for (size_t i = 0; i < rows.size(); ++i) {
+        cs[i].inner = std::get<0>(rows[i]);
+        cs[i].kind = std::get<1>(rows[i]);
+        cs[i].src = (const void*)std::get<2>(rows[i]);
+        cs[i].count = std::get<3>(rows[i]);
+        cs[i].row_ends = (const uint32_t*)std::get<4>(rows[i]);
+    }
+    return cs;
 }
 
 }  // namespace
@@ -323,6 +338,41 @@ void bind_gpu_ops(py::module_& g) {
         return out;
     }, py::arg("jobs"), py::arg("device") = 0);
     g.def("device_split_max_bytes", []() { return gpu::kDeviceSplitMaxBytes; });
+    // Records: jobs = [(number, [(inner, kind, src, count, row_ends)], rows,
+    // dst, cap)], src / row_ends / dst device pointers, row_ends 0 for a
+    // scalar column -> [(len, err, first_bad, bad_column)]
+    // (gpu::DeviceBuildRecords; all jobs share one launch sequence).
+    g.def("device_build_records", [](const std::vector<RecordsJobRow>& jobs, int device) {
+        std::vector<gpu::DeviceRecordsJob> js(jobs.size());
+        std::vector<std::vector<gpu::DeviceRecordColumn>> cols(jobs.size());
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            cols[i] = record_columns(std::get<1>(jobs[i]));
+            js[i].number = std::get<0>(jobs[i]);
+            js[i].columns = cols[i].data();
+            js[i].ncols = (uint32_t)cols[i].size();
+            js[i].rows = std::get<2>(jobs[i]);
+            js[i].dst = (void*)std::get<3>(jobs[i]);
+            js[i].cap = std::get<4>(jobs[i]);
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceBuildRecords(js.data(), (int)js.size(), device);
+        }
+        check(rc, "device_build_records");
+        py::list out;
+        for (const gpu::DeviceRecordsJob& j : js) out.append(py::make_tuple(j.len, j.err, j.first_bad, j.bad_column));
+        return out;
+    }, py::arg("jobs"), py::arg("device") = 0);
+    g.def("device_records_worst_case", [](uint32_t number, const std::vector<RecordColumnRow>& columns, uint64_t rows) {
+        const std::vector<gpu::DeviceRecordColumn> cols = record_columns(columns);
+        gpu::DeviceRecordsJob j;
+        j.number = number;
+        j.columns = cols.data();
+        j.ncols = (uint32_t)cols.size();
+        j.rows = rows;
+        return gpu::DeviceRecordsWorstCaseBytes(j);
+    }, py::arg("number"), py::arg("columns"), py::arg("rows"));
     g.def("device_rows_worst_case", [](uint32_t number, uint32_t inner, uint32_t kind, uint64_t count, uint64_t rows) {
         gpu::DeviceRowsJob j;
         j.number = number;

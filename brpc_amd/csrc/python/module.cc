@@ -29,6 +29,7 @@
 #include "json/json2pb.h"
 #include "pb/descriptor.h"
 #include "pb/parser.h"
+#include "pb/records.h"
 #include "pb/rows.h"
 #include "gpu/xgmi.h"
 #include "policy/device_payload.h"
@@ -107,6 +108,7 @@ class PyChannel {
 public:
     typedef std::vector<std::tuple<uint32_t, uint32_t, uintptr_t, uint64_t>> MessageFields;
     typedef std::tuple<uint32_t, uint32_t, uint32_t, uintptr_t, uint64_t, uintptr_t, uint64_t> RowsSource;
+    typedef std::vector<std::tuple<uint32_t, uint32_t, uintptr_t, uint64_t, uintptr_t>> RecordColumns;
     PyChannel(const std::string& server, const std::string& lb, const std::string& protocol,
               const std::string& connection_type, int timeout_ms, int max_retry) {
         GlobalInitializeOrDie();
@@ -201,6 +203,56 @@ public:
                                      std::to_string(job.first_bad) + ")");
         }
         return py::make_tuple(py::bytes(values), row_ends, job.others);
+    }
+    // A Batch whose repeated element has several fields: the block
+    // gpu::BuildDeviceMessage makes of `fields`, then the block
+    // gpu::BuildDeviceRecords makes of `columns` [(inner, kind, src, count,
+    // row_ends)] (row_ends 0: a scalar column) over `rows` records of field
+    // `number`, appended to one Buf. Returns the echoed attachment's bytes.
+    py::bytes echo_device_records(const MessageFields& fields, uint32_t number, const RecordColumns& columns,
+                                  uint64_t rows, int device) {
+        example::EchoRequest req;
+        example::EchoResponse res;
+        Controller cntl;
+        req.set_message("records");
+        std::vector<gpu::DeviceMessageField> fs(fields.size());
+        for (size_t i = 0; i < fields.size(); ++i) {
+            fs[i].number = std::get<0>(fields[i]);
+            fs[i].kind = std::get<1>(fields[i]);
+            fs[i].src = (const void*)std::get<2>(fields[i]);
+            fs[i].count = std::get<3>(fields[i]);
+        }
+        std::vector<gpu::DeviceRecordColumn> cols(columns.size());
+        for (size_t i = 0; i < columns.size(); ++i) {
+            cols[i].inner = std::get<0>(columns[i]);
+            cols[i].kind = std::get<1>(columns[i]);
+            cols[i].src = (const void*)std::get<2>(columns[i]);
+            cols[i].count = std::get<3>(columns[i]);
+            cols[i].row_ends = (const uint32_t*)std::get<4>(columns[i]);
+        }
+        gpu::DeviceRecordsJob job;
+        job.number = number;
+        job.columns = cols.data();
+        job.ncols = (uint32_t)cols.size();
+        job.rows = rows;
+        std::string got;
+        int rc = 0, copy_rc = 0;
+        {
+            py::gil_scoped_release nogil;
+            if (!fs.empty()) rc = gpu::BuildDeviceMessage(fs.data(), (int)fs.size(), &cntl.request_attachment(), device);
+            if (rc == 0) rc = gpu::BuildDeviceRecords(job, &cntl.request_attachment(), device);
+            if (rc == 0) {
+                example::EchoService_Stub stub(&_ch);
+                stub.Echo(&cntl, &req, &res, nullptr);
+                if (!cntl.Failed()) copy_rc = gpu::CopyBufToHost(cntl.response_attachment(), &got);
+            }
+        }
+        if (rc != 0) throw std::runtime_error("building the attachment on the device failed (code " + std::to_string(rc) + ")");
+        if (cntl.Failed()) {
+            throw std::runtime_error("[E" + std::to_string(cntl.ErrorCode()) + "] " + cntl.ErrorText());
+        }
+        if (copy_rc != 0) throw std::runtime_error("copying the echoed attachment to the host failed");
+        return py::bytes(got);
     }
 
 private:
@@ -728,6 +780,51 @@ PYBIND11_MODULE(_native, m) {
                                           row_ends.size(), &out, &first_bad);
         return py::make_tuple(err, first_bad, py::bytes(out));
     }, py::arg("number"), py::arg("inner"), py::arg("kind"), py::arg("values"), py::arg("row_ends"));
+    // The host twin of gpu::DeviceBuildRecords (pb::SerializeRecords):
+    // columns = [(inner, kind, values, row_ends)], values the memory image of
+    // the column's elements in the kind's vector layout, row_ends a list or
+    // the image of a uint32 array with `rows` entries, or None for a scalar
+    // column -> (err, first_bad, bad_column, wire bytes).
+    m.def("pb_serialize_records", [](uint32_t number, const std::vector<std::tuple<uint32_t, uint32_t, py::bytes, py::object>>& columns,
+                                     uint64_t rows) {
+        const size_t n = columns.size();
+        std::vector<std::vector<uint64_t>> values(n);
+        std::vector<std::vector<uint32_t>> ends(n);
+        std::vector<pb_records::Column> cols(n);
+        for (size_t c = 0; c < n; ++c) {
+            cols[c].inner = std::get<0>(columns[c]);
+            cols[c].kind = std::get<1>(columns[c]);
+            const std::string data = std::get<2>(columns[c]);
+            const size_t eb = cols[c].kind <= pb_rows::kKindFixed64 ? pb_rows::SourceBytes(cols[c].kind) : 1;
+            if (data.size() % eb) throw std::invalid_argument("values must hold whole elements");
+            values[c].resize(data.size() / 8 + 1);  // aligned for 8-byte elements, never null
+            if (!data.empty()) memcpy(values[c].data(), data.data(), data.size());
+            cols[c].src = values[c].data();
+            cols[c].count = data.size() / eb;
+            const py::object& re = std::get<3>(columns[c]);
+            if (re.is_none()) continue;
+            if (py::isinstance<py::bytes>(re)) {
+                const std::string image = re.cast<std::string>();
+                if (image.size() % 4) throw std::invalid_argument("row_ends must hold whole uint32 entries");
+                ends[c].resize(image.size() / 4);
+                if (!image.empty()) memcpy(ends[c].data(), image.data(), image.size());
+            } else {
+                ends[c] = re.cast<std::vector<uint32_t>>();
+            }
+            if (ends[c].size() != rows) throw std::invalid_argument("every row_ends must hold `rows` entries");
+            ends[c].push_back(0);  // data() of an empty table is still a table
+            cols[c].row_ends = ends[c].data();
+        }
+        pb_records::Job job;
+        job.number = number;
+        job.columns = cols.data();
+        job.ncols = (uint32_t)n;
+        job.rows = rows;
+        std::string out;
+        uint32_t first_bad = 0xFFFFFFFFu, bad_column = 0xFFFFFFFFu;
+        const int err = pb::SerializeRecords(job, &out, &first_bad, &bad_column);
+        return py::make_tuple(err, first_bad, bad_column, py::bytes(out));
+    }, py::arg("number"), py::arg("columns"), py::arg("rows"));
     // The host twin of gpu::DeviceSplitRows (pb::SplitRows): the message's
     // rows of field `number` -> (err, count, rows, others, first_bad, values
     // bytes, row_ends list). max_elems / max_rows are the outputs' capacities
@@ -980,6 +1077,8 @@ PYBIND11_MODULE(_native, m) {
              py::arg("sleep_us") = 0)
         .def("echo_device_rows", &PyChannel::echo_device_rows, py::arg("fields"), py::arg("rows"),
              py::arg("device") = 0)
+        .def("echo_device_records", &PyChannel::echo_device_records, py::arg("fields"), py::arg("number"),
+             py::arg("columns"), py::arg("rows"), py::arg("device") = 0)
         .def("echo_device_rows_split", &PyChannel::echo_device_rows_split, py::arg("fields"), py::arg("rows"),
              py::arg("device") = 0);
 
@@ -1186,6 +1285,9 @@ PYBIND11_MODULE(_native, m) {
         d["built_row_bytes"] = s.built_row_bytes;
         d["split_row_jobs"] = s.split_row_jobs;
         d["split_rows"] = s.split_rows;
+        d["built_record_jobs"] = s.built_record_jobs;
+        d["built_records"] = s.built_records;
+        d["built_record_bytes"] = s.built_record_bytes;
         d["built_fields"] = s.built_fields;
         d["built_bytes"] = s.built_bytes;
         d["build_errors"] = s.build_errors;

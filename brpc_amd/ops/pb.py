@@ -178,6 +178,88 @@ def pb_build_rows(number, values, row_ends, kind_name, inner=None):
     return out[:n]
 
 
+RECORDS_ERRORS = dict(ROWS_ERRORS)
+RECORDS_ERRORS[2] = "refused (field number, inner, kind, columns, a scalar column's length, alignment, rows or size)"
+
+
+def pb_build_records(number, columns, scalar=False):
+    """Serialize a batch of records in device memory as the occurrences of one
+    repeated sub-message with several fields (``gpu::DeviceBuildRecords``):
+    ``repeated Example examples = number``, every field of ``Example`` one
+    column.
+
+    columns: [(inner, values, row_ends_or_None, kind_name)], written into
+    every record in this order (at most 8). A column takes the tensor and
+    dtype rules of ``pb_build_rows``. With ``row_ends`` it is ragged: a packed
+    field ``inner`` (omitted in a record without elements) or, for kind bytes,
+    a bytes / string field (always present); an int64 ``row_ends`` is narrowed
+    on the device. With ``row_ends=None`` a 1-D tensor is a scalar column: one
+    element per record, written with explicit presence (a zero stays); a 2-D
+    tensor means equal rows of a ragged column, unless ``scalar=True`` flattens
+    it into a scalar column.
+
+    Returns a uint8 device tensor trimmed to the serialized length, which
+    composes with a ``pb_build_message`` result by concatenation.
+
+    The builder runs on its own stream: the caller's current stream is
+    synchronized before the call, as in ``pb_build_message``."""
+    if not columns:
+        raise ValueError("no columns")
+    dev = columns[0][1].device
+    rows, cols, keep = None, [], []
+    for c, (inner, values, row_ends, kind_name) in enumerate(columns):
+        if kind_name not in _ROW_KINDS:
+            raise ValueError("column %d: unknown kind %r (one of %s)" % (c, kind_name, ", ".join(_ROW_KINDS)))
+        kind, dtypes = _ROW_KINDS[kind_name]
+        require_gpu_tensor(values, "column %d" % c)
+        if values.device != dev:
+            raise ValueError("all columns must live on one device (%s vs %s)" % (values.device, dev))
+        if dtypes is not None and values.dtype not in dtypes:
+            raise TypeError("column %d: kind %s takes a tensor of %s, not %s" % (c, kind_name, dtypes[0], values.dtype))
+        if row_ends is None and values.dim() == 2 and not scalar:
+            per = values.shape[1] * (values.element_size() if kind == 7 else 1)
+            row_ends = torch.arange(per, per * values.shape[0] + 1, max(per, 1), dtype=torch.int32, device=dev) \
+                if per else torch.zeros(values.shape[0], dtype=torch.int32, device=dev)
+        values = values.contiguous()
+        count = values.numel() * values.element_size() if kind == 7 else values.numel()
+        ends_ptr, nrows = 0, count
+        if row_ends is not None:
+            require_gpu_tensor(row_ends, "column %d row_ends" % c)
+            if row_ends.device != dev:
+                raise ValueError("column %d: row_ends must live on the same device as values" % c)
+            if row_ends.dtype == torch.int64:
+                row_ends = row_ends.to(torch.int32)
+            if row_ends.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or row_ends.dim() != 1:
+                raise TypeError("column %d: row_ends must be a 1-D int32, uint32 or int64 tensor, not %s"
+                                % (c, row_ends.dtype))
+            row_ends = row_ends.contiguous()
+            if row_ends.numel() == 0:
+                raise ValueError("column %d: row_ends is empty" % c)
+            ends_ptr, nrows = row_ends.data_ptr(), row_ends.numel()
+            keep.append(row_ends)
+        elif kind == 7:
+            raise ValueError("column %d: a bytes column needs row_ends" % c)
+        if rows is None:
+            rows = nrows
+        elif nrows != rows:
+            raise ValueError("column %d holds %d records, the columns before it %d" % (c, nrows, rows))
+        keep.append(values)
+        cols.append((int(inner), kind, values.data_ptr() if count else 0, count, ends_ptr))
+    cap = native.gpu.device_records_worst_case(int(number), cols, rows)
+    if cap == 0:
+        raise ValueError("pb_build_records: " + RECORDS_ERRORS[2])
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (n, err, first_bad, bad_column), = native.gpu.device_build_records(
+            [(int(number), cols, rows, out.data_ptr(), cap)], dev.index or 0)
+    if err == 1:
+        raise ValueError("pb_build_records: %s (row %d, column %d)" % (RECORDS_ERRORS[1], first_bad, bad_column))
+    if err:
+        raise ValueError("pb_build_records: " + RECORDS_ERRORS.get(err, "code %d" % err))
+    return out[:n]
+
+
 SPLIT_ERRORS = {
     1: "malformed wire",
     2: "refused (field number, inner, kind or size)",
