@@ -129,5 +129,94 @@ MRPC_ROWS_FN uint64_t WorstCaseBytes(const Job& job) {
     return total > 0xFFFFFFFFull ? 0 : total;
 }
 
+// ---- the way back: a message that holds such records, split into the
+// columns again (pb::SplitRecords in pb/records.h, gpu::DeviceSplitRecords).
+// The codes are pb_rows' (kSplitMalformed 1, kSplitRefused 2, kSplitShort 5,
+// kSplitUnsupported 6).
+//
+// A split column is {inner, kind, scalar}. Column numbers must be distinct:
+// the builder allows repeats, the splitter cannot attribute them, and as it
+// cannot tell a packed form from an unpacked one either, one number must not
+// appear with two wire forms. SplitColumnsOk refuses duplicates (code 2).
+struct SplitColumn {
+    uint32_t inner = 0;
+    uint32_t kind = 0;
+    uint32_t scalar = 0;  // 1: one element per record, no row ends
+};
+
+MRPC_ROWS_FN bool SplitColumnsOk(uint32_t number, const SplitColumn* cols, uint32_t ncols) {
+    if (number < 1 || number > pb_rows::kMaxFieldNumber || !cols || ncols < 1 || ncols > kRecordMaxColumns) return false;
+    for (uint32_t c = 0; c < ncols; ++c) {
+        if (!ColumnOk(cols[c].inner, cols[c].kind, cols[c].scalar != 0)) return false;
+        for (uint32_t d = 0; d < c; ++d) {
+            if (cols[d].inner == cols[c].inner) return false;
+        }
+    }
+    return true;
+}
+
+// The verdict on one record whose value is b[v, v + s): 0, 1 or 6. For every
+// field that column c takes, take(c, offset, bytes) is called with the place
+// of its payload (a ragged column) or of its value (a scalar: the varint, or
+// the 4 or 8 bytes); a column that is never taken is absent from the record.
+//   - a field pb_rows::SpecField calls invalid makes the record 1;
+//   - a field is taken by column c when its number is the column's inner, its
+//     wire type is WireType(kind, scalar) and c was not taken earlier in this
+//     record; fields may come in any order;
+//   - a taken ragged payload of a fixed kind (or of bytes) must be whole
+//     elements, one of a varint kind must end in a byte without a
+//     continuation bit; a breach makes the record 1;
+//   - every other well-formed field (an unknown number, a column's number
+//     with another wire type, which is an unpacked repeated field, a column
+//     taken twice) makes the record 6, unless something in it is 1.
+// take() is called for the taken fields of a record that is 6 too (and for
+// those in front of the offender of one that is 1): whether a taken varint
+// payload holds only varints the packed-run decoder takes is
+// pb_rows::VarintsOk on the host and the check pass on the device, both of
+// which must see the payloads of a record that has both faults (it is 1).
+// An absent ragged column is a row of no element, an absent bytes field and
+// an empty one are the same row, an absent scalar reads as 0 (the proto3 rule
+// and the proto2 default) and is counted; an empty record is valid.
+// The walk reads only b[v, v + s) and takes at most s / 2 steps: both of
+// SpecField's invariants hold with the record's end in the place of n.
+template <typename Take>
+MRPC_ROWS_FN int RecordShape(const uint8_t* b, uint64_t v, uint64_t s, const SplitColumn* cols, uint32_t ncols,
+                             Take&& take) {
+    const uint64_t end = v + s;
+    uint32_t taken = 0;
+    int code = 0;
+    for (uint64_t p = v; p < end;) {
+        const pb_rows::Field f = pb_rows::SpecField(b, p, end);
+        if (!f.valid) return pb_rows::kSplitMalformed;
+        const uint32_t number = f.tag >> 3, wire = f.tag & 7;
+        uint32_t c = 0;
+        while (c < ncols && cols[c].inner != number) ++c;
+        if (c == ncols || wire != WireType(cols[c].kind, cols[c].scalar != 0) || (taken >> c & 1)) {
+            code = pb_rows::kSplitUnsupported;
+        } else if (cols[c].scalar) {
+            // the value ends the field; a varint's tag may be over-long, so its end is parsed again
+            uint64_t at = f.next - (wire == 1 ? 8 : 4);
+            if (wire == 0) {
+                uint32_t tn = 0;
+                uint64_t tag = 0;
+                pb_rows::GetVarint(b + p, end - p, &tn, &tag);
+                at = p + tn;
+            }
+            taken |= 1u << c;
+            take(c, at, f.next - at);
+        } else {
+            if (pb_rows::WireIsVarint(cols[c].kind)) {
+                if (f.vlen > 0 && (b[f.vpos + f.vlen - 1] & 0x80)) return pb_rows::kSplitMalformed;
+            } else if (f.vlen % pb_rows::SourceBytes(cols[c].kind)) {
+                return pb_rows::kSplitMalformed;
+            }
+            taken |= 1u << c;
+            take(c, f.vpos, f.vlen);
+        }
+        p = f.next;
+    }
+    return code;
+}
+
 }  // namespace pb_records
 }  // namespace mrpc

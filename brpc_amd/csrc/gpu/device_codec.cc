@@ -36,6 +36,7 @@ std::atomic<int64_t> g_encodes{0}, g_enc_bytes{0}, g_enc_out{0}, g_decodes{0}, g
 std::atomic<int64_t> g_built{0}, g_built_fields{0}, g_built_bytes{0}, g_build_err{0};
 std::atomic<int64_t> g_built_row_jobs{0}, g_built_rows{0}, g_built_row_bytes{0};
 std::atomic<int64_t> g_split_row_jobs{0}, g_split_rows{0};
+std::atomic<int64_t> g_split_record_jobs{0}, g_split_records{0};
 std::atomic<int64_t> g_built_record_jobs{0}, g_built_records{0}, g_built_record_bytes{0};
 
 uint32_t varint_len(uint64_t v) {
@@ -883,10 +884,197 @@ int DeviceSplitRows(DeviceRowsSplitJob* jobs, int n, int device) {
     return 0;
 }
 
+namespace {
+
+constexpr uint64_t kArenaLargestBlock = 256ull << 20;  // gpu/hbm_pool.cc: class 28
+
+// What the host can check of a record split job without reading device memory.
+bool record_split_job_ok(const DeviceRecordsSplitJob& j) {
+    if (!j.columns || j.ncols < 1 || j.ncols > kDeviceRecordMaxColumns) return false;
+    pb_records::SplitColumn cols[pb_records::kRecordMaxColumns];
+    for (uint32_t c = 0; c < j.ncols; ++c) {
+        cols[c].inner = j.columns[c].inner;
+        cols[c].kind = j.columns[c].kind;
+        cols[c].scalar = j.columns[c].scalar;
+    }
+    if (!pb_records::SplitColumnsOk(j.number, cols, j.ncols) || j.n > kDeviceSplitMaxBytes || (j.n > 0 && !j.msg)) {
+        return false;
+    }
+    for (uint32_t c = 0; c < j.ncols; ++c) {
+        const DeviceRecordSplitColumn& col = j.columns[c];
+        if ((col.cap > 0 && !col.values) || ((uintptr_t)col.values & (pb_rows::SourceBytes(col.kind) - 1)) != 0) return false;
+        if (!col.scalar && ((j.row_cap > 0 && !col.row_ends) || ((uintptr_t)col.row_ends & 3) != 0)) return false;
+    }
+    // the record table is one arena block
+    return std::min(j.row_cap, j.n / 2) * j.ncols * sizeof(uint64_t) <= kArenaLargestBlock;
+}
+
+}  // namespace
+
+// On a pool stream of its own, as DeviceSplitRows and for its reason.
+int DeviceSplitRecords(DeviceRecordsSplitJob* jobs, int n, int device) {
+    if (n <= 0) return 0;
+    if (!jobs || device < 0) return -1;
+    std::vector<int> live;
+    size_t ncols = 0;
+    for (int i = 0; i < n; ++i) {
+        DeviceRecordsSplitJob& j = jobs[i];
+        j.rows = j.others = 0;
+        j.first_bad = ~0ull;
+        j.err = 0;
+        for (uint32_t c = 0; j.columns && c < j.ncols && c < kDeviceRecordMaxColumns; ++c) {
+            j.columns[c].count = j.columns[c].absent = 0;
+        }
+        if (!record_split_job_ok(j)) {
+            j.err = pb_rows::kSplitRefused;
+            continue;
+        }
+        if (j.n == 0) {  // no field: no record, nothing to launch
+            g_split_record_jobs.fetch_add(1, std::memory_order_relaxed);
+            continue;
+        }
+        ncols += j.ncols;
+        live.push_back(i);
+    }
+    if (live.empty()) return 0;
+    const size_t nlive = live.size();
+    // the most aligned first: every struct here is 8-byte aligned
+    PinnedBlock tables(nlive * (sizeof(PbSplitJob) + sizeof(PbRecSplitJob) + sizeof(PbRecSplitResult)) +
+                       ncols * sizeof(PbRecSplitCol));
+    if (!tables) return -1;
+    PbSplitJob* tj = tables.as<PbSplitJob>();
+    PbRecSplitJob* rj = reinterpret_cast<PbRecSplitJob*>(tj + nlive);
+    PbRecSplitResult* tr = reinterpret_cast<PbRecSplitResult*>(rj + nlive);
+    PbRecSplitCol* tc = reinterpret_cast<PbRecSplitCol*>(tr + nlive);
+    PbRecSplitTables r;
+    PbSplitTables& t = r.front;
+    uint64_t nchunks = 0, nrblocks = 0, nbsums = 0, nochunks = 0, nentries = 0, ntags = 0;
+    for (size_t k = 0; k < nlive; ++k) {
+        const DeviceRecordsSplitJob& j = jobs[live[k]];
+        // the row splitter's passes see an occurrence of `number`, whatever it holds
+        PbSplitJob& o = tj[k];
+        o = PbSplitJob{};
+        o.msg = static_cast<const uint8_t*>(j.msg);
+        o.n = (uint32_t)j.n;
+        o.number = j.number;
+        o.kind = pb_rows::kKindBytes;
+        o.first_chunk = (uint32_t)nchunks;
+        o.nchunks = (uint32_t)((j.n + kPbSplitChunk - 1) / kPbSplitChunk);
+        o.nrblocks = 1;
+        nchunks += o.nchunks;
+        PbRecSplitJob& q = rj[k];
+        q = PbRecSplitJob{};
+        q.row_cap = j.row_cap;
+        q.rec_cap = (uint32_t)std::min(j.row_cap, j.n / 2);  // a record has a tag and a length
+        q.first_entry = nentries;
+        q.first_tag = (uint32_t)ntags;
+        q.first_col = (uint32_t)r.ncols;
+        q.ncols = j.ncols;
+        q.first_rblock = (uint32_t)nrblocks;
+        q.nrblocks = (uint32_t)std::max<uint64_t>(1, ((uint64_t)q.rec_cap + kPbSplitBlockRows - 1) / kPbSplitBlockRows);
+        for (uint32_t c = 0; c < j.ncols; ++c) {
+            const DeviceRecordSplitColumn& in = j.columns[c];
+            PbRecSplitCol& col = tc[r.ncols++];
+            col = PbRecSplitCol{};
+            col.values = in.values;
+            col.row_ends = in.row_ends;
+            col.cap = in.cap;
+            col.inner = in.inner;
+            col.kind = in.kind;
+            col.scalar = in.scalar;
+            col.job = (uint32_t)k;
+            col.index = c;
+            col.first_ochunk = (uint32_t)nochunks;
+            if (!in.scalar && !pb_rows::WireIsVarint(in.kind)) {
+                col.nochunks = (uint32_t)((std::min(in.cap, j.n / pb_rows::SourceBytes(in.kind)) + kPbSplitOutChunk - 1) /
+                                          kPbSplitOutChunk);
+            } else if (!in.scalar) {
+                q.any_varint = 1;
+                r.any_varint = true;
+            }
+            nochunks += col.nochunks;
+            col.first_bsum = (uint32_t)nbsums;
+            nbsums += q.nrblocks;
+        }
+        nrblocks += q.nrblocks;
+        nentries += (uint64_t)q.rec_cap * q.ncols;
+        ntags += q.rec_cap;
+        tr[k] = PbRecSplitResult{};
+        tr[k].first_bad = kPbSplitNone;
+    }
+    if (nbsums > 0x7FFFFFFEull || nochunks > 0x7FFFFFFEull || ntags > 0xFFFFFFFFull) return -1;
+    const size_t exit_bytes = (size_t)nchunks * kPbSplitChunk * sizeof(uint32_t);
+    const size_t masks = 2 * (size_t)nchunks * 64;
+    t.skip_hops = (uint32_t)std::max(1, std::min(64, FLAGS_device_split_skip));
+    const bool skips = t.skip_hops > 1 && nchunks > t.skip_hops;  // a short message is chased directly
+    if (!skips) t.skip_hops = 1;
+    // 8-byte tables, then the words
+    const size_t eights = masks * sizeof(uint64_t) + nlive * (sizeof(PbSplitJob) + sizeof(PbRecSplitJob)) +
+                          r.ncols * sizeof(PbRecSplitCol);
+    const size_t words = (size_t)nchunks * 64 + 3 * ((size_t)nchunks + 1) + 2 + (size_t)nbsums + 1 + 3 * nlive +
+                         (skips ? (size_t)nchunks : 0) + (size_t)r.ncols * (1 + sizeof(pb_records::SplitColumn) / 4);
+    HbmBlock exit_block(exit_bytes, device), skip_block(skips ? exit_bytes : 0, device);
+    HbmBlock entry_block(std::max<size_t>(nentries * sizeof(uint64_t), 16), device);
+    HbmBlock bias_block(std::max<size_t>((nentries + ntags) * sizeof(uint32_t), 16), device);
+    HbmBlock scratch(eights + words * sizeof(uint32_t), device);
+    if (!exit_block || !scratch || !entry_block || !bias_block || (skips && !skip_block)) return -1;
+    t.any_varint = r.any_varint;
+    t.skip = skip_block.as<uint32_t>();
+    t.jobs = tj;
+    t.njobs = (int)nlive;
+    t.nchunks = (uint32_t)nchunks;
+    t.nrblocks = 1;
+    t.exit = exit_block.as<uint32_t>();
+    t.term_mask = scratch.as<uint64_t>();
+    t.row_mask = t.term_mask + nchunks * 64;
+    t.jobs_dev = reinterpret_cast<PbSplitJob*>(t.row_mask + nchunks * 64);
+    r.jobs_dev = reinterpret_cast<PbRecSplitJob*>(t.jobs_dev + nlive);
+    r.cols_dev = reinterpret_cast<PbRecSplitCol*>(r.jobs_dev + nlive);
+    t.term_group = reinterpret_cast<uint32_t*>(r.cols_dev + r.ncols);
+    t.term_chunk = t.term_group + nchunks * 64;
+    t.row_chunk = t.term_chunk + nchunks + 1;
+    t.entry = t.row_chunk + nchunks + 1;
+    t.block_sum = t.entry + nchunks + 1;  // the row splitter's: one block, unused here
+    r.block_sum = t.block_sum + 2;
+    t.bad = r.block_sum + nbsums + 1;
+    t.others = t.bad + nlive;
+    t.ok = reinterpret_cast<int32_t*>(t.others + nlive);
+    r.absent = reinterpret_cast<uint32_t*>(t.ok + nlive);
+    r.specs = reinterpret_cast<pb_records::SplitColumn*>(r.absent + r.ncols);
+    t.land = skips ? reinterpret_cast<uint32_t*>(r.specs + r.ncols) : nullptr;
+    r.jobs = rj;
+    r.cols = tc;
+    r.nrblocks = (uint32_t)nrblocks;
+    r.nbsums = (uint32_t)nbsums;
+    r.nochunks = (uint32_t)nochunks;
+    r.entry = entry_block.as<uint64_t>();
+    r.bias = bias_block.as<uint32_t>();
+    r.rec_tag = r.bias + nentries;
+    r.res = tr;
+    if (RunOnPoolStream(device, [&](hipStream_t s) { return LaunchPbRecordsSplit(r, s); }) != 0) return -1;
+    for (size_t k = 0; k < nlive; ++k) {
+        DeviceRecordsSplitJob& j = jobs[live[k]];
+        j.err = tr[k].err;
+        j.rows = tr[k].rows;
+        j.others = tr[k].others;
+        for (uint32_t c = 0; c < j.ncols; ++c) {
+            j.columns[c].count = tr[k].count[c];
+            j.columns[c].absent = tr[k].absent[c];
+        }
+        if (j.err == pb_rows::kSplitMalformed || j.err == pb_rows::kSplitUnsupported) j.first_bad = tr[k].first_bad;
+        if (j.err) continue;
+        g_split_record_jobs.fetch_add(1, std::memory_order_relaxed);
+        g_split_records.fetch_add((int64_t)j.rows, std::memory_order_relaxed);
+    }
+    return 0;
+}
+
 DeviceCodecStats GetDeviceCodecStats() {
     DeviceCodecStats s;
     s.split_row_jobs = g_split_row_jobs.load();
     s.split_rows = g_split_rows.load();
+    s.split_record_jobs = g_split_record_jobs.load();
+    s.split_records = g_split_records.load();
     s.built_row_jobs = g_built_row_jobs.load();
     s.built_rows = g_built_rows.load();
     s.built_row_bytes = g_built_row_bytes.load();

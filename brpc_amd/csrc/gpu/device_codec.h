@@ -202,9 +202,9 @@ int BuildDeviceRows(const DeviceRowsJob& job, Buf* out, int device);
 // base/pb_records.h; pb::SerializeRecords (pb/records.h) is the host twin. A
 // job of one packed or one bytes column is DeviceBuildRows' output byte for
 // byte. As there, the output is a valid message by itself and composes with
-// a BuildDeviceMessage block by concatenation. Only the build side exists:
-// DeviceSplitRows answers 6 for such records (with inner 0 and kind bytes it
-// returns each record's sub-message), and the host parser takes them.
+// a BuildDeviceMessage block by concatenation. DeviceSplitRecords below is
+// the way back; DeviceSplitRows answers 6 for such records (with inner 0 and
+// kind bytes it returns each record's sub-message).
 constexpr uint32_t kDeviceRecordMaxColumns = 8;
 struct DeviceRecordColumn {
     uint32_t inner = 0;  // the field inside the record, 1 .. 2^29-1; numbers may repeat
@@ -285,6 +285,58 @@ struct DeviceRowsSplitJob {
 // (a failed scratch allocation is one); per-job codes in jobs[i].err.
 int DeviceSplitRows(DeviceRowsSplitJob* jobs, int n, int device);
 
+// ---- records back into columns: a message in device memory that holds
+// records of several fields (what DeviceBuildRecords wrote, or any sender's
+// `repeated Example examples = N`, fields in any order, other top-level
+// fields around and between the records) -> every column's flat array, its
+// row ends, and one element per record for a scalar column, without a copy of
+// the message to the host. The rules are base/pb_records.h (RecordShape);
+// pb::SplitRecords (pb/records.h) is the host twin: same codes, same outputs.
+// A ragged column absent from a record is a row of no element, a scalar
+// absent from one reads as 0 and is counted in `absent`. The top-level walk
+// is the row splitter's (gpu/kernels.h LaunchPbRecordsSplit), so the scratch
+// is that of DeviceSplitRows plus a record table of 12 bytes and a tag of 4
+// per (record, column) and record, sized by min(row_cap, n / 2) records.
+struct DeviceRecordSplitColumn {
+    uint32_t inner = 0;   // the field inside the record, 1 .. 2^29-1, distinct among the job's columns
+    uint32_t kind = 0;    // as DeviceRowsJob
+    bool scalar = false;  // one element per record, no row ends (not for bytes)
+    void* values = nullptr;  // device, cap elements, naturally aligned for the kind
+    uint64_t cap = 0;
+    uint32_t* row_ends = nullptr;  // device, 4-byte aligned, the job's row_cap entries; ragged columns only
+    // out
+    uint64_t count = 0;   // elements; a scalar column: the records
+    uint64_t absent = 0;  // scalar columns: records without the field
+};
+struct DeviceRecordsSplitJob {
+    uint32_t number = 0;  // the repeated field, 1 .. 2^29-1
+    DeviceRecordSplitColumn* columns = nullptr;  // host
+    uint32_t ncols = 0;                          // 1 .. kDeviceRecordMaxColumns
+    const void* msg = nullptr;                   // device, any byte alignment
+    uint64_t n = 0;
+    uint64_t row_cap = 0;  // entries of every ragged column's row_ends
+    // out
+    uint64_t rows = 0;           // records: always exact
+    uint64_t others = 0;         // top-level fields other than `number`, skipped
+    uint64_t first_bad = ~0ull;  // with err 1 and 6: the offset of the top-level field that offends
+    // 0 split; 1 malformed wire; 2 refused before any launch (bad number /
+    // inner / kind, a scalar bytes column, ncols 0 or above 8, a duplicate
+    // inner, a null pointer with a nonzero size, misaligned values or
+    // row_ends, n above kDeviceSplitMaxBytes, a record table of min(row_cap,
+    // n / 2) * ncols entries of 8 bytes above the arena's largest block of
+    // 256 MiB); 5 rows > row_cap or a column's count above its cap: the
+    // counts are exact when rows <= row_cap and all 0 otherwise, as the record
+    // table is sized by row_cap; 6 well-formed wire of a shape that is not
+    // split (pb_records::RecordShape): the host parser takes it. 1 and 6 name
+    // the lowest offender and win over 5. With 1, 5 and 6 every output is
+    // untouched; no store ever goes beyond a cap or row_cap.
+    int err = 0;
+};
+// All jobs share one sequence of launches on a pool stream and one wait; the
+// host reads nothing but the result words. Returns -1 only on a device error
+// (a failed scratch allocation is one); per-job codes in jobs[i].err.
+int DeviceSplitRecords(DeviceRecordsSplitJob* jobs, int n, int device);
+
 struct DeviceCodecStats {
     int64_t encodes = 0, encoded_bytes = 0, encoded_out_bytes = 0;
     int64_t decodes = 0, decoded_bytes = 0, bad_tables = 0, decode_errors = 0;
@@ -294,6 +346,7 @@ struct DeviceCodecStats {
     int64_t built_row_jobs = 0, built_rows = 0, built_row_bytes = 0;  // failed row jobs count in build_errors
     int64_t split_row_jobs = 0, split_rows = 0;                       // DeviceSplitRows jobs that ended with code 0
     int64_t built_record_jobs = 0, built_records = 0, built_record_bytes = 0;  // failed ones count in build_errors
+    int64_t split_record_jobs = 0, split_records = 0;  // DeviceSplitRecords jobs that ended with code 0
 };
 DeviceCodecStats GetDeviceCodecStats();
 

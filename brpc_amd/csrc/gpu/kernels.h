@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "base/pb_records.h"
 #include "gpu/gpu.h"
 
 namespace mrpc {
@@ -585,6 +586,101 @@ struct PbSplitTables {
     PbSplitResult* res = nullptr;   // njobs, pinned host
 };
 int LaunchPbRowsSplit(const PbSplitTables& t, hipStream_t s);
+
+// Record splitter: the same message walk, but every occurrence of `number` is
+// a record of up to 8 columns (base/pb_records.h has the rules,
+// pb::SplitRecords is the host twin). The passes up to and including mark and
+// the prefix over the row counts are the row splitter's own kernels, launched
+// on a PbSplitJob that carries the record job's {msg, n, number}: they find
+// and rank every occurrence of `number` whatever it holds, and neither they
+// nor LaunchPbRowsSplit change. What follows is new: six kernels in eight
+// launches (the check kernel is also the varint place pass, the count kernel
+// also the ends pass) and one prefix. With the row splitter's eight a call is
+// 17 launches, 15 when the message is short enough to be chased without the
+// skip table; 3 fewer when no column is a ragged varint one (the prefix over
+// the terminators, check and the varint place pass), 1 fewer when no column is
+// a ragged fixed-width or bytes one:
+//   init    a lane per job copies the record job, a lane per column the
+//           column, and zeroes the absent counters
+//   table   the lane that owns a record's tag applies
+//           pb_records::RecordShape from device memory. Record `rank` gets its
+//           tag offset in rec_tag and, per column, a 64-bit entry {payload
+//           offset (28 bits), payload bytes (28 bits), taken (1 bit)}; for a
+//           scalar that is the value's place. The table holds min(row_cap,
+//           n / 2) records: a record beyond it (the job then ends with 5
+//           unless something is 1 or 6) is judged all the same, and its taken
+//           varint payloads are checked by its lane with pb_rows::VarintsOk,
+//           as the check pass cannot find it in the table
+//   check   a workgroup per message chunk looks for varints of more than ten
+//           bytes (or ten with a last byte above 1). Such a terminator finds
+//           its record by binary search of rec_tag among the records that
+//           meet the chunk, then its column among the record's at most 8
+//           payloads, linearly, as field order inside a record is free.
+//           Terminators inside bytes, fixed-width or scalar payloads are not
+//           elements. A payload is preceded by the last byte of a length, so
+//           a varint's extent needs no bounds
+//   count   a workgroup per 256 records, column after column: the elements of
+//           (record, column) are payload bytes over the width or the
+//           difference of two terminator counts from the spec pass's tables,
+//           summed per block per column; absent scalars are counted per job
+//   prefix  over those sums: a column's are nrblocks consecutive entries
+//   publish a lane per job: the lowest offender, else rows against row_cap
+//           (then every count is 0), else every column's count against its
+//           cap; everything below runs only for jobs whose code is 0
+//   ends    the count kernel again: row_ends of every ragged column, the bias
+//           of varint ones (the row's first element index less the
+//           terminators in front of its payload), and the scalar values,
+//           decoded here (an absent one is 0)
+//   place   varint columns: the check kernel again, a workgroup per message
+//           chunk; every terminator inside a taken varint payload ends one
+//           element. Fixed-width and bytes columns: a workgroup per 2048
+//           output elements per column, every element finds its record in that
+//           column's row_ends by binary search
+// As in the row splitter no workgroup waits for another, every loop is
+// bounded by n, by 8 or by SpecField's invariants, and every table store is
+// guarded by its capacity.
+constexpr uint32_t kPbRecSplitMaxColumns = 8;
+struct PbRecSplitCol {
+    void* values;        // cap elements, naturally aligned
+    uint32_t* row_ends;  // row_cap entries (ragged columns)
+    uint64_t cap;
+    uint32_t inner, kind, scalar;
+    uint32_t job, index;              // its record job and its place among that job's columns
+    uint32_t first_ochunk, nochunks;  // ragged fixed-width and bytes columns: output chunks of 2048 elements
+    uint32_t first_bsum;              // in block_sum: the job's nrblocks entries of this column
+};
+struct PbRecSplitJob {
+    uint64_t row_cap;
+    uint64_t first_entry;             // in entry / bias: rec_cap * ncols entries, record-major
+    uint32_t first_tag, rec_cap;      // in rec_tag: min(row_cap, n / 2) records
+    uint32_t first_col, ncols;
+    uint32_t first_rblock, nrblocks;  // blocks of 256 records: ceil(rec_cap / 256), at least 1
+    uint32_t any_varint;              // some column is a ragged varint one
+};
+struct PbRecSplitResult {
+    uint64_t rows, others;
+    uint64_t count[kPbRecSplitMaxColumns], absent[kPbRecSplitMaxColumns];
+    uint32_t first_bad;
+    int32_t err;  // 0, 1, 5, 6
+};
+struct PbRecSplitTables {
+    PbSplitTables front;  // the row splitter's passes up to the row ranks: nrblocks 1, nochunks 0, nrows 0
+    const PbRecSplitJob* jobs = nullptr;  // pinned host, front.njobs of them
+    const PbRecSplitCol* cols = nullptr;  // pinned host
+    int ncols = 0;
+    PbRecSplitJob* jobs_dev = nullptr;
+    PbRecSplitCol* cols_dev = nullptr;
+    pb_records::SplitColumn* specs = nullptr;  // ncols: what RecordShape reads
+    uint32_t nrblocks = 0, nbsums = 0, nochunks = 0;
+    bool any_varint = false;
+    uint64_t* entry = nullptr;      // sum of rec_cap * ncols
+    uint32_t* bias = nullptr;       // as entry
+    uint32_t* rec_tag = nullptr;    // sum of rec_cap
+    uint32_t* block_sum = nullptr;  // nbsums + 1, scanned
+    uint32_t* absent = nullptr;     // ncols
+    PbRecSplitResult* res = nullptr;  // front.njobs, pinned host
+};
+int LaunchPbRecordsSplit(const PbRecSplitTables& t, hipStream_t s);
 
 // JSON float / double arrays (gpu/json_kernels.hip): arrays in device (or
 // pinned host) memory become "v,v,...,v" in device memory, every element

@@ -1722,21 +1722,351 @@ __global__ void __launch_bounds__(kRunThreads) pb_split_place_kernel(const PbSpl
     }
 }
 
+
+// ---------------------------------------------------------- record splitter
+// A message of records -> every column's flat array, row ends and scalars
+// (kernels.h: the row splitter's passes up to the row ranks, then init, table,
+// check, count, prefix, publish, ends, place; the rules are
+// base/pb_records.h). A table entry is the payload's offset (28 bits), its
+// bytes (28 bits) and a taken bit; an untaken one is 0, a payload of no byte.
+constexpr uint64_t kRecTaken = 1ull << 56;
+__device__ __forceinline__ uint64_t rec_pack(uint32_t off, uint32_t len) {
+    return (uint64_t)off | ((uint64_t)len << 28) | kRecTaken;
+}
+__device__ __forceinline__ bool rec_taken(uint64_t e) { return (e & kRecTaken) != 0; }
+__device__ __forceinline__ uint32_t rec_off(uint64_t e) { return (uint32_t)e & 0x0FFFFFFFu; }
+__device__ __forceinline__ uint32_t rec_len(uint64_t e) { return (uint32_t)(e >> 28) & 0x0FFFFFFFu; }
+
+__global__ void __launch_bounds__(64) pb_recsplit_init_kernel(const PbRecSplitJob* __restrict__ jobs, int njobs,
+                                                              PbRecSplitJob* __restrict__ jobs_dev,
+                                                              const PbRecSplitCol* __restrict__ cols, int ncols,
+                                                              PbRecSplitCol* __restrict__ cols_dev,
+                                                              pb_records::SplitColumn* __restrict__ specs,
+                                                              uint32_t* __restrict__ absent,
+                                                              uint32_t* __restrict__ block_sum, uint32_t nbsums) {
+    const int i = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (i == 0) block_sum[nbsums] = 0;  // behind the last column's: its prefix is that column's total
+    if (i < njobs) jobs_dev[i] = jobs[i];
+    if (i >= ncols) return;
+    const PbRecSplitCol col = cols[i];
+    cols_dev[i] = col;
+    specs[i].inner = col.inner;
+    specs[i].kind = col.kind;
+    specs[i].scalar = col.scalar;
+    absent[i] = 0;
+}
+
+__global__ void __launch_bounds__(kRunThreads) pb_recsplit_table_kernel(
+    const PbSplitJob* __restrict__ jobs, int njobs, const PbRecSplitJob* __restrict__ rjobs,
+    const pb_records::SplitColumn* __restrict__ specs, const uint64_t* __restrict__ row_mask,
+    const uint32_t* __restrict__ row_chunk, uint64_t* __restrict__ entry, uint32_t* __restrict__ rec_tag,
+    uint32_t* __restrict__ bad) {
+    __shared__ uint32_t before[64];
+    const int j = wg::job_of<&PbSplitJob::first_chunk>(jobs, njobs, blockIdx.x);
+    const PbSplitJob job = jobs[j];
+    const PbRecSplitJob rj = rjobs[j];
+    if (row_chunk[blockIdx.x + 1] == row_chunk[blockIdx.x]) return;
+    const uint32_t t = threadIdx.x;
+    const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbSplitChunk;
+    if (t < 64) {
+        const uint32_t mine = (uint32_t)__popcll(row_mask[(size_t)blockIdx.x * 64 + t]);
+        before[t] = wg::wave_incl_scan(mine) - mine;
+    }
+    __syncthreads();
+    const uint64_t m = row_mask[(size_t)blockIdx.x * 64 + (t >> 2)];
+    const uint32_t sh = (t & 3) * 16;
+    uint32_t mine = (uint32_t)(m >> sh) & 0xFFFFu;
+    uint32_t rank = row_chunk[blockIdx.x] - row_chunk[job.first_chunk] + before[t >> 2] +
+                    (uint32_t)__popcll(m & ((1ull << sh) - 1));
+    const pb_records::SplitColumn* cols = specs + rj.first_col;
+    while (mine) {
+        const uint32_t bit = (uint32_t)__ffs((int)mine) - 1;
+        mine &= mine - 1;
+        const uint32_t p = cs + t * 16 + bit;
+        const pb_rows::Field f = pb_rows::SpecField(job.msg, p, job.n);  // a record: the mark pass parsed it
+        // a record beyond the table is judged all the same: 1 and 6 win over 5
+        const bool keep = rank < rj.rec_cap;
+        uint64_t* row = entry + rj.first_entry + (uint64_t)rank * rj.ncols;
+        if (keep) {
+            rec_tag[rj.first_tag + rank] = p;
+            for (uint32_t c = 0; c < rj.ncols; ++c) row[c] = 0;
+        }
+        int code = pb_rows::kSplitMalformed;
+        if (f.valid) {
+            bool refused = false;
+            code = pb_records::RecordShape(job.msg, f.vpos, f.vlen, cols, rj.ncols,
+                                           [&](uint32_t c, uint64_t off, uint64_t len) {
+                                               if (keep) {
+                                                   row[c] = rec_pack((uint32_t)off, (uint32_t)len);
+                                               } else if (!cols[c].scalar && pb_rows::WireIsVarint(cols[c].kind)) {
+                                                   uint64_t ne = 0;  // the check pass cannot find this record
+                                                   if (!pb_rows::VarintsOk(job.msg + off, len, &ne)) refused = true;
+                                               }
+                                           });
+            if (refused) code = pb_rows::kSplitMalformed;
+        }
+        if (code != 0) atomicMin(&bad[j], (p << 3) | (uint32_t)code);
+        ++rank;
+    }
+}
+
+// Ragged varint columns, a workgroup per message chunk. kPlace false: the
+// check pass (a varint the packed-run decoder refuses, inside a taken varint
+// payload, is reported). kPlace true: the place pass (every terminator inside
+// such a payload ends one element).
+template <bool kPlace>
+__global__ void __launch_bounds__(kRunThreads) pb_recsplit_varint_kernel(
+    const PbSplitJob* __restrict__ jobs, int njobs, const PbRecSplitJob* __restrict__ rjobs,
+    const PbRecSplitCol* __restrict__ cols, const uint64_t* __restrict__ entry, const uint32_t* __restrict__ rec_tag,
+    const uint32_t* __restrict__ bias, const uint64_t* __restrict__ term_mask, const uint32_t* __restrict__ term_group,
+    const uint32_t* __restrict__ term_chunk, const uint32_t* __restrict__ row_chunk, uint32_t* __restrict__ bad,
+    const int32_t* __restrict__ ok) {
+    __shared__ u32x4 raw[kSplitStage16];
+    const int j = wg::job_of<&PbSplitJob::first_chunk>(jobs, njobs, blockIdx.x);
+    const PbSplitJob job = jobs[j];
+    const PbRecSplitJob rj = rjobs[j];
+    if (!rj.any_varint || (kPlace && !ok[j])) return;
+    // the records that start in this chunk, and the one before them that may reach into it
+    const uint32_t first = row_chunk[job.first_chunk];
+    uint32_t hi = row_chunk[blockIdx.x + 1] - first;
+    uint32_t lo = row_chunk[blockIdx.x] - first;
+    lo = lo ? lo - 1 : 0;
+    if (hi > rj.rec_cap) hi = rj.rec_cap;  // the table pass checked the records beyond the table itself
+    if (lo >= hi) return;
+    const uint32_t t = threadIdx.x;
+    const uint32_t cs = (blockIdx.x - job.first_chunk) * kPbSplitChunk;
+    const uint32_t len = job.n - cs < kPbSplitChunk ? job.n - cs : kPbSplitChunk;
+    const uint8_t* bytes = split_stage(job, cs, len, kSplitBack, raw);
+    const uint32_t* tags = rec_tag + rj.first_tag;
+    const size_t g = (size_t)blockIdx.x * 64 + (t >> 2);
+    const uint64_t m = term_mask[g];
+    uint32_t terms = 0;  // terminators in front of this lane's bytes
+    if (kPlace) {
+        terms = term_chunk[blockIdx.x] - term_chunk[job.first_chunk] + term_group[g] +
+                (uint32_t)__popcll(m & ((1ull << ((t & 3) * 16)) - 1));
+    }
+    __syncthreads();
+    uint32_t mine = (uint32_t)(m >> ((t & 3) * 16)) & 0xFFFFu;
+    while (mine) {
+        const uint32_t bit = (uint32_t)__ffs((int)mine) - 1;
+        mine &= mine - 1;
+        const int i = (int)(t * 16 + bit);  // bytes[i - 10 ..] is staged when it is in the message
+        const uint32_t q = cs + (uint32_t)i;
+        uint32_t nb = 1;  // bytes of the varint that ends at q; 11: more than ten
+        uint64_t v = bytes[i] & 0x7f;
+        while (nb <= 10 && nb <= q && (bytes[i - (int)nb] & 0x80)) {
+            v = (v << 7) | (bytes[i - (int)nb] & 0x7f);
+            ++nb;
+        }
+        const bool refused = nb > 10 || (nb == 10 && bytes[i] > 1);
+        if ((kPlace || refused) && tags[lo] <= q) {
+            // the last record whose tag is at or before q, then the column whose payload holds q
+            uint32_t a = lo, z = hi;
+            while (z - a > 1) {
+                const uint32_t mid = a + (z - a) / 2;
+                if (tags[mid] <= q) {
+                    a = mid;
+                } else {
+                    z = mid;
+                }
+            }
+            const uint64_t at0 = rj.first_entry + (uint64_t)a * rj.ncols;
+            for (uint32_t c = 0; c < rj.ncols; ++c) {
+                const uint64_t e = entry[at0 + c];
+                if (!rec_taken(e) || q - rec_off(e) >= rec_len(e)) continue;  // q below the offset wraps
+                const PbRecSplitCol& col = cols[rj.first_col + c];
+                if (col.scalar || !pb_rows::WireIsVarint(col.kind)) break;  // no element ends here
+                if (!kPlace) {
+                    atomicMin(&bad[j], (tags[a] << 3) | (uint32_t)pb_rows::kSplitMalformed);
+                } else {
+                    const uint32_t at = bias[at0 + c] + terms;
+                    if ((uint64_t)at < col.cap) pb_rows::StoreVarintElem(col.values, at, col.kind, v);
+                }
+                break;
+            }
+        }
+        ++terms;
+    }
+}
+
+// A workgroup per 256 records, column after column. kEnds false: the count
+// pass (each column's elements in the block, the absent scalars). kEnds true:
+// row_ends, bias and the scalar values of the jobs that passed.
+template <bool kEnds>
+__global__ void __launch_bounds__(kPbSplitBlockRows) pb_recsplit_rows_kernel(
+    const PbSplitJob* __restrict__ jobs, int njobs, const PbRecSplitJob* __restrict__ rjobs,
+    const PbRecSplitCol* __restrict__ cols, const uint64_t* __restrict__ entry,
+    const uint64_t* __restrict__ term_mask, const uint32_t* __restrict__ term_group,
+    const uint32_t* __restrict__ term_chunk, const uint32_t* __restrict__ row_chunk, uint32_t* __restrict__ block_sum,
+    uint32_t* __restrict__ bias, uint32_t* __restrict__ absent, const int32_t* __restrict__ ok) {
+    __shared__ uint32_t wave_tot[kPbSplitBlockRows / 64];
+    const int j = wg::job_of<&PbRecSplitJob::first_rblock>(rjobs, njobs, blockIdx.x);
+    const PbSplitJob job = jobs[j];
+    const PbRecSplitJob rj = rjobs[j];
+    if (kEnds && !ok[j]) return;
+    uint32_t rows = split_total(row_chunk, job.first_chunk, job.nchunks);
+    if (rows > rj.rec_cap) rows = rj.rec_cap;  // the job ends with 5 (or 1, 6): its counts are not reported
+    const uint32_t blk = blockIdx.x - rj.first_rblock;
+    const uint32_t r = blk * kPbSplitBlockRows + threadIdx.x;
+    for (uint32_t c = 0; c < rj.ncols; ++c) {
+        const PbRecSplitCol col = cols[rj.first_col + c];
+        const uint64_t at = rj.first_entry + (uint64_t)r * rj.ncols + c;
+        const uint64_t e = r < rows ? entry[at] : 0;
+        const bool varints = pb_rows::WireIsVarint(col.kind);
+        if (col.scalar) {
+            if (!kEnds) {
+                const uint32_t miss = wg::wave_sum((uint32_t)(r < rows && !rec_taken(e)));
+                if ((threadIdx.x & 63) == 0 && miss) atomicAdd(&absent[rj.first_col + c], miss);
+                if (threadIdx.x == 0) block_sum[col.first_bsum + blk] = 0;  // its count is the records
+            } else if (r < rows) {
+                // r < rows <= cap: the job passed. An absent scalar reads as 0.
+                const uint8_t* s = job.msg + rec_off(e);
+                uint64_t v = 0;
+                if (varints) {
+                    uint32_t used = 0;
+                    if (rec_taken(e)) pb_rows::GetVarint(s, rec_len(e), &used, &v);
+                    pb_rows::StoreVarintElem(col.values, r, col.kind, v);
+                } else {
+                    const uint32_t w = pb_rows::SourceBytes(col.kind);
+                    for (uint32_t b = 0; b < w && rec_taken(e); ++b) v |= (uint64_t)s[b] << (8 * b);
+                    if (w == 4) {
+                        static_cast<uint32_t*>(col.values)[r] = (uint32_t)v;
+                    } else {
+                        static_cast<uint64_t*>(col.values)[r] = v;
+                    }
+                }
+            }
+            continue;
+        }
+        uint32_t ne = 0, front = 0;
+        if (r < rows) {
+            const uint32_t po = rec_off(e), pl = rec_len(e);
+            if (!varints) {
+                ne = pl / pb_rows::SourceBytes(col.kind);
+            } else if (pl > 0) {
+                front = split_terms_before(job, term_mask, term_group, term_chunk, po);
+                ne = split_terms_before(job, term_mask, term_group, term_chunk, po + pl) - front;
+            }
+        }
+        uint32_t sum;
+        uint32_t before = wg::block_excl_scan<(int)kPbSplitBlockRows>(ne, wave_tot, &sum);
+        __syncthreads();  // the next column's scan writes wave_tot again
+        if (!kEnds) {
+            if (threadIdx.x == 0) block_sum[col.first_bsum + blk] = sum;
+            continue;
+        }
+        if (r >= rows) continue;  // rows <= row_cap, count <= cap: the job passed
+        before += block_sum[col.first_bsum + blk] - block_sum[col.first_bsum];
+        col.row_ends[r] = before + ne;
+        if (varints) bias[at] = before - front;
+    }
+}
+
+__global__ void __launch_bounds__(64) pb_recsplit_publish_kernel(
+    const PbSplitJob* __restrict__ jobs, int njobs, const PbRecSplitJob* __restrict__ rjobs,
+    const PbRecSplitCol* __restrict__ cols, const uint32_t* __restrict__ row_chunk,
+    const uint32_t* __restrict__ block_sum, const uint32_t* __restrict__ absent, const uint32_t* __restrict__ bad,
+    const uint32_t* __restrict__ others, int32_t* __restrict__ ok, PbRecSplitResult* __restrict__ res) {
+    const int j = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (j >= njobs) return;
+    const PbSplitJob job = jobs[j];
+    const PbRecSplitJob rj = rjobs[j];
+    const uint32_t key = bad[j];
+    // res[j] arrives zeroed, first_bad none: the counts of a job that fails with 1 or 6, or with more
+    // records than row_cap, stay 0
+    int32_t err = 0;
+    if (key != kPbSplitNone) {
+        res[j].first_bad = key >> 3;
+        err = (int32_t)(key & 7);
+    } else {
+        const uint32_t rows = split_total(row_chunk, job.first_chunk, job.nchunks);
+        res[j].rows = rows;
+        res[j].others = others[j];
+        if (rows > rj.row_cap) {
+            err = pb_rows::kSplitShort;
+        } else {
+            for (uint32_t c = 0; c < rj.ncols; ++c) {
+                const PbRecSplitCol& col = cols[rj.first_col + c];
+                const uint64_t count = col.scalar ? rows : split_total(block_sum, col.first_bsum, rj.nrblocks);
+                res[j].count[c] = count;
+                res[j].absent[c] = col.scalar ? absent[rj.first_col + c] : 0;
+                if (count > col.cap) err = pb_rows::kSplitShort;
+            }
+        }
+    }
+    res[j].err = err;
+    ok[j] = err == 0;
+}
+
+// Ragged fixed-width and bytes columns: a workgroup per 2048 elements of one
+// column's output.
+__global__ void __launch_bounds__(kRunThreads) pb_recsplit_place_kernel(
+    const PbSplitJob* __restrict__ jobs, const PbRecSplitJob* __restrict__ rjobs,
+    const PbRecSplitCol* __restrict__ cols, int ncols, const uint64_t* __restrict__ entry,
+    const uint32_t* __restrict__ row_chunk, const uint32_t* __restrict__ block_sum, const int32_t* __restrict__ ok) {
+    const PbRecSplitCol col = cols[wg::job_of<&PbRecSplitCol::first_ochunk>(cols, ncols, blockIdx.x)];
+    const int j = (int)col.job;
+    if (!ok[j] || blockIdx.x - col.first_ochunk >= col.nochunks) return;
+    const PbSplitJob job = jobs[j];
+    const PbRecSplitJob rj = rjobs[j];
+    const uint32_t count = split_total(block_sum, col.first_bsum, rj.nrblocks);
+    const uint32_t rows = split_total(row_chunk, job.first_chunk, job.nchunks);
+    const uint32_t i0 = (blockIdx.x - col.first_ochunk) * kPbSplitOutChunk;
+    if (i0 >= count || rows == 0) return;
+    const uint32_t i1 = count - i0 < kPbSplitOutChunk ? count - 1 : i0 + kPbSplitOutChunk - 1;
+    const uint32_t* ends = col.row_ends;
+    // the first record whose end lies beyond element i, among records [lo, hi]
+    auto row_of = [ends](uint32_t lo, uint32_t hi, uint32_t i) {
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (ends[mid] > i) {
+                hi = mid;
+            } else {
+                lo = mid + 1;
+            }
+        }
+        return lo;
+    };
+    const uint32_t r_lo = row_of(0, rows - 1, i0), r_hi = row_of(r_lo, rows - 1, i1);
+    const uint32_t w = pb_rows::SourceBytes(col.kind);
+    for (uint32_t k = 0; k < kPbSplitOutChunk / kRunThreads; ++k) {
+        const uint32_t i = i0 + k * kRunThreads + threadIdx.x;
+        if (i > i1) break;
+        const uint32_t r = row_of(r_lo, r_hi, i);
+        const uint32_t start = r ? ends[r - 1] : 0;
+        const uint64_t e = entry[rj.first_entry + (uint64_t)r * rj.ncols + col.index];
+        const uint32_t off = (i - start) * w;
+        if (i < start || off + w > rec_len(e)) continue;  // never: row_ends are sums of these lengths
+        const uint8_t* s = job.msg + rec_off(e) + off;
+        uint64_t v = 0;
+        for (uint32_t b = 0; b < w; ++b) v |= (uint64_t)s[b] << (8 * b);
+        if (w == 1) {
+            static_cast<uint8_t*>(col.values)[i] = (uint8_t)v;
+        } else if (w == 4) {
+            static_cast<uint32_t*>(col.values)[i] = (uint32_t)v;
+        } else {
+            static_cast<uint64_t*>(col.values)[i] = v;
+        }
+    }
+}
+
 }  // namespace
 
-int LaunchPbRowsSplit(const PbSplitTables& t, hipStream_t s) {
-    if (t.njobs <= 0) return 0;
+#define SPLIT_LAUNCH(kernel, grid, block, ...)                          \
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, t.jobs_dev, t.njobs, __VA_ARGS__); \
+    if (hipGetLastError() != hipSuccess) return -1
+
+// The passes both splitters share: the top-level field starts, and with them
+// every occurrence of `number` marked and ranked (row_chunk scanned).
+static int split_front(const PbSplitTables& t, hipStream_t s) {
     if (!t.jobs || !t.jobs_dev || !t.exit || !t.term_mask || !t.row_mask || !t.term_group || !t.term_chunk ||
-        !t.row_chunk || !t.entry || !t.block_sum || !t.bad || !t.others || !t.ok || !t.res || t.nchunks == 0 ||
+        !t.row_chunk || !t.entry || !t.block_sum || !t.bad || !t.others || !t.ok || t.nchunks == 0 ||
         t.nrblocks == 0 || t.nchunks > 0x7FFFFFFEu || t.nrblocks > 0x7FFFFFFEu || (t.nrows > 0 && !t.row_bias) ||
         t.skip_hops == 0 || (t.skip_hops > 1 && (!t.skip || !t.land))) {
         return -1;
     }
     const bool skips = t.skip_hops > 1;
     const dim3 per_job((unsigned)(t.njobs + 63) / 64), wave(64), wg(kRunThreads);
-#define SPLIT_LAUNCH(kernel, grid, block, ...)                          \
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, t.jobs_dev, t.njobs, __VA_ARGS__); \
-    if (hipGetLastError() != hipSuccess) return -1
     hipLaunchKernelGGL(pb_split_init_kernel, per_job, wave, 0, s, t.jobs, t.njobs, t.jobs_dev, t.term_chunk,
                        t.row_chunk, t.block_sum, t.nchunks, t.nrblocks, t.bad, t.others, t.ok);
     if (hipGetLastError() != hipSuccess) return -1;
@@ -1752,7 +2082,13 @@ int LaunchPbRowsSplit(const PbSplitTables& t, hipStream_t s) {
         SPLIT_LAUNCH(pb_split_chase_kernel, per_job, wave, t.exit, t.entry);
     }
     SPLIT_LAUNCH(pb_split_mark_kernel, dim3(t.nchunks), wg, t.entry, t.row_mask, t.row_chunk, t.bad, t.others);
-    if (LaunchPbRunPrefix(t.row_chunk, (int)t.nchunks + 1, s) != 0) return -1;
+    return LaunchPbRunPrefix(t.row_chunk, (int)t.nchunks + 1, s);
+}
+
+int LaunchPbRowsSplit(const PbSplitTables& t, hipStream_t s) {
+    if (t.njobs <= 0) return 0;
+    if (!t.res || split_front(t, s) != 0) return -1;
+    const dim3 per_job((unsigned)(t.njobs + 63) / 64), wave(64), wg(kRunThreads);
     SPLIT_LAUNCH(pb_split_table_kernel, dim3(t.nchunks), wg, t.row_mask, t.row_chunk, t.exit, t.bad);
     if (t.any_varint) {
         SPLIT_LAUNCH(pb_split_varint_kernel<false>, dim3(t.nchunks), wg, t.exit, t.term_mask, t.term_group,
@@ -1771,9 +2107,47 @@ int LaunchPbRowsSplit(const PbSplitTables& t, hipStream_t s) {
     if (t.nochunks > 0) {
         SPLIT_LAUNCH(pb_split_place_kernel, dim3(t.nochunks), wg, t.exit, t.row_chunk, t.block_sum, t.ok);
     }
-#undef SPLIT_LAUNCH
     return 0;
 }
+
+int LaunchPbRecordsSplit(const PbRecSplitTables& r, hipStream_t s) {
+    const PbSplitTables& t = r.front;
+    if (t.njobs <= 0) return 0;
+    if (!r.jobs || !r.cols || !r.jobs_dev || !r.cols_dev || !r.specs || !r.entry || !r.bias || !r.rec_tag ||
+        !r.block_sum || !r.absent || !r.res || r.ncols <= 0 || r.nrblocks == 0 || r.nrblocks > 0x7FFFFFFEu ||
+        r.nbsums == 0 || r.nbsums > 0x7FFFFFFEu || t.any_varint != r.any_varint || split_front(t, s) != 0) {
+        return -1;
+    }
+    const int most = t.njobs > r.ncols ? t.njobs : r.ncols;
+    const dim3 per_job((unsigned)(t.njobs + 63) / 64), wave(64), wg(kRunThreads), rblocks(r.nrblocks);
+    hipLaunchKernelGGL(pb_recsplit_init_kernel, dim3((unsigned)(most + 63) / 64), wave, 0, s, r.jobs, t.njobs,
+                       r.jobs_dev, r.cols, r.ncols, r.cols_dev, r.specs, r.absent, r.block_sum, r.nbsums);
+    if (hipGetLastError() != hipSuccess) return -1;
+    SPLIT_LAUNCH(pb_recsplit_table_kernel, dim3(t.nchunks), wg, r.jobs_dev, r.specs, t.row_mask, t.row_chunk, r.entry,
+                 r.rec_tag, t.bad);
+    if (r.any_varint) {
+        SPLIT_LAUNCH(pb_recsplit_varint_kernel<false>, dim3(t.nchunks), wg, r.jobs_dev, r.cols_dev, r.entry, r.rec_tag,
+                     r.bias, t.term_mask, t.term_group, t.term_chunk, t.row_chunk, t.bad, t.ok);
+    }
+    SPLIT_LAUNCH(pb_recsplit_rows_kernel<false>, rblocks, dim3(kPbSplitBlockRows), r.jobs_dev, r.cols_dev, r.entry,
+                 t.term_mask, t.term_group, t.term_chunk, t.row_chunk, r.block_sum, r.bias, r.absent, t.ok);
+    if (LaunchPbRunPrefix(r.block_sum, (int)r.nbsums + 1, s) != 0) return -1;
+    SPLIT_LAUNCH(pb_recsplit_publish_kernel, per_job, wave, r.jobs_dev, r.cols_dev, t.row_chunk, r.block_sum, r.absent,
+                 t.bad, t.others, t.ok, r.res);
+    SPLIT_LAUNCH(pb_recsplit_rows_kernel<true>, rblocks, dim3(kPbSplitBlockRows), r.jobs_dev, r.cols_dev, r.entry,
+                 t.term_mask, t.term_group, t.term_chunk, t.row_chunk, r.block_sum, r.bias, r.absent, t.ok);
+    if (r.any_varint) {
+        SPLIT_LAUNCH(pb_recsplit_varint_kernel<true>, dim3(t.nchunks), wg, r.jobs_dev, r.cols_dev, r.entry, r.rec_tag,
+                     r.bias, t.term_mask, t.term_group, t.term_chunk, t.row_chunk, t.bad, t.ok);
+    }
+    if (r.nochunks > 0) {
+        hipLaunchKernelGGL(pb_recsplit_place_kernel, dim3(r.nochunks), wg, 0, s, t.jobs_dev, r.jobs_dev, r.cols_dev,
+                           r.ncols, r.entry, t.row_chunk, r.block_sum, t.ok);
+        if (hipGetLastError() != hipSuccess) return -1;
+    }
+    return 0;
+}
+#undef SPLIT_LAUNCH
 
 int LaunchPbRowsBuild(const PbRowsTables& t, hipStream_t s) {
     if (t.njobs <= 0) return 0;

@@ -85,6 +85,10 @@ typedef std::tuple<uint32_t, uint32_t, uint32_t, uintptr_t, uint64_t, uintptr_t,
 typedef std::tuple<uint32_t, uint32_t, uintptr_t, uint64_t, uintptr_t> RecordColumnRow;
 // (number, columns, rows, dst, cap) rows of device_build_records
 typedef std::tuple<uint32_t, std::vector<RecordColumnRow>, uint64_t, uintptr_t, uint64_t> RecordsJobRow;
+// (inner, kind, scalar, values, cap, row_ends) columns and (number, columns,
+// msg, n, row_cap) rows of device_split_records
+typedef std::tuple<uint32_t, uint32_t, bool, uintptr_t, uint64_t, uintptr_t> RecordSplitColumnRow;
+typedef std::tuple<uint32_t, std::vector<RecordSplitColumnRow>, uintptr_t, uint64_t, uint64_t> RecordsSplitJobRow;
 std::vector<gpu::DeviceMessageField> message_fields(const std::vector<MessageFieldRow>& rows) {
     std::vector<gpu::DeviceMessageField> fs(rows.size());
     for (size_t i = 0; i < rows.size(); ++i) {
@@ -337,6 +341,47 @@ void bind_gpu_ops(py::module_& g) {
         }
         return out;
     }, py::arg("jobs"), py::arg("device") = 0);
+    // Records back into columns: table = [(number, [(inner, kind, scalar,
+    // values, cap, row_ends)], msg, n, row_cap)], msg / values / row_ends
+    // device pointers (row_ends 0 for a scalar column) -> [(rows, others, err,
+    // first_bad, [(count, absent)])] (gpu::DeviceSplitRecords; all jobs share
+    // one launch sequence).
+    g.def("device_split_records", [](const std::vector<RecordsSplitJobRow>& table, int device) {
+        std::vector<gpu::DeviceRecordsSplitJob> js(table.size());
+        std::vector<std::vector<gpu::DeviceRecordSplitColumn>> cols(table.size());
+        for (size_t i = 0; i < table.size(); ++i) {
+            const std::vector<RecordSplitColumnRow>& rows = std::get<1>(table[i]);
+            cols[i].resize(rows.size());
+            for (size_t c = 0; c < rows.size(); ++c) {
+                cols[i][c].inner = std::get<0>(rows[c]);
+                cols[i][c].kind = std::get<1>(rows[c]);
+                cols[i][c].scalar = std::get<2>(rows[c]);
+                cols[i][c].values = (void*)std::get<3>(rows[c]);
+                cols[i][c].cap = std::get<4>(rows[c]);
+                cols[i][c].row_ends = (uint32_t*)std::get<5>(rows[c]);
+            }
+            js[i].number = std::get<0>(table[i]);
+            js[i].columns = cols[i].data();
+            js[i].ncols = (uint32_t)cols[i].size();
+            js[i].msg = (const void*)std::get<2>(table[i]);
+            js[i].n = std::get<3>(table[i]);
+            js[i].row_cap = std::get<4>(table[i]);
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceSplitRecords(js.data(), (int)js.size(), device);
+        }
+        check(rc, "device_split_records");
+        py::list out;
+        for (size_t i = 0; i < js.size(); ++i) {
+            py::list per;
+            // a job refused for its column count reports no column
+            for (size_t c = 0; c < cols[i].size(); ++c) per.append(py::make_tuple(cols[i][c].count, cols[i][c].absent));
+            out.append(py::make_tuple(js[i].rows, js[i].others, js[i].err, js[i].first_bad, per));
+        }
+        return out;
+    }, py::arg("table"), py::arg("device") = 0);
     g.def("device_split_max_bytes", []() { return gpu::kDeviceSplitMaxBytes; });
     // Records: jobs = [(number, [(inner, kind, src, count, row_ends)], rows,
     // dst, cap)], src / row_ends / dst device pointers, row_ends 0 for a

@@ -211,9 +211,101 @@ public:
     // `number`, appended to one Buf. Returns the echoed attachment's bytes.
     py::bytes echo_device_records(const MessageFields& fields, uint32_t number, const RecordColumns& columns,
                                   uint64_t rows, int device) {
+        Controller cntl;
+        std::string got;
+        int copy_rc = 0;
+        echo_records(fields, number, columns, rows, device, &cntl,
+                     [&]() { copy_rc = gpu::CopyBufToHost(cntl.response_attachment(), &got); });
+        if (copy_rc != 0) throw std::runtime_error("copying the echoed attachment to the host failed");
+        return py::bytes(got);
+    }
+    // The same round trip, then the echoed attachment is split where it
+    // arrived (gpu::DeviceSplitRecords on its device block; blocks that
+    // arrived apart are gathered into one in HBM first), with no host copy of
+    // it: only the split's outputs come to the host. `split` is [(inner,
+    // kind, scalar)], the columns to take. Returns ([(values bytes, row_ends
+    // list or None, absent)] per split column, others).
+    py::tuple echo_device_records_split(const MessageFields& fields, uint32_t number, const RecordColumns& columns,
+                                        uint64_t rows, const std::vector<std::tuple<uint32_t, uint32_t, bool>>& split,
+                                        int device) {
+        Controller cntl;
+        std::vector<gpu::DeviceRecordSplitColumn> cols(split.size());
+        for (size_t c = 0; c < split.size(); ++c) {
+            cols[c].inner = std::get<0>(split[c]);
+            cols[c].kind = std::get<1>(split[c]);
+            cols[c].scalar = std::get<2>(split[c]);
+            if (!pb_records::ColumnOk(cols[c].inner, cols[c].kind, cols[c].scalar)) {
+                throw std::invalid_argument("split column refused");
+            }
+        }
+        if (cols.empty() || cols.size() > gpu::kDeviceRecordMaxColumns) throw std::invalid_argument("1 to 8 split columns");
+        gpu::DeviceRecordsSplitJob job;
+        job.number = number;
+        job.columns = cols.data();
+        job.ncols = (uint32_t)cols.size();
+        std::vector<std::string> values(cols.size());
+        std::vector<std::vector<uint32_t>> row_ends(cols.size());
+        int rc = 0;
+        echo_records(fields, number, columns, rows, device, &cntl, [&]() {
+            const Buf& got = cntl.response_attachment();
+            Buf gathered;
+            const Buf* one = &got;
+            if (got.backing_block_num() != 1 || got.ref_at(0).block->kind != MemKind::DEVICE ||
+                got.ref_at(0).block->device != device) {
+                if (gpu::GatherToDevice(got, &gathered, device) != 0 || gathered.backing_block_num() != 1) {
+                    rc = -1;
+                    return;
+                }
+                one = &gathered;
+            }
+            job.msg = one->block_data(0);
+            job.n = one->block_len(0);
+            job.row_cap = job.n / 2;
+            std::vector<gpu::HbmBlock> vals, ends;
+            for (gpu::DeviceRecordSplitColumn& col : cols) {
+                const size_t eb = pb_rows::SourceBytes(col.kind);
+                col.cap = col.scalar ? job.row_cap : job.n / (pb_rows::WireIsVarint(col.kind) ? 1 : eb);
+                vals.emplace_back(std::max<size_t>(col.cap * eb, 16), device);
+                ends.emplace_back(col.scalar ? 0 : std::max<size_t>(job.row_cap * 4, 16), device);
+                if (!vals.back() || (!col.scalar && !ends.back())) {
+                    rc = -1;
+                    return;
+                }
+                col.values = vals.back().p;
+                col.row_ends = ends.back().as<uint32_t>();
+            }
+            rc = gpu::DeviceSplitRecords(&job, 1, device);
+            if (rc != 0 || job.err != 0) return;
+            for (size_t c = 0; c < cols.size() && rc == 0; ++c) {
+                values[c].resize((size_t)cols[c].count * pb_rows::SourceBytes(cols[c].kind));
+                if (!values[c].empty()) rc = gpu::CopyDeviceToHost(&values[c][0], vals[c].p, values[c].size(), device);
+                if (cols[c].scalar) continue;
+                row_ends[c].resize((size_t)job.rows);
+                if (rc == 0 && job.rows > 0) rc = gpu::CopyDeviceToHost(row_ends[c].data(), ends[c].p, job.rows * 4, device);
+            }
+        });
+        if (rc != 0) throw std::runtime_error("splitting the echoed attachment on the device failed");
+        if (job.err != 0) {
+            throw std::runtime_error("the echoed attachment does not split (code " + std::to_string(job.err) + ", offset " +
+                                     std::to_string(job.first_bad) + ")");
+        }
+        py::list out;
+        for (size_t c = 0; c < cols.size(); ++c) {
+            out.append(py::make_tuple(py::bytes(values[c]), cols[c].scalar ? py::object(py::none()) : py::cast(row_ends[c]),
+                                      cols[c].absent));
+        }
+        return py::make_tuple(out, job.others);
+    }
+
+private:
+    // Builds the message block and the records block, echoes them and runs
+    // `then` on the response (without the GIL); throws what the build or the
+    // RPC reports.
+    template <typename F>
+    void echo_records(const MessageFields& fields, uint32_t number, const RecordColumns& columns, uint64_t rows,
+                      int device, Controller* cntl, F&& then) {
         example::EchoRequest req;
         example::EchoResponse res;
-        Controller cntl;
         req.set_message("records");
         std::vector<gpu::DeviceMessageField> fs(fields.size());
         for (size_t i = 0; i < fields.size(); ++i) {
@@ -235,27 +327,22 @@ public:
         job.columns = cols.data();
         job.ncols = (uint32_t)cols.size();
         job.rows = rows;
-        std::string got;
-        int rc = 0, copy_rc = 0;
+        int rc = 0;
         {
             py::gil_scoped_release nogil;
-            if (!fs.empty()) rc = gpu::BuildDeviceMessage(fs.data(), (int)fs.size(), &cntl.request_attachment(), device);
-            if (rc == 0) rc = gpu::BuildDeviceRecords(job, &cntl.request_attachment(), device);
+            if (!fs.empty()) rc = gpu::BuildDeviceMessage(fs.data(), (int)fs.size(), &cntl->request_attachment(), device);
+            if (rc == 0) rc = gpu::BuildDeviceRecords(job, &cntl->request_attachment(), device);
             if (rc == 0) {
                 example::EchoService_Stub stub(&_ch);
-                stub.Echo(&cntl, &req, &res, nullptr);
-                if (!cntl.Failed()) copy_rc = gpu::CopyBufToHost(cntl.response_attachment(), &got);
+                stub.Echo(cntl, &req, &res, nullptr);
+                if (!cntl->Failed()) then();
             }
         }
         if (rc != 0) throw std::runtime_error("building the attachment on the device failed (code " + std::to_string(rc) + ")");
-        if (cntl.Failed()) {
-            throw std::runtime_error("[E" + std::to_string(cntl.ErrorCode()) + "] " + cntl.ErrorText());
+        if (cntl->Failed()) {
+            throw std::runtime_error("[E" + std::to_string(cntl->ErrorCode()) + "] " + cntl->ErrorText());
         }
-        if (copy_rc != 0) throw std::runtime_error("copying the echoed attachment to the host failed");
-        return py::bytes(got);
     }
-
-private:
     // Builds the two blocks, echoes them and runs `then` on the response
     // (without the GIL); throws what the build or the RPC reports.
     template <typename F>
@@ -849,6 +936,62 @@ PYBIND11_MODULE(_native, m) {
                               row_ends);
     }, py::arg("number"), py::arg("inner"), py::arg("kind"), py::arg("message"), py::arg("max_elems") = py::none(),
        py::arg("max_rows") = py::none());
+    // The host twin of gpu::DeviceSplitRecords (pb::SplitRecords): the
+    // message's records of field `number`, columns = [(inner, kind, scalar)]
+    // -> (err, rows, others, first_bad, [(count, absent, values bytes,
+    // row_ends list or None)]). max_rows is the capacity of every row_ends
+    // and max_elems a list of the columns' capacities (default: what any
+    // message of this size can hold); values and row_ends are empty unless
+    // err is 0. With ends_as_bytes the row ends come as the memory image of a
+    // uint32 array, not as a list.
+    m.def("pb_split_records", [](uint32_t number, const std::vector<std::tuple<uint32_t, uint32_t, bool>>& columns,
+                                 py::bytes message, py::object max_rows, py::object max_elems, bool ends_as_bytes) {
+        const std::string msg = message;
+        const size_t nc = columns.size();
+        std::vector<uint64_t> caps;
+        if (!max_elems.is_none()) {
+            caps = max_elems.cast<std::vector<uint64_t>>();
+            if (caps.size() != nc) throw std::invalid_argument("max_elems must hold one capacity per column");
+        }
+        pb::SplitRecordsJob job;
+        job.number = number;
+        job.msg = msg.data();
+        job.n = msg.size();
+        job.row_cap = max_rows.is_none() ? msg.size() / 2 : max_rows.cast<uint64_t>();
+        std::vector<pb::SplitRecordsColumn> cols(nc);
+        std::vector<std::vector<uint64_t>> values(nc);
+        std::vector<std::vector<uint32_t>> ends(nc);
+        for (size_t c = 0; c < nc; ++c) {
+            cols[c].inner = std::get<0>(columns[c]);
+            cols[c].kind = std::get<1>(columns[c]);
+            cols[c].scalar = std::get<2>(columns[c]);
+            const size_t eb = cols[c].kind <= pb_rows::kKindFixed64 ? pb_rows::SourceBytes(cols[c].kind) : 1;
+            cols[c].cap = !caps.empty() ? caps[c]
+                          : cols[c].scalar ? job.row_cap
+                                           : msg.size() / (cols[c].kind >= pb_rows::kKindFixed32 ? eb : 1);
+            values[c].resize((size_t)(cols[c].cap * eb + 7) / 8 + 1);
+            ends[c].resize((size_t)job.row_cap + 1);
+            cols[c].values = values[c].data();
+            cols[c].row_ends = cols[c].scalar ? nullptr : ends[c].data();
+        }
+        job.columns = cols.data();
+        job.ncols = (uint32_t)nc;
+        const int err = pb::SplitRecords(&job);
+        py::list out;
+        for (size_t c = 0; c < nc; ++c) {
+            const size_t eb = cols[c].kind <= pb_rows::kKindFixed64 ? pb_rows::SourceBytes(cols[c].kind) : 1;
+            ends[c].resize(err == 0 ? (size_t)job.rows : 0);
+            out.append(py::make_tuple(cols[c].count, cols[c].absent,
+                                      py::bytes(reinterpret_cast<const char*>(values[c].data()),
+                                                err == 0 ? (size_t)cols[c].count * eb : 0),
+                                      cols[c].scalar  ? py::object(py::none())
+                                      : ends_as_bytes ? py::object(py::bytes(reinterpret_cast<const char*>(ends[c].data()),
+                                                                             ends[c].size() * sizeof(uint32_t)))
+                                                      : py::cast(ends[c])));
+        }
+        return py::make_tuple(err, job.rows, job.others, job.first_bad, out);
+    }, py::arg("number"), py::arg("columns"), py::arg("message"), py::arg("max_rows") = py::none(),
+       py::arg("max_elems") = py::none(), py::arg("ends_as_bytes") = false);
     // The host base64 coder (base/util.h over base/base64.h), reading the
     // bytes object in place: the text pb2json gives a bytes field, and what
     // json2pb makes of one (None where base64_decode refuses the text).
@@ -1080,7 +1223,9 @@ PYBIND11_MODULE(_native, m) {
         .def("echo_device_records", &PyChannel::echo_device_records, py::arg("fields"), py::arg("number"),
              py::arg("columns"), py::arg("rows"), py::arg("device") = 0)
         .def("echo_device_rows_split", &PyChannel::echo_device_rows_split, py::arg("fields"), py::arg("rows"),
-             py::arg("device") = 0);
+             py::arg("device") = 0)
+        .def("echo_device_records_split", &PyChannel::echo_device_records_split, py::arg("fields"), py::arg("number"),
+             py::arg("columns"), py::arg("rows"), py::arg("split"), py::arg("device") = 0);
 
     py::class_<PyStreamPress>(m, "StreamPress")
         .def(py::init<const py::dict&>())
@@ -1285,6 +1430,8 @@ PYBIND11_MODULE(_native, m) {
         d["built_row_bytes"] = s.built_row_bytes;
         d["split_row_jobs"] = s.split_row_jobs;
         d["split_rows"] = s.split_rows;
+        d["split_record_jobs"] = s.split_record_jobs;
+        d["split_records"] = s.split_records;
         d["built_record_jobs"] = s.built_record_jobs;
         d["built_records"] = s.built_records;
         d["built_record_bytes"] = s.built_record_bytes;

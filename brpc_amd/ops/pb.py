@@ -315,6 +315,81 @@ def pb_split_rows(message, number, kind_name, inner=None, max_elems=None, max_ro
     return values[:count], row_ends[:rows]
 
 
+RECORDS_SPLIT_ERRORS = dict(SPLIT_ERRORS)
+RECORDS_SPLIT_ERRORS[2] = "refused (field number, columns, a duplicate inner, a scalar bytes column or size)"
+RECORDS_SPLIT_ERRORS[5] = "more records or elements than max_rows / max_elems"
+RECORDS_SPLIT_ERRORS[6] = ("well-formed, but a record holds a field that is no column (or a column twice, or "
+                           "unpacked): use the host parser")
+
+
+def pb_split_records(message, number, columns, max_rows=None, max_elems=None):
+    """The inverse of ``pb_build_records`` (``gpu::DeviceSplitRecords``):
+    every occurrence of field ``number`` in ``message`` (a uint8 device
+    tensor) is a record; other top-level fields are skipped.
+
+    columns: [(inner, kind_name, scalar)] with distinct ``inner`` numbers (at
+    most 8). A record's fields may come in any order. A ragged column absent
+    from a record is a row of no element; a scalar absent from one reads as 0.
+
+    Returns ``[(values, row_ends_or_None)]`` per column, trimmed, in the
+    dtypes ``pb_split_rows`` uses: a ragged column's values and its int32
+    ``row_ends``, a scalar column's one element per record and None.
+    ``pb_build_records(number, ...)`` of the result gives canonical builder
+    output back byte for byte.
+
+    max_rows sizes every ``row_ends`` and the scalar columns, max_elems (one
+    number, or one per column) the ragged values; without them they hold what
+    any message of this size can (``n // 2`` records; the device keeps a table
+    of 8 bytes per record and column, which for a message of several MB with
+    many columns no longer fits one arena block: such a call is refused and
+    needs ``max_rows``). The splitter runs on its own stream: the
+    caller's current stream is synchronized first, as in ``pb_split_rows``."""
+    if not columns:
+        raise ValueError("no columns")
+    require_gpu_tensor(message, "message")
+    if message.dtype != torch.uint8 or message.dim() != 1:
+        raise TypeError("message must be a 1-D uint8 tensor")
+    message = message.contiguous()
+    dev = message.device
+    n = message.numel()
+    if n > native.gpu.device_split_max_bytes():
+        raise ValueError("pb_split_records: a message of %d bytes is above device_split_max_bytes()" % n)
+    row_cap = n // 2 if max_rows is None else int(max_rows)
+    if max_elems is not None and not isinstance(max_elems, (list, tuple)):
+        max_elems = [max_elems] * len(columns)
+    if max_elems is not None and len(max_elems) != len(columns):
+        raise ValueError("max_elems must hold one capacity per column")
+    outs, table = [], []
+    for c, (inner, kind_name, scalar) in enumerate(columns):
+        if kind_name not in _ROW_KINDS:
+            raise ValueError("column %d: unknown kind %r (one of %s)" % (c, kind_name, ", ".join(_ROW_KINDS)))
+        kind, dtypes = _ROW_KINDS[kind_name]
+        dtype = dtypes[0] if dtypes else torch.uint8
+        eb = torch.empty(0, dtype=dtype).element_size()
+        if scalar:
+            cap = row_cap
+        else:
+            cap = n // (eb if kind >= 8 else 1) if max_elems is None else int(max_elems[c])
+        values = torch.empty(max(cap, 1), dtype=dtype, device=dev)
+        row_ends = None if scalar else torch.empty(max(row_cap, 1), dtype=torch.int32, device=dev)
+        outs.append((values, row_ends))
+        table.append((int(inner), kind, bool(scalar), values.data_ptr(), cap,
+                      0 if scalar else row_ends.data_ptr()))
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (rows, _, err, first_bad, counts), = native.gpu.device_split_records(
+            [(int(number), table, message.data_ptr() if n else 0, n, row_cap)], dev.index or 0)
+    if err in (1, 6):
+        raise ValueError("pb_split_records: %s (offset %d)" % (RECORDS_SPLIT_ERRORS[err], first_bad))
+    if err == 5:
+        raise ValueError("pb_split_records: %s (%d records, elements per column: %s)"
+                         % (RECORDS_SPLIT_ERRORS[5], rows, ", ".join(str(c[0]) for c in counts)))
+    if err:
+        raise ValueError("pb_split_records: " + RECORDS_SPLIT_ERRORS.get(err, "code %d" % err))
+    return [(values[:count], None if row_ends is None else row_ends[:rows])
+            for (values, row_ends), (count, _) in zip(outs, counts)]
+
+
 def pb_scan_host(msg, max_fields=16):
     """Pure-python reference of one message's scan (tests)."""
     out, p = [], 0
