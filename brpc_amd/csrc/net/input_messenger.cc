@@ -98,6 +98,7 @@ void InputMessenger::OnNewMessages(Socket* m) {
     int num_queued = 0;
     bool read_eof = false;
     bool failed = false;
+    uint32_t prepaid = 0;  // references of m taken and not yet handed to a message
     while (!read_eof && !failed) {
         size_t once = (size_t)(m->_avg_msg_size * 16);
         if (once < kMinOnceRead) once = kMinOnceRead;
@@ -116,6 +117,7 @@ void InputMessenger::OnNewMessages(Socket* m) {
                 break;
             }
         }
+        int64_t ncut = 0;  // messages cut from this read
         for (;;) {
             size_t index = 0;
             ParseResult pr = messenger->CutInputMessage(m, &index, read_eof);
@@ -140,9 +142,13 @@ void InputMessenger::OnNewMessages(Socket* m) {
             msg->_process = h.process;
             msg->_arg = h.arg;
             msg->_received_us = monotonic_us();
-            m->AddRef();
+            if (prepaid == 0) {
+                m->AddRefs(kPrepaidRefs);
+                prepaid = kPrepaidRefs;
+            }
+            --prepaid;
             msg->_socket.reset(m);
-            m->AddInMessage();
+            ++ncut;
             if (h.verify && !m->_server_verified.load(std::memory_order_acquire)) {
                 if (!h.verify(msg)) {
                     m->SetFailed(ERPCAUTH, "fail to authenticate %s", m->remote_side().to_string().c_str());
@@ -158,12 +164,15 @@ void InputMessenger::OnNewMessages(Socket* m) {
             }
             last = msg;
         }
+        if (ncut) m->AddInMessages(ncut);
         // update average message size estimate
         if (nr > 0) {
             const int64_t avg = m->_avg_msg_size;
             m->_avg_msg_size = avg == 0 ? nr : (avg * 7 + nr) / 8;
         }
     }
+    // every exit of the loop comes here: give back what no message took
+    m->DereferenceMany(prepaid);
     if (num_queued) fiber::flush();
     if (last) QueueOrProcessMessage(last, true);
     if (read_eof) m->SetFailed(EEOF, "got EOF of fd=%d", m->fd());

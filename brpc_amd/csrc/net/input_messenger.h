@@ -27,6 +27,10 @@ public:
     int AddNonProtocolHandler(const InputMessageHandler& h);
     // Socket callback (on_edge_triggered_events).
     static void OnNewMessages(Socket* m);
+    // OnNewMessages takes the socket references of the messages it cuts this
+    // many at a time: one add per chunk on the line that every worker's
+    // Address and Dereference fight for, instead of one per message.
+    static constexpr uint32_t kPrepaidRefs = 16;
     // Create a socket whose reads are handled by this messenger.
     int Create(const SocketOptions& options, SocketId* id);
     size_t handler_count() const { return _handlers.size(); }

@@ -59,13 +59,38 @@ static void finish_write_request(Socket::WriteRequest* r, int fd) {
 
 static Socket::WriteRequest* const UNCONNECTED = (Socket::WriteRequest*)(intptr_t)-1;
 
+// The ids that SetFailed() must end are kept in shards, each with a lock and
+// a line of its own: with one lock, every call on a shared connection took
+// it. A thread always uses the same shard.
+static const int kIdWaitShards = Socket::kIdWaitShards;
+struct MRPC_CACHELINE_ALIGNED IdWaitShard {
+    std::mutex mu;
+    std::vector<fiber::CallId> ids;
+    size_t last_compact = 0;
+};
+
+static inline uint32_t this_thread_id_wait_shard() {
+    static std::atomic<uint32_t> next_thread{0};
+    static thread_local const uint32_t shard = next_thread.fetch_add(1, std::memory_order_relaxed) % kIdWaitShards;
+    return shard;
+}
+
 struct Socket::SharedPart {
     std::mutex mu;
     std::vector<SocketId> pool;  // free pooled sub-sockets
-    std::vector<fiber::CallId> id_wait_list;
-    size_t last_compact = 0;
     std::vector<std::function<void()>> failure_callbacks;
+    IdWaitShard id_wait[kIdWaitShards];
 };
+
+size_t Socket::id_wait_count() const {
+    std::shared_ptr<SharedPart> sp = _shared;
+    size_t n = 0;
+    for (int i = 0; sp && i < kIdWaitShards; ++i) {
+        std::lock_guard<std::mutex> g(sp->id_wait[i].mu);
+        n += sp->id_wait[i].ids.size();
+    }
+    return n;
+}
 
 void Socket::AddFailureCallback(std::function<void()> cb) {
     std::shared_ptr<SharedPart> sp = _shared;
@@ -93,6 +118,12 @@ static SocketVars& socket_vars() {
     return *v;
 }
 
+// A counter with one writer at a time: no locked add. The role's hand-over
+// (_nevent for the reader, _write_head for the writer) orders the writers.
+static inline void single_writer_add(std::atomic<int64_t>& c, int64_t n) {
+    c.store(c.load(std::memory_order_relaxed) + n, std::memory_order_relaxed);
+}
+
 static inline uint64_t make_vref(uint32_t ver, uint32_t nref) { return ((uint64_t)ver << 32) | nref; }
 static inline uint32_t vref_ver(uint64_t v) { return (uint32_t)(v >> 32); }
 static inline int32_t vref_nref(uint64_t v) { return (int32_t)(uint32_t)v; }
@@ -118,26 +149,80 @@ Socket::Socket()
     : _versioned_ref(0),
       _this_id(INVALID_SOCKET_ID),
       _fd(-1),
+      _plane_rank(kPlaneUnknown),
       _user(nullptr),
       _on_edge_triggered_events(nullptr),
-      _health_check_interval_s(-1),
-      _connect_lazily(false),
-      _nevent(0),
+      _main_socket_id(INVALID_SOCKET_ID),
       _write_head(nullptr),
       _unwritten_bytes(0),
-      _epollout_butex(fiber::butex_create()),
+      _nevent(0),
       _last_active_us(0),
+      _health_check_interval_s(-1),
+      _connect_lazily(false),
+      _epollout_butex(fiber::butex_create()),
       _error_code(0),
       _auth_error(0),
       _auth_state(0),
-      _plane_rank(kPlaneUnknown),
       _dev_hello_butex(fiber::butex_create()),
       _auth_butex(fiber::butex_create()),
-      _main_socket_id(INVALID_SOCKET_ID),
       _recycle_flag(false),
       _hc_started(false) {}
 
 Socket::~Socket() {}
+
+// No field of one group shares a cache line with a field of another: each
+// group starts on a line of its own and the next group starts on a later one.
+void Socket::CheckLayout() {
+#define MRPC_SOCKET_LINE(f) (offsetof(Socket, f) / MRPC_CACHELINE)
+#define MRPC_SOCKET_LAST_LINE(f) ((offsetof(Socket, f) + sizeof(Socket::f) - 1) / MRPC_CACHELINE)
+    static_assert(alignof(Socket) >= MRPC_CACHELINE, "Socket must be allocated on a cache line boundary");
+    // (a) _versioned_ref alone
+    static_assert(offsetof(Socket, _versioned_ref) % MRPC_CACHELINE == 0, "");
+    static_assert(MRPC_SOCKET_LINE(_this_id) > MRPC_SOCKET_LAST_LINE(_versioned_ref), "(a) | (b)");
+    // (b) identity and mode: first _this_id, last _local_side
+    static_assert(offsetof(Socket, _this_id) % MRPC_CACHELINE == 0, "");
+    static_assert(MRPC_SOCKET_LINE(_fd) >= MRPC_SOCKET_LINE(_this_id) &&
+                      MRPC_SOCKET_LAST_LINE(_remote_side) <= MRPC_SOCKET_LAST_LINE(_local_side) &&
+                      MRPC_SOCKET_LAST_LINE(_user) <= MRPC_SOCKET_LAST_LINE(_local_side) &&
+                      MRPC_SOCKET_LAST_LINE(_on_edge_triggered_events) <= MRPC_SOCKET_LAST_LINE(_local_side) &&
+                      MRPC_SOCKET_LAST_LINE(_conn) <= MRPC_SOCKET_LAST_LINE(_local_side) &&
+                      MRPC_SOCKET_LAST_LINE(_ssl_state) <= MRPC_SOCKET_LAST_LINE(_local_side) &&
+                      MRPC_SOCKET_LAST_LINE(_rdma_state) <= MRPC_SOCKET_LAST_LINE(_local_side) &&
+                      MRPC_SOCKET_LAST_LINE(_rdma_ep_raw) <= MRPC_SOCKET_LAST_LINE(_local_side) &&
+                      MRPC_SOCKET_LAST_LINE(_main_socket_id) <= MRPC_SOCKET_LAST_LINE(_local_side),
+                  "(b) lies between _this_id and _local_side");
+    static_assert(MRPC_SOCKET_LINE(_write_head) > MRPC_SOCKET_LAST_LINE(_local_side), "(b) | (c)");
+    // (c) the producers: first _write_head, last out_messages
+    static_assert(offsetof(Socket, _write_head) % MRPC_CACHELINE == 0, "");
+    static_assert(MRPC_SOCKET_LINE(_unwritten_bytes) == MRPC_SOCKET_LINE(_write_head) &&
+                      MRPC_SOCKET_LINE(out_messages) == MRPC_SOCKET_LINE(_write_head),
+                  "(c) is one line");
+    static_assert(MRPC_SOCKET_LINE(_nevent) > MRPC_SOCKET_LAST_LINE(out_messages), "(c) | (d)");
+    // (d) dispatcher and reader: first _nevent, last read_calls
+    static_assert(offsetof(Socket, _nevent) % MRPC_CACHELINE == 0, "");
+    static_assert(MRPC_SOCKET_LINE(_read_buf) >= MRPC_SOCKET_LINE(_nevent) &&
+                      MRPC_SOCKET_LINE(_preferred_index) >= MRPC_SOCKET_LINE(_nevent) &&
+                      MRPC_SOCKET_LAST_LINE(_read_buf) <= MRPC_SOCKET_LAST_LINE(read_calls) &&
+                      MRPC_SOCKET_LAST_LINE(_avg_msg_size) <= MRPC_SOCKET_LAST_LINE(read_calls) &&
+                      MRPC_SOCKET_LAST_LINE(_last_active_us) <= MRPC_SOCKET_LAST_LINE(read_calls) &&
+                      MRPC_SOCKET_LAST_LINE(in_bytes) <= MRPC_SOCKET_LAST_LINE(read_calls) &&
+                      MRPC_SOCKET_LAST_LINE(in_messages) <= MRPC_SOCKET_LAST_LINE(read_calls),
+                  "(d) lies between _nevent and read_calls");
+    static_assert(MRPC_SOCKET_LINE(out_bytes) > MRPC_SOCKET_LAST_LINE(read_calls), "(d) | (e)");
+    // (e) the writer: out_bytes, write_calls, write_eagains on one line
+    static_assert(offsetof(Socket, out_bytes) % MRPC_CACHELINE == 0, "");
+    static_assert(MRPC_SOCKET_LINE(write_calls) == MRPC_SOCKET_LINE(out_bytes) &&
+                      MRPC_SOCKET_LINE(write_eagains) == MRPC_SOCKET_LINE(out_bytes),
+                  "(e) is one line");
+    // (f) the rest starts at ninflight_health_check
+    static_assert(MRPC_SOCKET_LINE(ninflight_health_check) > MRPC_SOCKET_LAST_LINE(write_eagains), "(e) | (f)");
+    static_assert(MRPC_SOCKET_LINE(_health_check_interval_s) >= MRPC_SOCKET_LINE(ninflight_health_check) &&
+                      MRPC_SOCKET_LINE(_error_code) >= MRPC_SOCKET_LINE(ninflight_health_check) &&
+                      MRPC_SOCKET_LINE(_epollout_butex) >= MRPC_SOCKET_LINE(ninflight_health_check),
+                  "(f) follows (e)");
+#undef MRPC_SOCKET_LINE
+#undef MRPC_SOCKET_LAST_LINE
+}
 
 int64_t Socket::nsocket() { return g_nsocket.load(std::memory_order_relaxed); }
 
@@ -297,6 +382,29 @@ int Socket::Dereference() {
     return -1;
 }
 
+int Socket::DereferenceMany(uint32_t n) {
+    if (n == 0) return 0;
+    const SocketId id = _this_id;
+    const uint64_t vref = _versioned_ref.fetch_sub(n, std::memory_order_release);
+    const int32_t nref = vref_nref(vref);
+    if (nref > (int32_t)n) return 0;
+    if (nref == (int32_t)n) {
+        const uint32_t ver = vref_ver(vref);
+        if (ver & 1) {
+            uint64_t expected = vref - n;
+            if (_versioned_ref.compare_exchange_strong(expected, make_vref(ver + 1, 0), std::memory_order_acquire)) {
+                OnRecycle();
+                return_resource<Socket>(sid_slot(id));
+                return 1;
+            }
+            return 0;
+        }
+        LOG(FATAL) << "Socket " << id << " dereferenced to 0 without SetFailed";
+    }
+    LOG(FATAL) << "Over dereferenced socket " << id;
+    return -1;
+}
+
 bool Socket::Failed() const {
     return vref_ver(_versioned_ref.load(std::memory_order_acquire)) != sid_ver(_this_id);
 }
@@ -356,8 +464,18 @@ int Socket::SetFailed(int error_code, const char* fmt, ...) {
     std::vector<std::function<void()>> cbs;
     {
         std::lock_guard<std::mutex> g(_shared->mu);
-        ids.swap(_shared->id_wait_list);
         cbs.swap(_shared->failure_callbacks);
+    }
+    // a Write() that registers its id from now on sees Failed() under the
+    // shard's lock and ends the id itself
+    for (IdWaitShard& sh : _shared->id_wait) {
+        std::vector<fiber::CallId> part;
+        {
+            std::lock_guard<std::mutex> g(sh.mu);
+            part.swap(sh.ids);
+            sh.last_compact = 0;
+        }
+        ids.insert(ids.end(), part.begin(), part.end());
     }
     for (fiber::CallId cid : ids) fiber::call_id_error(cid, error_code, _error_text);
     for (auto& cb : cbs) cb();
@@ -449,9 +567,9 @@ void Socket::StartInputEvent(SocketId id, uint32_t events) {
     }
 }
 
-void Socket::AddInMessage() {
-    in_messages.fetch_add(1, std::memory_order_relaxed);
-    socket_vars().in_messages << 1;
+void Socket::AddInMessages(int64_t n) {
+    single_writer_add(in_messages, n);
+    socket_vars().in_messages << n;
 }
 
 void* Socket::ProcessEvent(void* arg) {
@@ -471,13 +589,13 @@ ssize_t Socket::DoRead(size_t size_hint) {
         errno = EBADF;
         return -1;
     }
-    read_calls.fetch_add(1, std::memory_order_relaxed);
+    single_writer_add(read_calls, 1);
     socket_vars().read_calls << 1;
     if (_rdma_state.load(std::memory_order_acquire) != RDMA_OFF) return RdmaRead(fd, size_hint);
     if (_ssl_state.load(std::memory_order_acquire) != SSL_OFF) return SslRead(fd, size_hint);
     ssize_t n = _read_buf.append_from_fd(fd, size_hint);
     if (n > 0) {
-        in_bytes.fetch_add(n, std::memory_order_relaxed);
+        single_writer_add(in_bytes, n);
         _last_active_us.store(monotonic_us(), std::memory_order_relaxed);
     }
     return n;
@@ -494,7 +612,7 @@ ssize_t Socket::RdmaRead(int fd, size_t size_hint) {
         // Server side, first bytes: an RDMA hello or a plain TCP client.
         const ssize_t n = _read_buf.append_from_fd(fd, size_hint);
         if (n <= 0) return n;
-        in_bytes.fetch_add(n, std::memory_order_relaxed);
+        single_writer_add(in_bytes, n);
         _last_active_us.store(monotonic_us(), std::memory_order_relaxed);
         std::shared_ptr<rdma::Endpoint> ep;
         std::string err;
@@ -528,7 +646,7 @@ ssize_t Socket::RdmaRead(int fd, size_t size_hint) {
     rdma::Endpoint* ep = rdma_endpoint();
     const ssize_t n = ep ? ep->ReadInto(&_read_buf) : -1;
     if (n > 0) {
-        in_bytes.fetch_add(n, std::memory_order_relaxed);
+        single_writer_add(in_bytes, n);
         _last_active_us.store(monotonic_us(), std::memory_order_relaxed);
         return n;
     }
@@ -583,7 +701,7 @@ ssize_t Socket::SslRead(int fd, size_t size_hint) {
         BufPortal raw;
         const ssize_t n = raw.append_from_fd(fd, size_hint);
         if (n <= 0) return n;
-        in_bytes.fetch_add(n, std::memory_order_relaxed);
+        single_writer_add(in_bytes, n);
         _last_active_us.store(monotonic_us(), std::memory_order_relaxed);
         if (_ssl_state.load(std::memory_order_acquire) == SSL_UNKNOWN) {
             char head[2];
@@ -656,6 +774,8 @@ bool Socket::FightDeviceHello(int64_t timeout_us) {
 }
 
 void Socket::DeviceHelloAnswered() {
+    // every response comes here: once answered, only read the shared line
+    if (_dev_hello.load(std::memory_order_acquire) == 2) return;
     if (_dev_hello.exchange(2, std::memory_order_acq_rel) == 2) return;
     _dev_hello_butex->fetch_add(1, std::memory_order_release);
     fiber::butex_wake_all(_dev_hello_butex);
@@ -781,7 +901,8 @@ bool Socket::IsWriteComplete(WriteRequest* old_head, bool singular_node, WriteRe
         desired = old_head;
         return_when_no_more = false;
     }
-    if (_write_head.compare_exchange_strong(new_head, desired, std::memory_order_acquire)) {
+    // acq_rel: giving up the write role publishes this writer's counters
+    if (_write_head.compare_exchange_strong(new_head, desired, std::memory_order_acq_rel, std::memory_order_acquire)) {
         if (new_tail) *new_tail = old_head;
         return return_when_no_more;
     }
@@ -821,25 +942,37 @@ int Socket::Write(Buf* data, const WriteOptions* options) {
         if (opt.auth_winner) ResetAuthentication();  // the next writer sends the credentials
         return -1;
     }
+    if (opt.id_wait != fiber::INVALID_CALL_ID) {
+        IdWaitShard& sh = _shared->id_wait[this_thread_id_wait_shard()];
+        std::unique_lock<std::mutex> lk(sh.mu);
+        // SetFailed() bumps the version before it drains the shards: an id
+        // pushed after the drain would wait for its timeout, so look again
+        if (Failed()) {
+            lk.unlock();
+            const int saved_ec = _error_code.load(std::memory_order_relaxed);
+            const int ec = saved_ec ? saved_ec : EFAILEDSOCKET;
+            fiber::call_id_error(opt.id_wait, ec, error_text());
+            errno = ec;
+            if (opt.auth_winner) SetAuthentication(ec);
+            return -1;
+        }
+        auto& v = sh.ids;
+        v.push_back(opt.id_wait);
+        if (v.size() > 256 && v.size() > 2 * sh.last_compact) {
+            size_t j = 0;
+            for (size_t i = 0; i < v.size(); ++i) {
+                if (fiber::call_id_exists(v[i])) v[j++] = v[i];
+            }
+            v.resize(j);
+            sh.last_compact = j;
+        }
+    }
     WriteRequest* req = get_object<WriteRequest>();
     req->data.swap(*data);
     req->next = UNCONNECTED;
     req->id_wait = opt.id_wait;
     req->socket = this;
     req->shutdown_after = opt.shutdown_write_after;
-    if (opt.id_wait != fiber::INVALID_CALL_ID) {
-        std::lock_guard<std::mutex> g(_shared->mu);
-        auto& v = _shared->id_wait_list;
-        v.push_back(opt.id_wait);
-        if (v.size() > 256 && v.size() > 2 * _shared->last_compact) {
-            size_t j = 0;
-            for (size_t i = 0; i < v.size(); ++i) {
-                if (fiber::call_id_exists(v[i])) v[j++] = v[i];
-            }
-            v.resize(j);
-            _shared->last_compact = j;
-        }
-    }
     if (opt.pipelined_count > 0) {
         // the queue order must equal the wire order: enqueue the entry and
         // the write under one lock (StartWrite's exchange fixes the order)
@@ -884,7 +1017,8 @@ int Socket::StartWrite(WriteRequest* req, const WriteOptions& opt) {
     _unwritten_bytes.fetch_add((int64_t)req->data.size(), std::memory_order_relaxed);
     out_messages.fetch_add(1, std::memory_order_relaxed);
     socket_vars().out_messages << 1;
-    WriteRequest* const prev_head = _write_head.exchange(req, std::memory_order_release);
+    // acq_rel: taking the write role (prev_head == nullptr) sees the last writer's counters
+    WriteRequest* const prev_head = _write_head.exchange(req, std::memory_order_acq_rel);
     if (prev_head != nullptr) {
         // Someone is writing; it will pick up this request.
         __atomic_store_n(&req->next, prev_head, __ATOMIC_RELEASE);  // read by the writer's IsWriteComplete
@@ -921,7 +1055,7 @@ int Socket::StartWrite(WriteRequest* req, const WriteOptions& opt) {
             }
         } else {
             _unwritten_bytes.fetch_sub(nw, std::memory_order_relaxed);
-            out_bytes.fetch_add(nw, std::memory_order_relaxed);
+            single_writer_add(out_bytes, nw);
         }
         if (IsWriteComplete(req, true, nullptr)) {
             finish_write_request(req, this->fd());
@@ -939,9 +1073,9 @@ int Socket::StartWrite(WriteRequest* req, const WriteOptions& opt) {
 }
 
 void Socket::CountWriteCall(ssize_t rc) {
-    write_calls.fetch_add(1, std::memory_order_relaxed);
+    single_writer_add(write_calls, 1);
     socket_vars().write_calls << 1;
-    if (rc < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) write_eagains.fetch_add(1, std::memory_order_relaxed);
+    if (rc < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) single_writer_add(write_eagains, 1);
 }
 
 ssize_t Socket::DoWrite(WriteRequest* req) {
@@ -955,7 +1089,7 @@ ssize_t Socket::DoWrite(WriteRequest* req) {
     }
     ssize_t nw = WriteList(fd, list, n);
     CountWriteCall(nw);
-    if (nw > 0) out_bytes.fetch_add(nw, std::memory_order_relaxed);
+    if (nw > 0) single_writer_add(out_bytes, nw);
     return nw;
 }
 

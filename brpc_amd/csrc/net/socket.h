@@ -29,6 +29,7 @@
 
 #include "base/buf.h"
 #include "base/endpoint.h"
+#include "base/macros.h"
 #include "fiber/call_id.h"
 #include "fiber/fiber.h"
 #include "net/ssl.h"
@@ -180,16 +181,11 @@ public:
     // read side
     ssize_t DoRead(size_t size_hint);
     bool MoreReadEvents(int* progress);
-    BufPortal _read_buf;
-    int _preferred_index = -1;          // protocol index that parsed the last message
     // Protocol private per-connection state (http parser, h2 context, ...).
     ParsingContext* parsing_context() const { return _parsing_context.load(std::memory_order_acquire); }
     void reset_parsing_context(ParsingContext* ctx);
     // Install ctx if none is set yet; false (ctx untouched) if another won.
     bool InstallParsingContext(ParsingContext* ctx);
-    std::atomic<ParsingContext*> _parsing_context{nullptr};
-    int64_t _avg_msg_size = 0;
-    std::atomic<bool> _server_verified{false};  // server-side authentication done
 
     // Connection pool (client side)
     int GetPooledSocket(SocketUniquePtr* out);
@@ -243,15 +239,15 @@ public:
     // Health-check / revive
     int Revive(int new_fd);
     int health_check_interval() const { return _health_check_interval_s; }
-    int64_t ninflight_health_check = 0;
 
-    // stats
-    std::atomic<int64_t> in_bytes{0}, out_bytes{0}, in_messages{0}, out_messages{0};
-    // System calls (or transport calls) of the write and the read path, EAGAIN
-    // results included; write_eagains is the EAGAIN share of write_calls.
-    // out_messages / write_calls is how many messages one call carries.
-    std::atomic<int64_t> write_calls{0}, read_calls{0}, write_eagains{0};
-    void AddInMessage();  // a message was cut from _read_buf (InputMessenger)
+    // n messages were cut from _read_buf (InputMessenger, once per batch)
+    void AddInMessages(int64_t n);
+    // The call ids that SetFailed() must end are kept in this many shards; a
+    // writing thread always uses the same one.
+    static const int kIdWaitShards = 8;
+    // Ids registered at the moment, over all shards (finished ones included
+    // until a shard compacts itself).
+    size_t id_wait_count() const;
     std::string description() const;
 
     static int64_t nsocket();
@@ -261,6 +257,10 @@ public:
     ~Socket();
     void AddRef() { _versioned_ref.fetch_add(1, std::memory_order_relaxed); }
     int Dereference();
+    // n references in one step. A reader that cuts many messages prepays a
+    // chunk, hands one to each message and gives the unused rest back.
+    void AddRefs(uint32_t n) { _versioned_ref.fetch_add(n, std::memory_order_relaxed); }
+    int DereferenceMany(uint32_t n);
 
     struct WriteRequest;
 
@@ -282,21 +282,79 @@ private:
     static void* HealthCheckThread(void* arg);
     void StartHealthCheck();
 
-    std::atomic<uint64_t> _versioned_ref;
-    SocketId _this_id;
+    // TLS / RDMA states
+    enum { SSL_OFF = 0, SSL_UNKNOWN = 1, SSL_ON = 2 };
+    enum { RDMA_OFF = 0, RDMA_UNKNOWN = 1, RDMA_ON = 2 };
+    ssize_t SslRead(int fd, size_t size_hint);
+    ssize_t WriteList(int fd, Buf** list, size_t n);
+    ssize_t RdmaRead(int fd, size_t size_hint);
+    void InstallRdmaEndpoint(std::shared_ptr<rdma::Endpoint> ep);
+    static void CheckLayout();  // the static_asserts on the groups below
+
+    // Fields are grouped by who writes them, each group on cache lines of
+    // its own: with one connection every worker works on the same Socket,
+    // and a line that one role writes is lost by every role that shares it.
+    // A counter with one writer at a time (the read role is held through
+    // _nevent, the write role through _write_head, and both hand-overs
+    // order memory) is a relaxed load plus store, not a locked add.
+
+    // (a) the reference count: every Address/Dereference writes it
+    MRPC_CACHELINE_ALIGNED std::atomic<uint64_t> _versioned_ref;
+
+    // (b) identity and mode: set by Create/connect/handshake, then only read
+    MRPC_CACHELINE_ALIGNED SocketId _this_id;
     std::atomic<int> _fd;
-    EndPoint _remote_side;
-    EndPoint _local_side;
+    std::atomic<int> _ssl_state{SSL_OFF};
+    std::atomic<int> _rdma_state{RDMA_OFF};
+    std::atomic<int> _plane_rank;
     void* _user;
     void (*_on_edge_triggered_events)(Socket*);
+    std::atomic<rdma::Endpoint*> _rdma_ep_raw{nullptr};
+    SocketId _main_socket_id;  // pooled connections: the main socket keeps a free list of sub sockets
     std::shared_ptr<SocketConnection> _conn;
+    std::atomic<int> _dev_hello{0};  // 0 not started, 1 in flight, 2 answered
+public:
+    std::atomic<bool> _server_verified{false};  // server-side authentication done
+    std::atomic<ParsingContext*> _parsing_context{nullptr};
+private:
+    struct SharedPart;
+    std::shared_ptr<SharedPart> _shared;
+    EndPoint _remote_side;
+    EndPoint _local_side;
+
+    // (c) the producers' line: every Write() pushes here
+    MRPC_CACHELINE_ALIGNED std::atomic<WriteRequest*> _write_head;
+    std::atomic<int64_t> _unwritten_bytes;
+public:
+    // counted as a message is queued, on the line its producer owns then
+    std::atomic<int64_t> out_messages{0};
+
+    // (d) the dispatcher and the one fiber that holds the read role
+private:
+    MRPC_CACHELINE_ALIGNED std::atomic<int> _nevent;
+public:
+    int _preferred_index = -1;  // protocol index that parsed the last message
+    BufPortal _read_buf;
+    int64_t _avg_msg_size = 0;
+private:
+    std::atomic<int64_t> _last_active_us;
+public:
+    std::atomic<int64_t> in_bytes{0}, in_messages{0};
+    // System calls (or transport calls) of the read and the write path, EAGAIN
+    // results included; write_eagains is the EAGAIN share of write_calls.
+    // out_messages / write_calls is how many messages one call carries.
+    std::atomic<int64_t> read_calls{0};
+
+    // (e) the one fiber (or caller) that holds the write role
+    MRPC_CACHELINE_ALIGNED std::atomic<int64_t> out_bytes{0};
+    std::atomic<int64_t> write_calls{0}, write_eagains{0};
+
+    // (f) the rest: failure, health check, authentication, negotiation, TLS
+    MRPC_CACHELINE_ALIGNED int64_t ninflight_health_check = 0;
+private:
     int _health_check_interval_s;
     bool _connect_lazily;
-    std::atomic<int> _nevent;
-    std::atomic<WriteRequest*> _write_head;
-    std::atomic<int64_t> _unwritten_bytes;
     std::atomic<int>* _epollout_butex;
-    std::atomic<int64_t> _last_active_us;
     // set after the version bump that marks the socket failed: a reader that
     // sees Failed() before it lands falls back to EFAILEDSOCKET
     std::atomic<int> _error_code;
@@ -305,34 +363,17 @@ private:
     std::shared_ptr<Transport> _transport;
     std::atomic<int> _auth_error;
     std::atomic<int> _auth_state;  // 0 none, 1 fighting, 2 done
-    std::atomic<int> _plane_rank;
-    std::atomic<int> _dev_hello{0};  // 0 not started, 1 in flight, 2 answered
     std::atomic<int>* _dev_hello_butex = nullptr;
     std::atomic<int>* _auth_butex;
-    // pooled connections: the main socket keeps a free list of sub sockets
-    SocketId _main_socket_id;
-    struct SharedPart;
-    std::shared_ptr<SharedPart> _shared;
     std::atomic<bool> _recycle_flag;
     std::mutex _pipeline_mu;
     std::deque<PipelinedInfo> _pipeline_q;
     std::atomic<bool> _hc_started;
-    // TLS
-    enum { SSL_OFF = 0, SSL_UNKNOWN = 1, SSL_ON = 2 };
-    ssize_t SslRead(int fd, size_t size_hint);
-    ssize_t WriteList(int fd, Buf** list, size_t n);
     std::shared_ptr<SslContext> _ssl_ctx;
     std::string _ssl_sni;
     std::shared_ptr<SslSession> _ssl;
-    std::atomic<int> _ssl_state{SSL_OFF};
-    // RDMA
-    enum { RDMA_OFF = 0, RDMA_UNKNOWN = 1, RDMA_ON = 2 };
-    ssize_t RdmaRead(int fd, size_t size_hint);
-    void InstallRdmaEndpoint(std::shared_ptr<rdma::Endpoint> ep);
     int _rdma_mode = 0;
-    std::atomic<int> _rdma_state{RDMA_OFF};
     std::shared_ptr<rdma::Endpoint> _rdma_ep;  // guarded by _mu
-    std::atomic<rdma::Endpoint*> _rdma_ep_raw{nullptr};
 };
 
 // Dump /connections-style info of all live sockets.

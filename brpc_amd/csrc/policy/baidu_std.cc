@@ -68,10 +68,28 @@ ParseResult ParseRpcMessage(Buf* source, Socket* socket, bool, const void*) {
         return MakeParseError(PARSE_ERROR_ABSOLUTELY_WRONG);
     }
     source->pop_front(sizeof(header));
+    // One cut for meta and payload: each Buf cut here takes references of
+    // the read blocks that a worker gives back, on lines both of them write.
     MostCommonMessage* msg = MostCommonMessage::Get();
-    source->cutn(&msg->meta, meta_size);
-    source->cutn(&msg->payload, body_size - meta_size);
+    source->cutn(&msg->payload, body_size);
+    msg->meta_size = meta_size;
     return MakeMessage(msg);
+}
+
+// Parses the RpcMeta at the front of a frame cut by ParseRpcMessage: in place
+// when one block holds it, else through the Buf parser. The frame is left as
+// it is; the caller pops meta_size bytes to get at the payload.
+static bool ParseFrameMeta(RpcMeta* meta, const MostCommonMessage* msg) {
+    const size_t n = msg->meta_size;
+    const Buf& frame = msg->payload;
+    if (n > FLAGS_max_body_size || n > frame.size()) return false;
+    if (n == 0) return meta->ParseFromArray("", 0);
+    if (frame.block_len(0) >= n && IsHostAccessible(frame.ref_at(0).block->kind)) {
+        return meta->ParseFromArray(frame.block_data(0), n);
+    }
+    Buf copy(frame), spanning;
+    copy.cutn(&spanning, n);
+    return ParsePbFromBuf(meta, spanning);
 }
 
 void SerializeRpcRequest(Buf* buf, Controller* cntl, const pb::Message* request) {
@@ -144,8 +162,9 @@ static void SendRpcResponse(int64_t correlation_id, Controller* cntl, pb::Messag
     std::unique_ptr<pb::Message> req_guard(req);
     std::unique_ptr<pb::Message> res_guard(res);
     ConcurrencyRemover remover(method_status, cntl, received_us, server);
-    SocketUniquePtr sock;
-    if (Socket::Address(cntl->_server_socket_id, &sock) != 0) return;  // client gone
+    SocketUniquePtr addressed;
+    Socket* const sock = cntl->ServerSocketForResponse(&addressed);
+    if (!sock) return;  // client gone
     if (cntl->IsCloseConnection()) {
         sock->SetFailed(ECLOSE, "close connection by user");
         return;
@@ -168,7 +187,7 @@ static void SendRpcResponse(int64_t correlation_id, Controller* cntl, pb::Messag
         res_body.clear();
     } else {
         meta.set_compress_type(cntl->response_compress_type());
-        if (!SplitDevicePayload(cntl, /*request=*/false, cntl->response_attachment(), &host_attachment, &meta, sock.get())) {
+        if (!SplitDevicePayload(cntl, /*request=*/false, cntl->response_attachment(), &host_attachment, &meta, sock)) {
             res_body.clear();
             meta.Clear();
             meta.mutable_response()->set_error_code(cntl->ErrorCode());
@@ -210,11 +229,12 @@ void ProcessRpcRequest(InputMessageBase* msg_base) {
     Socket* socket = msg->socket();
     Server* server = const_cast<Server*>(static_cast<const Server*>(msg->arg()));
     RpcMeta meta;
-    if (!ParsePbFromBuf(&meta, msg->meta)) {
+    if (!ParseFrameMeta(&meta, msg)) {
         LOG(WARNING) << "Fail to parse RpcMeta from " << socket->remote_side();
         socket->SetFailed(EREQUEST, "fail to parse RpcMeta");
         return;
     }
+    msg->payload.pop_front(msg->meta_size);
     const RpcRequestMeta& rm = meta.request();
     Controller* cntl = new Controller;
     cntl->_server = server;
@@ -235,7 +255,7 @@ void ProcessRpcRequest(InputMessageBase* msg_base) {
         if (cntl->_span) {
             cntl->_span->remote_side = socket->remote_side();
             cntl->_span->start_parse_real_us = realtime_us();
-            cntl->_span->request_size = (int64_t)(msg->meta.size() + msg->payload.size() + 12);
+            cntl->_span->request_size = (int64_t)(msg->meta_size + msg->payload.size() + 12);
             cntl->_span->log_id = (uint64_t)rm.log_id();
             cntl->_trace_id = cntl->_span->trace_id;
             cntl->_span_id = cntl->_span->span_id;
@@ -331,6 +351,7 @@ void ProcessRpcRequest(InputMessageBase* msg_base) {
     // rejected before the attachment was looked at: the sender's lent HBM
     // blocks must still be given back, or they stay pinned on its side
     if (!device_payload_taken) ReleaseDevicePayload(socket, meta);
+    cntl->_server_socket = std::move(msg->socket_ptr());  // the message's reference stays with the call
     msg->Destroy();
     destroyer.m = nullptr;
     if (!concurrency_added) server = nullptr;  // nothing to remove
@@ -352,7 +373,7 @@ bool VerifyRpcRequest(const InputMessageBase* msg_base) {
     const Authenticator* auth = server->options().auth;
     if (!auth) return true;
     RpcMeta meta;
-    if (!ParsePbFromBuf(&meta, msg->meta)) return false;
+    if (!ParseFrameMeta(&meta, msg)) return false;
     AuthContext ctx;
     return auth->VerifyCredential(meta.authentication_data(), msg->socket()->remote_side(), &ctx) == 0;
 }
@@ -360,11 +381,12 @@ bool VerifyRpcRequest(const InputMessageBase* msg_base) {
 void ProcessRpcResponse(InputMessageBase* msg_base) {
     MostCommonMessage* msg = static_cast<MostCommonMessage*>(msg_base);
     RpcMeta meta;
-    if (!ParsePbFromBuf(&meta, msg->meta)) {
+    if (!ParseFrameMeta(&meta, msg)) {
         LOG(WARNING) << "Fail to parse RpcMeta from " << msg->socket()->remote_side();
         msg->Destroy();
         return;
     }
+    msg->payload.pop_front(msg->meta_size);
     if (meta.has_stream_settings() && !meta.has_correlation_id()) {
         ReleaseDevicePayload(msg->socket(), meta);
         msg->Destroy();

@@ -94,6 +94,7 @@ void ProcessHuluRequest(InputMessageBase* base) {
         r.error_text = "user_message_size is larger than the payload";
     }
     const int64_t corr = meta.correlation_id();
+    r.socket_ref = std::move(msg->socket_ptr());
     msg->Destroy();
     RunPbServerCall(&r, [corr](Controller* cntl, Buf* body, Buf* attachment, Buf* packet) {
         HuluRpcResponseMeta rm;

@@ -76,8 +76,9 @@ void SendPbResponse(ServerCallState* st) {
     std::unique_ptr<pb::Message> req(st->req);
     std::unique_ptr<pb::Message> res(st->res);
     ConcurrencyRemover remover(st->ms, cntl.get(), st->start_us, st->server);
-    SocketUniquePtr sock;
-    if (Socket::Address(cntl->_server_socket_id, &sock) != 0) return;
+    SocketUniquePtr addressed;
+    Socket* const sock = cntl->ServerSocketForResponse(&addressed);
+    if (!sock) return;
     if (cntl->IsCloseConnection()) {
         sock->SetFailed(ECLOSE, "close connection by user");
         return;
@@ -124,6 +125,7 @@ void RunPbServerCall(PbServerRequest* r, PbResponsePacker packer) {
     Controller* cntl = new Controller;
     cntl->_server = server;
     cntl->_server_socket_id = socket->id();
+    cntl->_server_socket = std::move(r->socket_ref);
     cntl->_remote_side = socket->remote_side();
     cntl->_local_side = socket->local_side();
     cntl->_received_us = r->received_us;

@@ -26,6 +26,9 @@ namespace policy {
 struct PbServerRequest {
     Server* server = nullptr;
     Socket* socket = nullptr;
+    // The request message's reference of `socket`, if the protocol hands it
+    // over: it stays with the call and the response is written through it.
+    SocketUniquePtr socket_ref;
     int64_t received_us = 0;
     ProtocolType protocol = PROTOCOL_UNKNOWN;
     // The method, resolved by the protocol (service name+index, full name...).

@@ -94,6 +94,7 @@ void ProcessSofaRequest(InputMessageBase* base) {
     r.body.swap(msg->payload);
     if (meta.has_expected_response_compress_type()) r.response_compress = FromSofa(meta.expected_response_compress_type());
     const uint64_t seq = meta.sequence_id();
+    r.socket_ref = std::move(msg->socket_ptr());
     msg->Destroy();
     RunPbServerCall(&r, [seq](Controller* cntl, Buf* body, Buf*, Buf* packet) {
         SofaRpcMeta rm;

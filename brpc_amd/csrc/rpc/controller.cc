@@ -127,6 +127,7 @@ void Controller::Reset() {
     _server = nullptr;
     _method_status = nullptr;
     _server_socket_id = INVALID_SOCKET_ID;
+    _server_socket.reset();
     _server_correlation_id = 0;
     _close_connection = false;
     _on_end = nullptr;

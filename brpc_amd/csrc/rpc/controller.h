@@ -306,6 +306,17 @@ public:
     Server* _server = nullptr;
     MethodStatus* _method_status = nullptr;
     SocketId _server_socket_id = INVALID_SOCKET_ID;
+    // The reference that the request message held on its connection stays
+    // with the call (released with the controller), so that sending the
+    // response does not address the id again.
+    SocketUniquePtr _server_socket;
+    // The connection to write the response to, or null when it is gone:
+    // _server_socket if the protocol kept it, else `addressed` by id.
+    Socket* ServerSocketForResponse(SocketUniquePtr* addressed) {
+        Socket* s = _server_socket.get();
+        if (s) return s->Failed() ? nullptr : s;
+        return Socket::Address(_server_socket_id, addressed) == 0 ? addressed->get() : nullptr;
+    }
     int64_t _server_correlation_id = 0;
     bool _close_connection = false;
     void* _session_local_data = nullptr;

@@ -7,6 +7,7 @@
 #include <memory>
 #include <string>
 
+#include "base/macros.h"
 #include "rpc/concurrency_limiter.h"
 #include "var/var.h"
 
@@ -32,8 +33,9 @@ public:
     std::string Describe() const;
 
 private:
-    std::atomic<int> _nconcurrency{0};
-    var::LatencyRecorder _latency_rec;
+    // written by every request of the method: on a line of its own
+    MRPC_CACHELINE_ALIGNED std::atomic<int> _nconcurrency{0};
+    MRPC_CACHELINE_ALIGNED var::LatencyRecorder _latency_rec;
     var::Adder<int64_t> _nerror;
     AdaptiveMaxConcurrency _amc;
     std::unique_ptr<ConcurrencyLimiter> _cl;

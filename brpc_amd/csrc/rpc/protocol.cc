@@ -35,6 +35,7 @@ MostCommonMessage* MostCommonMessage::Get() {
     m->_arg = nullptr;
     m->_received_us = 0;
     m->_base_real_us = 0;
+    m->meta_size = 0;
     return m;
 }
 

@@ -67,6 +67,10 @@ class MostCommonMessage : public InputMessageBase {
 public:
     Buf meta;
     Buf payload;
+    // baidu_std cuts a frame as one Buf: `payload` starts with this many
+    // bytes of meta and `meta` stays empty (policy/baidu_std.cc). 0 for the
+    // protocols that cut meta and payload apart.
+    uint32_t meta_size = 0;
     static MostCommonMessage* Get();
     void Destroy() override;
 };

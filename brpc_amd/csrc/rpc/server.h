@@ -173,8 +173,10 @@ private:
     std::unordered_map<std::string, MethodProperty> _methods;  // "svc.Method"
     std::vector<std::pair<std::string, std::string>> _restful;  // prefix -> full method name
     const MethodProperty* _master_mp = nullptr;
-    std::atomic<int> _concurrency{0};
-    std::unique_ptr<ConcurrencyLimiter> _cl;
+    // every request of every connection adds and removes itself here: on a
+    // line of its own, away from what the same requests only read
+    MRPC_CACHELINE_ALIGNED std::atomic<int> _concurrency{0};
+    MRPC_CACHELINE_ALIGNED std::unique_ptr<ConcurrencyLimiter> _cl;
     AdaptiveMaxConcurrency _amc;
     int64_t _start_us = 0;
     std::string _version;

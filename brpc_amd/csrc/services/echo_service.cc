@@ -153,7 +153,7 @@ void EchoServiceImpl::Echo(RpcController* cntl_base, const example::EchoRequest*
                            example::EchoResponse* response, Closure* done) {
     ClosureGuard done_guard(done);
     Controller* cntl = static_cast<Controller*>(cntl_base);
-    _ncalls.fetch_add(1, std::memory_order_relaxed);
+    _ncalls << 1;
     if (request->sleep_us() > 0) fiber::usleep((uint64_t)request->sleep_us());
     if (request->server_fail()) {
         cntl->SetFailed(request->code() ? request->code() : EINTERNAL, "server_fail requested");

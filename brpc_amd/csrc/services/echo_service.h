@@ -6,6 +6,7 @@
 #include <atomic>
 
 #include "mrpc/proto/echo.pb.h"
+#include "var/var.h"
 
 namespace mrpc {
 
@@ -13,7 +14,7 @@ class EchoServiceImpl : public example::EchoService {
 public:
     void Echo(RpcController* controller, const example::EchoRequest* request, example::EchoResponse* response,
               Closure* done) override;
-    int64_t ncalls() const { return _ncalls.load(); }
+    int64_t ncalls() const { return _ncalls.get_value(); }
     int64_t gpu_calls() const { return _gpu_calls.load(); }
     // GPU that serves requests with gpu_process set (-1: none, such
     // requests fail with EREQUEST). The attachment is gathered into HBM by
@@ -22,7 +23,7 @@ public:
     void set_gpu_device(int device) { _gpu_device = device; }
 
 private:
-    std::atomic<int64_t> _ncalls{0};
+    var::Adder<int64_t> _ncalls;  // per-thread cells summed on read: every call counts here
     std::atomic<int64_t> _gpu_calls{0};
     int _gpu_device = -1;
 };
