@@ -26,6 +26,24 @@ a machine without a GPU.
 
   python benchmarks/base64_bw.py [--sizes-ki 4,64,1024,16384,65536] [--runs 3]
   python benchmarks/base64_bw.py --table profiles/base64.txt   # the README table
+
+--only rows measures the rows form instead (gpu::DeviceBase64EncodeRows /
+DeviceBase64DecodeRows: `repeated bytes` <-> a JSON array of base64 strings):
+random bytes in rows of 1, 32 and 1024 bytes and in one row, at 4 KiB, 64 KiB,
+1 MiB and 64 MiB, each way, four routes, the median microseconds of a blocking
+call, three runs:
+
+  a  what a handler had: D2H of bytes and row_ends into pinned memory, the
+     host twin (json::EncodeBase64Rows / DecodeBase64Rows), H2D of the result
+  b  the rows entry, HBM -> HBM
+  c  the flat DeviceBase64Encode / Decode over the same bytes as one buffer
+     (for decode: over the symbols alone, without quotes and commas): the floor
+  d  encode only: one flat job per row in one call, with the host copy of
+     row_ends it needs (D2H, timed) and without the quotes and commas: the
+     device route there was. Left out above --max-flat-jobs rows.
+
+  python benchmarks/base64_bw.py --only rows > profiles/base64_rows.txt
+  python benchmarks/base64_bw.py --only rows --table profiles/base64_rows.txt
 """
 import argparse
 import base64
@@ -117,6 +135,142 @@ def table(path):
             med("e_hbm_dst_plus_1_us"), med("d_data_gb_per_s"), med("d_over_g")))
 
 
+def rows_table(path):
+    """The README table of the rows form from a profile: medians over the runs, and the ranges."""
+    rows = {}
+    for line in open(path):
+        line = line.strip()
+        if not line.startswith('{"run"'):
+            continue
+        r = json.loads(line)
+        if "b_rows_us" in r:
+            rows.setdefault((r["direction"], r["data_bytes"], r["row_bytes"]), []).append(r)
+    print("| direction | data | row | a D2H + twin + H2D | b rows entry | c flat floor | d job per row | a / b | b / c | "
+          "b range |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for (direction, n, width), rs in sorted(rows.items(), key=lambda kv: (kv[0][0] != "encode", kv[0][1], kv[0][2] or 1 << 40)):
+        def med(k):
+            vals = [r[k] for r in rs if r.get(k) is not None]
+            return statistics.median(vals) if vals else None
+        name = "%d KiB" % (n >> 10) if n < 1 << 20 else "%d MiB" % (n >> 20)
+        d = med("d_job_per_row_us")
+        bs = [r["b_rows_us"] for r in rs]
+        print("| %s | %s | %s | %.1f µs | %.1f µs | %.1f µs | %s | %.2f | %.2f | %.1f .. %.1f |" % (
+            direction, name, "one row" if not width else "%d B" % width, med("a_d2h_twin_h2d_us"), med("b_rows_us"),
+            med("c_flat_us"), "-" if d is None else "%.1f µs" % d, med("a_d2h_twin_h2d_us") / med("b_rows_us"),
+            med("b_rows_us") / med("c_flat_us"), min(bs), max(bs)))
+
+
+def rows_main(args):
+    import torch
+    from brpc_amd import native
+    assert torch.cuda.is_available() and native.gpu.device_count() > 0, "this benchmark needs the GPU"
+    dev = torch.device("cuda", 0)
+    g = native.gpu
+    sync = torch.cuda.synchronize
+    sizes = [int(float(x) * 1024) for x in args.sizes_ki.split(",")]
+
+    def pinned(nbytes):
+        return torch.empty(max(nbytes, 1), dtype=torch.uint8).pin_memory()
+
+    def device_bytes(b):
+        return torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()).to(dev)
+
+    for run in range(args.runs):
+        for n in sizes:
+            for width in (1, 32, 1024, 0):
+                iters = iters_for(n, args.iters)
+                data = np.random.default_rng(n + run).integers(0, 256, n, dtype=np.uint8)
+                ends = np.arange(width, n + 1, width, dtype=np.uint32) if width else np.array([n], dtype=np.uint32)
+                rows = len(ends)
+                cap = g.base64_rows_worst_case(n, rows, True)
+                d_data, d_ends = torch.from_numpy(data).to(dev), torch.from_numpy(ends.view(np.int32)).to(dev)
+                d_text = torch.zeros(cap + 16, dtype=torch.uint8, device=dev)
+                p_data, p_ends, p_text = pinned(n), pinned(4 * rows), pinned(cap)
+
+                def enc_before():  # a
+                    p_data[:n].copy_(d_data)
+                    p_ends[:4 * rows].copy_(d_ends.view(torch.uint8))
+                    sync()
+                    got, _ = native.base64_rows_twin(0, p_data.data_ptr(), n, p_text.data_ptr(), cap, p_ends.data_ptr(), rows)
+                    d_text[:got].copy_(p_text[:got])
+                    sync()
+                    return got
+
+                def enc_rows():  # b
+                    return g.device_base64_encode_rows([d_data.data_ptr()], [n], [d_ends.data_ptr()], [rows], True,
+                                                       [d_text.data_ptr()], [cap], 0)[0]
+
+                def enc_flat():  # c
+                    return g.device_base64_encode([d_data.data_ptr()], [n], [d_text.data_ptr()], [cap], 0)[0]
+
+                def enc_per_row():  # d
+                    p_ends[:4 * rows].copy_(d_ends.view(torch.uint8))
+                    sync()
+                    e = p_ends[:4 * rows].numpy().view(np.uint32).astype(np.int64)
+                    starts = np.concatenate(([0], e[:-1]))
+                    lens = e - starts
+                    outs = (starts + 2) // 3 * 4 + 3 * np.arange(rows)  # room for what the rows form would take
+                    return g.device_base64_encode((d_data.data_ptr() + starts).tolist(), lens.tolist(),
+                                                  (d_text.data_ptr() + outs).tolist(), ((lens + 2) // 3 * 4).tolist(), 0)
+
+                want = native.base64_encode_rows(data.tobytes(), ends.tobytes(), True)
+                tlen = len(want)
+                assert enc_before() == tlen and d_text[:tlen].cpu().numpy().tobytes() == want
+                d_text.zero_()
+                assert tuple(enc_rows()[:2]) == (tlen, 0) and d_text[:tlen].cpu().numpy().tobytes() == want
+                row = {"run": run, "direction": "encode", "data_bytes": n, "row_bytes": width, "rows": rows,
+                       "text_bytes": tlen,
+                       "a_d2h_twin_h2d_us": round(timed(enc_before, sync, args.warmup, iters) * 1e6, 1),
+                       "b_rows_us": round(timed(enc_rows, sync, args.warmup, iters) * 1e6, 1),
+                       "c_flat_us": round(timed(enc_flat, sync, args.warmup, iters) * 1e6, 1),
+                       "d_job_per_row_us": None}
+                if rows <= args.max_flat_jobs:
+                    assert all(r[1] == 0 for r in enc_per_row())
+                    row["d_job_per_row_us"] = round(timed(enc_per_row, sync, args.warmup, iters) * 1e6, 1)
+                row["b_data_gb_per_s"] = round(n / row["b_rows_us"] / 1e3, 2)
+                print(json.dumps(row), flush=True)
+
+                # decode: the text just made; the floor decodes as many symbols in one flat buffer
+                d_src = device_bytes(want)
+                flat = device_bytes(base64.b64encode(data.tobytes()))
+                bcap, rcap = g.base64_rows_max_bytes(tlen), g.base64_rows_max_rows(tlen)
+                d_out = torch.zeros(bcap + 16, dtype=torch.uint8, device=dev)
+                d_oends = torch.zeros(rcap + 1, dtype=torch.int32, device=dev)
+                p_src, p_out, p_oends = pinned(tlen), pinned(bcap), pinned(4 * rcap)
+
+                def dec_before():  # a
+                    p_src[:tlen].copy_(d_src)
+                    sync()
+                    got, nrows = native.base64_rows_twin(1, p_src.data_ptr(), tlen, p_out.data_ptr(), bcap,
+                                                         p_oends.data_ptr(), rcap)
+                    d_out[:got].copy_(p_out[:got])
+                    d_oends.view(torch.uint8)[:4 * nrows].copy_(p_oends[:4 * nrows])
+                    sync()
+                    return got, nrows
+
+                def dec_rows():  # b
+                    return g.device_base64_decode_rows([d_src.data_ptr()], [tlen], [d_out.data_ptr()], [bcap],
+                                                       [d_oends.data_ptr()], [rcap], 0)[0]
+
+                def dec_flat():  # c
+                    return g.device_base64_decode([flat.data_ptr()], [flat.numel()], [d_out.data_ptr()], [bcap + 16], 0)[0]
+
+                assert dec_before() == (n, rows) and d_out[:n].cpu().numpy().tobytes() == data.tobytes()
+                d_out.zero_()
+                d_oends.zero_()
+                assert tuple(dec_rows()[:4]) == (n, rows, 1, 0)
+                assert d_out[:n].cpu().numpy().tobytes() == data.tobytes()
+                assert np.array_equal(d_oends[:rows].cpu().numpy().view(np.uint32), ends)
+                row = {"run": run, "direction": "decode", "data_bytes": n, "row_bytes": width, "rows": rows,
+                       "text_bytes": tlen,
+                       "a_d2h_twin_h2d_us": round(timed(dec_before, sync, args.warmup, iters) * 1e6, 1),
+                       "b_rows_us": round(timed(dec_rows, sync, args.warmup, iters) * 1e6, 1),
+                       "c_flat_us": round(timed(dec_flat, sync, args.warmup, iters) * 1e6, 1)}
+                row["b_data_gb_per_s"] = round(n / row["b_rows_us"] / 1e3, 2)
+                print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes-ki", default="4,64,1024,16384,65536")
@@ -125,7 +279,13 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--cpu-only", action="store_true")
     ap.add_argument("--table", metavar="PROFILE")
+    ap.add_argument("--only", choices=["rows"], help="measure the rows form alone")
+    ap.add_argument("--max-flat-jobs", type=int, default=1 << 16, help="rows: most rows route d is run with")
     args = ap.parse_args()
+    if args.only == "rows":
+        if args.sizes_ki == ap.get_default("sizes_ki"):
+            args.sizes_ki = "4,64,1024,65536"
+        return rows_table(args.table) if args.table else rows_main(args)
     if args.table:
         return table(args.table)
     from brpc_amd import native

@@ -10,6 +10,8 @@
 
 #include <cstdint>
 
+#include "base/base64_rows.h"
+
 namespace mrpc {
 namespace gpu {
 
@@ -46,6 +48,73 @@ int DeviceBase64Encode(DeviceBase64Job* jobs, int njobs, int device);
 // size before the padding is known (err 3 otherwise). Launches, wait and
 // return value as above.
 int DeviceBase64Decode(DeviceBase64Job* jobs, int njobs, int device);
+
+// ---- rows: `repeated bytes`, or a bytes column of records, to and from the
+// text of a JSON array of base64 strings, HBM -> HBM. The rules are
+// base/base64_rows.h; json::EncodeBase64Rows / DecodeBase64Rows (json/json.h)
+// are the host twins. (bytes, row_ends) is the pair DeviceSplitRows /
+// DeviceSplitRecords give and DeviceBuildRows / DeviceBuildRecords take.
+//
+// Codes of both entries: 0 done; 1 see each entry, first_bad is set; 2 refused
+// before any launch (a null pointer where something is to be read or written,
+// n above 2^32 - 2 or an output above 2^32 - 1, ranges that overlap, row_ends
+// that is not 4-byte aligned, rows without row_ends); 3 cap or row_cap too
+// small, found on the device, len and rows say what is needed; 4 (decode) the
+// source changed between the passes. With 1, 3 and 4 dst and row_ends are
+// untouched apart from what code 4 had placed before it was found; no store
+// ever goes beyond a capacity. All jobs of a call share the launches, on one
+// pool stream with one fiber-friendly wait; the host reads nothing but the
+// result words, row_ends neither. Each returns -1 only on a device error.
+
+// The text of `rows` rows holding n bytes in all is never longer than this.
+constexpr uint64_t Base64RowsWorstCaseBytes(uint64_t n, uint64_t rows, bool brackets) {
+    return base64_rows::Base64RowsWorstCaseBytes(n, rows, brackets);
+}
+// A text of n bytes never decodes to more bytes, or holds more strings.
+constexpr uint64_t Base64RowsMaxBytes(uint64_t n) { return base64_rows::Base64RowsMaxBytes(n); }
+constexpr uint64_t Base64RowsMaxRows(uint64_t n) { return base64_rows::Base64RowsMaxRows(n); }
+
+// Row r is src[row_ends[r - 1], row_ends[r]) (row_ends[-1] = 0, equal
+// neighbours: an empty row); the output is "b0","b1",...,"b(rows-1)", wrapped
+// in '[' ']' with brackets, no whitespace. rows == 0 writes "[]" or nothing;
+// n == 0 with rows > 0 writes "","",.. . Code 1: row_ends decreases at row
+// first_bad, rises above n, or does not end at n (the lowest such row, found
+// on the device). The table is read once, into a copy the later passes use.
+// The size depends on every row length: cap may be anything from the true
+// size up, Base64RowsWorstCaseBytes always suffices.
+struct DeviceBase64RowsEncodeJob {
+    const void* src = nullptr;       // device, any alignment
+    uint64_t n = 0;                  // at most 2^32 - 2
+    const void* row_ends = nullptr;  // uint32[rows], device, 4-byte aligned
+    uint64_t rows = 0;
+    bool brackets = true;
+    void* dst = nullptr;  // device-writable, any alignment, cap bytes; overlaps neither src nor row_ends
+    uint64_t cap = 0;
+    uint64_t len = 0;        // out: bytes written (code 3: the size needed)
+    uint64_t first_bad = 0;  // out, code 1
+    int err = 0;
+};
+int DeviceBase64EncodeRows(DeviceBase64RowsEncodeJob* jobs, int njobs, int device);
+
+// "b0","b1",... or ["b0","b1",...], JSON whitespace wherever JSON allows it,
+// every body canonical base64 -> the decoded bytes of all strings at dst and
+// row_ends[r], the bytes in strings 0..r. Code 1: the text is not for the
+// device (json::Reader and base64_decode are laxer), first_bad is the offset
+// at which a parser reading from the left cannot go on; len, rows and depth
+// are 0. Code 2 also: dst or row_ends overlapping src or each other. n == 0 is
+// code 0, no rows, nothing written, no launch.
+struct DeviceBase64RowsDecodeJob {
+    const void* src = nullptr;  // device, any alignment
+    uint64_t n = 0;             // at most 2^32 - 2
+    void* dst = nullptr;        // decoded bytes, any alignment
+    uint64_t cap = 0;           // Base64RowsMaxBytes(n) always suffices
+    void* row_ends = nullptr;   // uint32[row_cap], 4-byte aligned
+    uint64_t row_cap = 0;       // Base64RowsMaxRows(n) always suffices
+    uint64_t len = 0, rows = 0, first_bad = 0;  // out
+    uint32_t depth = 0;                         // out: 1 when the text is bracketed
+    int err = 0;
+};
+int DeviceBase64DecodeRows(DeviceBase64RowsDecodeJob* jobs, int njobs, int device);
 
 }  // namespace gpu
 }  // namespace mrpc

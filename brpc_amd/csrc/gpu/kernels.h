@@ -939,6 +939,112 @@ int LaunchBase64Encode(const Base64Job* jobs, int njobs, uint32_t nblocks, hipSt
 int LaunchBase64Decode(const Base64Job* jobs, int njobs, uint32_t nblocks, JsonNumberResult* res_dev,
                        JsonNumberResult* res_out, hipStream_t s);
 
+// Base64 rows in device memory (gpu/base64_kernels.hip; the rules are
+// base/base64_rows.h, the code json::EncodeBase64Rows / DecodeBase64Rows run
+// on the host): (bytes, row_ends) <-> the text "b0","b1",.. or ["b0",..] of a
+// JSON array of base64 strings. All jobs of a call share the launches, ordered
+// by the stream alone; the job table is copied to device memory first, and
+// nothing is written to a dst before the job's verdict (ok[job]) is known.
+// Workgroups of 256 lanes; no workgroup waits for another.
+//   encode  rows    a lane per row reads row_ends once and keeps what it read
+//                   in ends[] (the later passes read only that copy, so a table
+//                   that changes under the call cannot move a store): a
+//                   decrease, an end above n or a last end other than n goes
+//                   into bad[job] (atomicMin); the symbols of the row,
+//                   (len + 2) / 3 * 4, are summed over the block of 256 rows
+//                   by a workgroup scan: the symbols in front of the row
+//                   within its block into rowoff[], the block's sum into
+//                   prefix[]
+//           prefix  LaunchPbRunPrefix over the row blocks
+//           verdict a lane per job: len, err 1 / 3, ok[job], the brackets
+//           punct   a lane per row writes its two quotes and its comma at
+//                   symbols before the row + 3 * row (+ 1 with brackets), so
+//                   empty rows cost the place pass nothing
+//           place   a workgroup per kBase64RowsEncodeChunkBytes of source,
+//                   staged in LDS with two bytes beyond. The rows that meet
+//                   the chunk are found by two lower-bound searches of ends[].
+//                   A 3-byte group is counted from its row's start and belongs
+//                   to the chunk that holds its first byte. Up to
+//                   kBase64RowsSegmentRows rows: per row a lane takes four
+//                   groups of the row's part of the chunk, the symbols go
+//                   through an LDS image and leave with 16-byte stores
+//                   (wg::copy_out_shifted). More rows: a lane takes the groups
+//                   that start in its 12 bytes, finds its row by a lower-bound
+//                   search (again at every row end it crosses, so a run of
+//                   empty rows is skipped in one search) and stores four bytes
+//                   per group. Every store is compared with cap.
+//   decode  a chunk is kBase64RowsDecodeChunkBytes of text, a lane 16 bytes.
+//           The in-string mask is the prefix-xor of all quotes (no escape can
+//           hide one: a backslash is refused). What crosses a chunk's edge is
+//           one of nine states: outside a string after token kind k
+//           (json_string_rows::Kind, 5 states) or inside at body offset mod 4
+//           (4 states); the byte before a chunk is read from the text.
+//           scan    a workgroup per chunk: a bit per byte for symbols, '=',
+//                   quotes and the tokens outside; the quote parity in front of
+//                   each lane by ballot, the last quote in front of it by a
+//                   max-scan (its distance gives the body offset). For the two
+//                   ways the mask can start: decoded bytes (a group belongs to
+//                   the lane and chunk of its first symbol and reads up to 3
+//                   bytes on, never past n), closing quotes, the lowest byte
+//                   that breaks a local rule, first token, first ']', exit.
+//                   The lanes in front of the chunk's first quote also compute
+//                   size and lowest fault for each of the four phases
+//           carry   a workgroup per job composes the chunks' maps over the nine
+//                   states (4 bits per image in a 64-bit word), picks every
+//                   chunk's entry, judges its first token against the true
+//                   predecessor, writes the two size tables and the job's
+//                   lowest offender, first ']', depth and final state
+//           prefix  LaunchPbRunPrefix over both tables at once
+//           verdict a lane per job: a ']' at depth 0, the end rule, cap and
+//                   row_cap (err 3), ok[job], the result words
+//           place   a workgroup per chunk with its entry: groups decoded with
+//                   Decode4 into an LDS image that leaves with 16-byte stores;
+//                   the lane that holds the k-th closing quote writes
+//                   row_ends[k]. Sizes that differ from the scan's: err 4
+// res is device-writable pinned host memory; everything else device memory.
+constexpr uint32_t kBase64RowsEncodeChunkBytes = kBase64ChunkBytes;
+constexpr uint32_t kBase64RowsDecodeChunkBytes = 4096;
+constexpr uint32_t kBase64RowsBlockRows = 256;
+constexpr uint32_t kBase64RowsSegmentRows = 8;
+// decode, per chunk: for the entries outside / inside size, closing quotes,
+// lowest offender, first token, first ']', exit; then size and lowest offender
+// of the leading in-string run for the four phases; then the chosen entry
+constexpr uint32_t kBase64RowsInfoWords = 24;
+constexpr uint32_t kBase64RowsStateWords = 4;  // per job: lowest offender, final state, depth, first ']'
+struct Base64RowsJob {
+    const uint8_t* src;
+    uint8_t* dst;
+    const uint32_t* row_ends;  // encode: the table to read. decode: the row ends to write
+    uint64_t cap;
+    uint32_t n, rows;          // decode: rows is row_cap
+    uint32_t brackets;         // encode
+    uint32_t first_chunk, nchunks;  // encode: ceil(n / encode chunk); decode: ceil(n / decode chunk); may be 0
+    uint32_t first_rblock;          // encode: ceil(rows / kBase64RowsBlockRows) row blocks
+    uint32_t first_row;             // encode: the job's rows in ends[] and rowoff[]
+    uint32_t pad;
+};
+struct Base64RowsResult {
+    uint64_t len;  // bytes written (with err 3: the size needed)
+    uint32_t rows, first_bad, depth;
+    int32_t err;  // 0, 1, 3, 4
+};
+struct Base64RowsTables {
+    const Base64RowsJob* jobs = nullptr;  // pinned host
+    int njobs = 0;
+    Base64RowsJob* jobs_dev = nullptr;
+    uint32_t nchunks = 0, nrblocks = 0, nrows = 0;  // of all jobs
+    uint32_t* prefix = nullptr;  // encode: nrblocks + 1. decode: 2 * (nchunks + 1)
+    uint32_t* ends = nullptr;    // encode: nrows
+    uint32_t* rowoff = nullptr;  // encode: nrows
+    uint32_t* info = nullptr;    // decode: nchunks * kBase64RowsInfoWords
+    uint32_t* bad = nullptr;     // njobs
+    int32_t* ok = nullptr;       // njobs
+    uint32_t* state = nullptr;   // decode: njobs * kBase64RowsStateWords
+    Base64RowsResult* res = nullptr;  // njobs, pinned host
+};
+int LaunchBase64EncodeRows(const Base64RowsTables& t, hipStream_t s);
+int LaunchBase64DecodeRows(const Base64RowsTables& t, hipStream_t s);
+
 // JSON string bodies and UTF-8 in device memory (gpu/json_string_kernels.hip;
 // the rules are base/json_string.h, the code json::EscapeStringBody,
 // UnescapeStringBody and Utf8FirstBad run on the host). A job's n bytes are

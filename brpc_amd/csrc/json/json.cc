@@ -10,12 +10,14 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "base/base64_rows.h"
 #include "base/decimal_to_double.h"
 #include "base/json_string.h"
 #include "base/json_string_rows.h"
 #include "base/number_print.h"
 #include "base/number_text.h"
 #include "base/shortest_double.h"
+#include "base/util.h"
 
 namespace mrpc {
 namespace json {
@@ -207,6 +209,45 @@ int UnescapeStringRows(const char* text, size_t n, StringRows* out) {
     const int rc = json_string_rows::WalkStringRows(
         [&](uint64_t k) { return (uint8_t)text[k]; }, n, [&](uint64_t from, uint64_t len) { out->bytes.append(text + from, len); },
         [&](const char* p, uint32_t len) { out->bytes.append(p, len); },
+        [&] { out->row_ends.push_back((uint32_t)out->bytes.size()); }, &out->depth, &out->first_bad);
+    if (rc != 0) {
+        out->bytes.clear();
+        out->row_ends.clear();
+        out->depth = 0;
+    }
+    return rc;
+}
+
+bool EncodeBase64Rows(const char* bytes, const uint32_t* row_ends, size_t rows, bool brackets, std::string* out) {
+    for (size_t r = 1; r < rows; ++r) {
+        if (row_ends[r] < row_ends[r - 1]) return false;
+    }
+    size_t at = out->size();
+    out->resize(at + base64_rows::Base64RowsWorstCaseBytes(rows ? row_ends[rows - 1] : 0, rows, brackets));
+    char* o = &(*out)[0];
+    if (brackets) o[at++] = '[';
+    uint32_t from = 0;
+    for (size_t r = 0; r < rows; ++r) {
+        if (r) o[at++] = ',';
+        o[at++] = '"';
+        base64_encode_to(bytes + from, row_ends[r] - from, o + at);
+        at += base64::Base64EncodedBytes(row_ends[r] - from);
+        o[at++] = '"';
+        from = row_ends[r];
+    }
+    if (brackets) o[at++] = ']';
+    out->resize(at);
+    return true;
+}
+
+int DecodeBase64Rows(const char* text, size_t n, StringRows* out) {
+    out->bytes.clear();
+    out->row_ends.clear();
+    out->depth = 0;
+    out->first_bad = 0;
+    out->bytes.reserve(base64_rows::Base64RowsMaxBytes(n));
+    const int rc = base64_rows::WalkBase64Rows(
+        [&](uint64_t k) { return (uint8_t)text[k]; }, n, [&](const char* p, uint32_t len) { out->bytes.append(p, len); },
         [&] { out->row_ends.push_back((uint32_t)out->bytes.size()); }, &out->depth, &out->first_bad);
     if (rc != 0) {
         out->bytes.clear();

@@ -276,6 +276,17 @@ struct StringRows {
     uint64_t first_bad = 0;
 };
 int UnescapeStringRows(const char* text, size_t n, StringRows* out);
+// The host twins of gpu::DeviceBase64EncodeRows / DeviceBase64DecodeRows
+// (gpu/base64_offload.h); the rules are base/base64_rows.h for both.
+// "b0","b1",... appended to *out, wrapped in '[' ']' with brackets: row r, cut
+// from bytes as above, as its '='-padded base64. False, with nothing appended,
+// when row_ends decreases.
+bool EncodeBase64Rows(const char* bytes, const uint32_t* row_ends, size_t rows, bool brackets, std::string* out);
+// The inverse: the text of an array of base64 strings, depth 0 or 1 as above,
+// bodies canonical base64 only. 0: done, filled like UnescapeStringRows. 1:
+// not decided here (json::Reader and base64_decode are laxer): first_bad is
+// set, everything else empty and 0. One sequential walk.
+int DecodeBase64Rows(const char* text, size_t n, StringRows* out);
 // The first offset at which no well-formed UTF-8 sequence starts on the walk
 // from 0 (what Python reports as UnicodeDecodeError.start), n when the text
 // is well-formed.

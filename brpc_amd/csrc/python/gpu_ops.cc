@@ -690,6 +690,75 @@ void bind_gpu_ops(py::module_& g) {
         return out;
     }, py::arg("srcs"), py::arg("ns"), py::arg("dsts"), py::arg("caps"), py::arg("device") = 0);
     g.def("base64_chunk_bytes", [] { return gpu::kBase64ChunkBytes; });
+    // Base64 rows in device memory (gpu::DeviceBase64EncodeRows /
+    // DeviceBase64DecodeRows): (bytes, uint32 row ends) <-> the text of a JSON
+    // array of base64 strings. Encode returns [(len, err, first_bad)], decode
+    // [(len, rows, depth, err, first_bad)]; err 3: len and rows say what is
+    // needed.
+    g.def("device_base64_encode_rows", [](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& ns,
+                                          const std::vector<uintptr_t>& row_ends, const std::vector<uint64_t>& rows,
+                                          bool brackets, const std::vector<uintptr_t>& dsts,
+                                          const std::vector<uint64_t>& caps, int device) {
+        if (srcs.size() != ns.size() || dsts.size() != ns.size() || caps.size() != ns.size() ||
+            row_ends.size() != ns.size() || rows.size() != ns.size())
+            throw std::invalid_argument("size mismatch");
+        std::vector<gpu::DeviceBase64RowsEncodeJob> jobs(ns.size());
+        for (size_t i = 0; i < ns.size(); ++i) {
+            jobs[i].src = (const void*)srcs[i];
+            jobs[i].n = ns[i];
+            jobs[i].row_ends = (const void*)row_ends[i];
+            jobs[i].rows = rows[i];
+            jobs[i].brackets = brackets;
+            jobs[i].dst = (void*)dsts[i];
+            jobs[i].cap = caps[i];
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceBase64EncodeRows(jobs.data(), (int)jobs.size(), device);
+        }
+        check(rc, "device_base64_encode_rows");
+        py::list out;
+        for (const gpu::DeviceBase64RowsEncodeJob& j : jobs) out.append(py::make_tuple(j.len, j.err, j.first_bad));
+        return out;
+    }, py::arg("srcs"), py::arg("ns"), py::arg("row_ends"), py::arg("rows"), py::arg("brackets"), py::arg("dsts"),
+       py::arg("caps"), py::arg("device") = 0);
+    g.def("device_base64_decode_rows", [](const std::vector<uintptr_t>& srcs, const std::vector<uint64_t>& ns,
+                                          const std::vector<uintptr_t>& dsts, const std::vector<uint64_t>& caps,
+                                          const std::vector<uintptr_t>& ends, const std::vector<uint64_t>& row_caps,
+                                          int device) {
+        if (srcs.size() != ns.size() || dsts.size() != ns.size() || caps.size() != ns.size() || ends.size() != ns.size() ||
+            row_caps.size() != ns.size())
+            throw std::invalid_argument("size mismatch");
+        std::vector<gpu::DeviceBase64RowsDecodeJob> jobs(ns.size());
+        for (size_t i = 0; i < ns.size(); ++i) {
+            jobs[i].src = (const void*)srcs[i];
+            jobs[i].n = ns[i];
+            jobs[i].dst = (void*)dsts[i];
+            jobs[i].cap = caps[i];
+            jobs[i].row_ends = (void*)ends[i];
+            jobs[i].row_cap = row_caps[i];
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DeviceBase64DecodeRows(jobs.data(), (int)jobs.size(), device);
+        }
+        check(rc, "device_base64_decode_rows");
+        py::list out;
+        for (const gpu::DeviceBase64RowsDecodeJob& j : jobs)
+            out.append(py::make_tuple(j.len, j.rows, j.depth, j.err, j.first_bad));
+        return out;
+    }, py::arg("srcs"), py::arg("ns"), py::arg("dsts"), py::arg("caps"), py::arg("ends"), py::arg("row_caps"),
+       py::arg("device") = 0);
+    g.def("base64_rows_worst_case", [](uint64_t n, uint64_t rows, bool brackets) {
+        return gpu::Base64RowsWorstCaseBytes(n, rows, brackets);
+    }, py::arg("n"), py::arg("rows"), py::arg("brackets") = true);
+    g.def("base64_rows_max_bytes", [](uint64_t n) { return gpu::Base64RowsMaxBytes(n); });
+    g.def("base64_rows_max_rows", [](uint64_t n) { return gpu::Base64RowsMaxRows(n); });
+    g.def("base64_rows_encode_chunk_bytes", [] { return gpu::kBase64RowsEncodeChunkBytes; });
+    g.def("base64_rows_decode_chunk_bytes", [] { return gpu::kBase64RowsDecodeChunkBytes; });
+    g.def("base64_rows_segment_rows", [] { return gpu::kBase64RowsSegmentRows; });
     // JSON string bodies in device memory, all jobs sharing the launches
     // (gpu/json_string_offload.h): escape returns [(len, err, first_bad)]
     // (row_ends[i] 0: one string, else `rows[i]` uint32 in device memory),

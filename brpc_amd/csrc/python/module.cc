@@ -1067,6 +1067,34 @@ PYBIND11_MODULE(_native, m) {
         for (uint32_t e : rows.row_ends) ends.append(e);
         return py::make_tuple(py::bytes(rows.bytes), ends, rows.depth);
     });
+    // The host twins of the device's base64 rows entries (json/json.h over
+    // base/base64_rows.h). base64_encode_rows: row_ends as uint32 little-endian
+    // bytes ascending to len(data) -> "b0","b1",..., in '[' ']' with brackets.
+    // base64_decode_rows: (bytes, row_ends list, depth), or (None, first_bad)
+    // where the twin leaves the text to json::Reader and base64_decode.
+    m.def("base64_encode_rows", [](py::bytes data, py::bytes row_ends, bool brackets) {
+        char* p = nullptr;
+        Py_ssize_t n = 0;
+        if (PyBytes_AsStringAndSize(data.ptr(), &p, &n) != 0) throw py::error_already_set();
+        const std::string ends = row_ends;
+        if (ends.size() % 4 != 0) throw py::value_error("row_ends: a multiple of 4 bytes");
+        std::vector<uint32_t> e(ends.size() / 4);
+        if (!e.empty()) memcpy(e.data(), ends.data(), ends.size());
+        if ((e.empty() ? 0u : e.back()) != (uint64_t)n) throw py::value_error("row_ends does not end at len(data)");
+        std::string out;
+        if (!json::EncodeBase64Rows(p, e.data(), e.size(), brackets, &out)) throw py::value_error("row_ends decreases");
+        return py::bytes(out);
+    }, py::arg("data"), py::arg("row_ends"), py::arg("brackets") = true);
+    m.def("base64_decode_rows", [](py::bytes text) -> py::tuple {
+        char* p = nullptr;
+        Py_ssize_t n = 0;
+        if (PyBytes_AsStringAndSize(text.ptr(), &p, &n) != 0) throw py::error_already_set();
+        json::StringRows rows;
+        if (json::DecodeBase64Rows(p, (size_t)n, &rows) != 0) return py::make_tuple(py::none(), rows.first_bad);
+        py::list ends;
+        for (uint32_t e : rows.row_ends) ends.append(e);
+        return py::make_tuple(py::bytes(rows.bytes), ends, rows.depth);
+    });
     // What json::Reader makes of the text of an array of strings (a text whose
     // first byte that is no whitespace is not '[' is bracketed first): the list
     // of bytes, or None when it refuses or an element is no string.
@@ -1128,6 +1156,30 @@ PYBIND11_MODULE(_native, m) {
         return (int64_t)out.size();
     }, py::arg("op"), py::arg("src"), py::arg("n"), py::arg("dst"), py::arg("cap"), py::arg("row_ends") = 0,
        py::arg("rows") = 0);
+    // The base64 rows twins between raw buffers (pinned host memory of a
+    // benchmark), the GIL released: op 0 encode (row_ends: `rows` uint32, text
+    // at dst), op 1 decode (bytes at dst, row_ends receives up to `rows`
+    // uint32). Returns (bytes written at dst, rows), (-1, 0) when the twin
+    // refuses or an output is too small.
+    m.def("base64_rows_twin", [](int op, uintptr_t src, size_t n, uintptr_t dst, size_t cap, uintptr_t row_ends,
+                                 size_t rows, bool brackets) -> std::pair<int64_t, uint64_t> {
+        py::gil_scoped_release nogil;
+        const char* s = reinterpret_cast<const char*>(src);
+        if (op == 0) {
+            std::string out;
+            if (!json::EncodeBase64Rows(s, reinterpret_cast<const uint32_t*>(row_ends), rows, brackets, &out) ||
+                out.size() > cap)
+                return {-1, 0};
+            memcpy(reinterpret_cast<char*>(dst), out.data(), out.size());
+            return {(int64_t)out.size(), rows};
+        }
+        json::StringRows got;
+        if (json::DecodeBase64Rows(s, n, &got) != 0 || got.bytes.size() > cap || got.row_ends.size() > rows) return {-1, 0};
+        memcpy(reinterpret_cast<char*>(dst), got.bytes.data(), got.bytes.size());
+        memcpy(reinterpret_cast<char*>(row_ends), got.row_ends.data(), got.row_ends.size() * 4);
+        return {(int64_t)got.bytes.size(), got.row_ends.size()};
+    }, py::arg("op"), py::arg("src"), py::arg("n"), py::arg("dst"), py::arg("cap"), py::arg("row_ends"), py::arg("rows"),
+       py::arg("brackets") = true);
     // What json::Reader makes of '"' + body + '"': the bytes, or None where it refuses.
     m.def("json_reader_string", [](py::bytes body) -> py::object {
         std::string text = "\"";

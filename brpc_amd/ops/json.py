@@ -608,6 +608,112 @@ def json_unescape_string_rows(text, max_bytes=None, max_rows=None):
     return out[:length], ends[:rows]
 
 
+def base64_encode_rows(data, row_ends=None, brackets=True):
+    """uint8 device tensor of bytes and an int32 / int64 device tensor
+    ``row_ends`` (the bytes in rows 0..r, as ``pb_split_rows(..., "bytes")`` and
+    a bytes column of ``pb_split_records`` return them) -> uint8 device tensor
+    of the text ``["b0","b1",...,"bk"]``, every row as its ``=``-padded base64:
+    a ``repeated bytes`` field, or a bytes column, as http+json carries it.
+    ``brackets=False`` leaves the ``[`` ``]`` away. A 2-D ``data`` with
+    ``row_ends=None`` means equal rows. The bytes never leave HBM
+    (``gpu::DeviceBase64EncodeRows``); int64 ends are narrowed on the device.
+
+    ValueError names the first row whose end lies below its predecessor's or
+    above ``len(data)``, or the last row when it does not end at ``len(data)``.
+
+    The coder runs on a pool stream, not on torch's: the caller's current
+    stream is synchronized before the call, and the text is complete when
+    this returns."""
+    require_gpu_tensor(data, "data")
+    if data.dtype != torch.uint8:
+        raise TypeError("data must be uint8")
+    dev = data.device
+    if row_ends is None:
+        if data.dim() != 2:
+            raise ValueError("base64_encode_rows: row_ends is needed unless data is 2-D")
+        rows, width = data.shape
+        ends = torch.arange(1, rows + 1, dtype=torch.int64, device=dev).mul_(width).to(torch.int32)
+    else:
+        require_gpu_tensor(row_ends, "row_ends")
+        if row_ends.dtype not in (torch.int32, torch.int64):
+            raise TypeError("row_ends must be int32 or int64")
+        ends = row_ends.contiguous().view(-1).to(torch.int32)
+        rows = ends.numel()
+    t = _flat_bytes(data, "data")
+    n = t.numel()
+    if rows == 0 and n:
+        raise ValueError("base64_encode_rows: bytes without rows")
+    cap = native.gpu.base64_rows_worst_case(n, rows, brackets)
+    if cap >= 1 << 32:
+        raise ValueError("base64_encode_rows: the worst case must be below 4 GiB")
+    out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+    if cap == 0:
+        return out[:0]
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (length, err, first_bad), = native.gpu.device_base64_encode_rows(
+            [t.data_ptr() if n else 0], [n], [ends.data_ptr() if rows else 0], [rows], brackets, [out.data_ptr()], [cap],
+            dev.index or 0)
+    if err == 1:
+        raise ValueError("base64_encode_rows: row_ends is not ascending to len(data) (row %d)" % first_bad)
+    if err:
+        raise ValueError("base64_encode_rows: " + _STRING_ERRORS.get(err, "code %d" % err))
+    return out[:length]
+
+
+def base64_decode_rows(text, max_bytes=None, max_rows=None):
+    """uint8 device tensor holding the text of an array of base64 strings,
+    ``"b0","b1",...,"bk"`` or ``["b0","b1",...,"bk"]`` with JSON whitespace
+    wherever JSON allows it -> ``(bytes, row_ends)``: a uint8 device tensor of
+    the decoded rows one after the other and an int32 one with ``row_ends[r]``
+    the bytes in rows 0..r. The inverse of ``base64_encode_rows``, and what
+    ``pb_build_rows(number, bytes, row_ends, "bytes")`` and a bytes column of
+    ``pb_build_records`` take. The text never leaves HBM
+    (``gpu::DeviceBase64DecodeRows``); empty text, whitespace and ``[ ]`` give
+    no rows.
+
+    The outputs are sized for the worst case unless ``max_bytes`` /
+    ``max_rows`` bound them (ValueError naming what the text takes when it
+    holds more). A text the device leaves to the host (anything but canonical
+    base64 inside the strings: a line break, an escape, URL-safe symbols; or
+    anything that is not an array of strings) is fetched and given to the
+    reader (``native.json_reader_string_array``) and then, row by row, to
+    ``native.base64_decode``: their result is returned as device tensors, or
+    ValueError raised naming the offset the device reported.
+
+    The coder runs on a pool stream, not on torch's: the caller's current
+    stream is synchronized before the call, and both tensors are complete
+    when this returns."""
+    t = _flat_bytes(text, "text")
+    dev = t.device
+    n = t.numel()
+    worst_bytes = native.gpu.base64_rows_max_bytes(n)
+    worst_rows = native.gpu.base64_rows_max_rows(n)
+    cap = worst_bytes if max_bytes is None else min(int(max_bytes), worst_bytes)
+    row_cap = worst_rows if max_rows is None else min(int(max_rows), worst_rows)
+    out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+    ends = torch.empty(max(row_cap, 1), dtype=torch.int32, device=dev)
+    if n == 0:
+        return out[:0], ends[:0]
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (length, rows, _, err, first_bad), = native.gpu.device_base64_decode_rows(
+            [t.data_ptr()], [n], [out.data_ptr() if cap else 0], [cap], [ends.data_ptr() if row_cap else 0], [row_cap],
+            dev.index or 0)
+    if err == 1:
+        strings = native.json_reader_string_array(bytes(t.cpu().numpy()))
+        lax = None if strings is None else [native.base64_decode(s) for s in strings]
+        if lax is None or any(r is None for r in lax):
+            raise ValueError("base64_decode_rows: not an array of base64 strings (offset %d)" % first_bad)
+        return _string_rows_tensors(lax, dev)
+    if err == 3:
+        raise ValueError("base64_decode_rows: max_bytes=%d, max_rows=%d is too small (the text takes %d bytes in %d "
+                         "rows)" % (cap, row_cap, length, rows))
+    if err:
+        raise ValueError("base64_decode_rows: " + _STRING_ERRORS.get(err, "code %d" % err))
+    return out[:length], ends[:rows]
+
+
 def utf8_validate(data):
     """uint8 device tensor -> None when it is well-formed UTF-8 (the rule a
     protobuf ``string`` and a JSON text carry), else the first offset at which
