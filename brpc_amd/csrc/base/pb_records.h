@@ -27,7 +27,16 @@
 //   varint(number << 3 | 2) varint(s) F0 F1 .. Fk-1
 // with s the bytes of its fields; a record whose fields are all omitted is
 // tag 0x00. A job of one packed (or one bytes) column is the pb_rows output
-// for the same number / inner / kind byte for byte.
+// for the same number / inner / kind byte for byte, and the device builds it
+// as one: gpu::DeviceBuildRows runs a one-column record job.
+//
+// The headerless column: inner == 0, kind bytes, ragged, the job's only
+// column. Its payload follows the record header with no field header in
+// between (HasFieldHeader), so record r is varint(number << 3 | 2) varint(p)
+// P: pb_rows' `repeated bytes`. Only the header rules below know it.
+// ColumnOk, FieldsOk, WorstCaseBytes and SplitColumnsOk refuse inner == 0, so
+// no caller of pb::SerializeRecords, DeviceBuildRecords or a splitter can
+// pass one; the rows entry point does, behind pb_rows::WorstCaseBytes.
 #pragma once
 
 #include <cstddef>
@@ -73,16 +82,23 @@ MRPC_ROWS_FN bool HasField(uint32_t kind, bool scalar, uint64_t p) {
     return scalar || kind == pb_rows::kKindBytes || p > 0;
 }
 
-// Bytes in front of the field's payload of p bytes; 0 when it is omitted.
+// Whether a tag (and, for a ragged column, a length) stands in front of the
+// field's payload: not when the field is omitted, and never for the
+// headerless column.
+MRPC_ROWS_FN bool HasFieldHeader(uint32_t inner, uint32_t kind, bool scalar, uint64_t p) {
+    return inner != 0 && HasField(kind, scalar, p);
+}
+
+// Bytes in front of the field's payload of p bytes; 0 when there is none.
 MRPC_ROWS_FN uint32_t FieldHeaderBytes(uint32_t inner, uint32_t kind, bool scalar, uint64_t p) {
-    if (!HasField(kind, scalar, p)) return 0;
+    if (!HasFieldHeader(inner, kind, scalar, p)) return 0;
     const uint32_t tag = pb_rows::VarintLen((uint64_t)inner << 3);
     return scalar ? tag : tag + pb_rows::VarintLen(p);
 }
 
 // Writes them (at most kMaxFieldHeaderBytes); returns FieldHeaderBytes().
 MRPC_ROWS_FN uint32_t PutFieldHeader(uint8_t* o, uint32_t inner, uint32_t kind, bool scalar, uint64_t p) {
-    if (!HasField(kind, scalar, p)) return 0;
+    if (!HasFieldHeader(inner, kind, scalar, p)) return 0;
     const uint32_t n = pb_rows::PutVarint(o, ((uint64_t)inner << 3) | WireType(kind, scalar));
     return scalar ? n : n + pb_rows::PutVarint(o + n, p);
 }

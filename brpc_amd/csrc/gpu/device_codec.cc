@@ -467,126 +467,6 @@ bool rows_job_ok(const DeviceRowsJob& j) {
     return j.count == 0 || (j.src && ((uintptr_t)j.src & (pb_rows::SourceBytes(j.kind) - 1)) == 0);
 }
 
-}  // namespace
-
-uint64_t DeviceRowsWorstCaseBytes(const DeviceRowsJob& job) {
-    return pb_rows::WorstCaseBytes(job.number, job.inner, job.kind, job.count, job.rows);
-}
-
-// The jobs go to a pool stream of their own rather than into the cross-RPC
-// codec batch: a rows job brings scratch sized by its rows and groups (three
-// words per row), which the batch's recycled tables do not hold, and its
-// seven launches share nothing with the small codec jobs of other RPCs.
-int DeviceBuildRows(DeviceRowsJob* jobs, int n, int device) {
-    if (n <= 0) return 0;
-    if (!jobs || device < 0) return -1;
-    std::vector<int> live;  // the jobs that go to the device, in order
-    uint64_t nchunks = 0, nrblocks = 0, ngroups = 0, nrows = 0;
-    for (int i = 0; i < n; ++i) {
-        DeviceRowsJob& j = jobs[i];
-        j.len = 0;
-        j.first_bad = 0xFFFFFFFFu;
-        j.err = 0;
-        if (!rows_job_ok(j)) {
-            j.err = 2;
-            g_build_err.fetch_add(1, std::memory_order_relaxed);
-            continue;
-        }
-        nchunks += (j.count + kPbRowsChunkElems - 1) / kPbRowsChunkElems;
-        nrblocks += (j.rows + kPbRowsBlockRows - 1) / kPbRowsBlockRows;
-        if (pb_rows::IsVarintKind(j.kind)) ngroups += j.count / kPbRowsGroupElems + 2;
-        nrows += j.rows;
-        live.push_back(i);
-    }
-    if (live.empty()) return 0;
-    // one grid per pass, 32-bit table indices
-    if (nchunks > 0x7FFFFFFFull || nrblocks > 0x7FFFFFFFull || ngroups > 0x7FFFFFFFull || nrows > 0x7FFFFFFFull) {
-        return -1;
-    }
-    const size_t nlive = live.size();
-    PinnedBlock tables(nlive * (sizeof(PbRowsJob) + sizeof(PbRowsResult)));
-    const size_t jobs_bytes = nlive * sizeof(PbRowsJob);  // first: the most aligned
-    const size_t words = (size_t)ngroups + 3 * (size_t)nrows + (size_t)nrblocks + 2 * nlive;
-    HbmBlock scratch(jobs_bytes + words * sizeof(uint32_t), device);
-    if (!tables || !scratch) return -1;
-    PbRowsJob* tj = tables.as<PbRowsJob>();
-    PbRowsResult* tr = reinterpret_cast<PbRowsResult*>(tj + nlive);
-    PbRowsTables t;
-    for (size_t k = 0; k < nlive; ++k) {
-        const DeviceRowsJob& j = jobs[live[k]];
-        PbRowsJob& o = tj[k];
-        o.src = j.src;
-        o.row_ends = j.row_ends;
-        o.dst = static_cast<uint8_t*>(j.dst);
-        o.cap = j.cap;
-        o.count = (uint32_t)j.count;
-        o.rows = (uint32_t)j.rows;
-        o.number = j.number;
-        o.inner = j.inner;
-        o.kind = j.kind;
-        o.first_chunk = t.nchunks;
-        o.nchunks = (uint32_t)((j.count + kPbRowsChunkElems - 1) / kPbRowsChunkElems);
-        o.first_rblock = t.nrblocks;
-        o.first_row = t.nrows;
-        o.first_group = t.ngroups;
-        t.nchunks += o.nchunks;
-        t.nrblocks += (uint32_t)((j.rows + kPbRowsBlockRows - 1) / kPbRowsBlockRows);
-        t.nrows += o.rows;
-        if (pb_rows::IsVarintKind(j.kind)) t.ngroups += o.count / kPbRowsGroupElems + 2;
-        tr[k] = PbRowsResult{0, 0xFFFFFFFFu, 0};
-    }
-    t.jobs = tj;
-    t.njobs = (int)nlive;
-    t.jobs_dev = scratch.as<PbRowsJob>();
-    t.groups = reinterpret_cast<uint32_t*>(static_cast<char*>(scratch.p) + jobs_bytes);
-    t.row_size = t.groups + t.ngroups;
-    t.row_pay = t.row_size + t.nrows;
-    t.row_delta = t.row_pay + t.nrows;
-    t.block_off = t.row_delta + t.nrows;
-    t.first_bad = t.block_off + t.nrblocks + nlive;
-    t.res = tr;
-    if (RunOnPoolStream(device, [&](hipStream_t s) { return LaunchPbRowsBuild(t, s); }) != 0) return -1;
-    for (size_t k = 0; k < nlive; ++k) {
-        DeviceRowsJob& j = jobs[live[k]];
-        j.len = tr[k].len;
-        j.err = tr[k].err;
-        if (j.err == 1) j.first_bad = tr[k].first_bad;
-        if (j.err) {
-            g_build_err.fetch_add(1, std::memory_order_relaxed);
-            continue;
-        }
-        g_built_row_jobs.fetch_add(1, std::memory_order_relaxed);
-        g_built_rows.fetch_add((int64_t)j.rows, std::memory_order_relaxed);
-        g_built_row_bytes.fetch_add((int64_t)j.len, std::memory_order_relaxed);
-    }
-    return 0;
-}
-
-int BuildDeviceRows(const DeviceRowsJob& job, Buf* out, int device) {
-    const uint64_t worst = DeviceRowsWorstCaseBytes(job);
-    if (!out || worst == 0) {
-        g_build_err.fetch_add(1, std::memory_order_relaxed);
-        return 2;
-    }
-    const size_t cap = (size_t)std::max<uint64_t>(worst, 16);
-    HbmBlock dst(cap, device);
-    if (!dst) return -1;
-    DeviceRowsJob j = job;
-    j.dst = dst.p;
-    j.cap = cap;
-    const int rc = DeviceBuildRows(&j, 1, device);
-    if (rc != 0 || j.err != 0) return rc != 0 ? -1 : j.err;
-    ArenaBlock* a = new ArenaBlock{cap, device};
-    if (AppendDevice(out, dst.p, (size_t)j.len, device, free_arena_block, a) != 0) {
-        delete a;
-        return -1;
-    }
-    dst.release();  // the Buf block owns it now
-    return 0;
-}
-
-namespace {
-
 static_assert(kDeviceRecordMaxColumns == pb_records::kRecordMaxColumns, "one column limit");
 
 // The job as the rules see it; false when it has no column table to look at.
@@ -620,39 +500,66 @@ bool records_job_ok(const DeviceRecordsJob& j) {
     return true;
 }
 
-}  // namespace
-
-uint64_t DeviceRecordsWorstCaseBytes(const DeviceRecordsJob& job) {
-    pb_records::Column cols[pb_records::kRecordMaxColumns];
-    pb_records::Job view;
-    return records_view(job, cols, &view) ? pb_records::WorstCaseBytes(view) : 0;
+// What the two fronts of the builder say about their job type: the host's
+// gate, the columns, where the offender goes and which counters a built job
+// moves. A rows job is one column, headerless (base/pb_records.h) when its
+// inner is 0.
+bool build_job_ok(const DeviceRowsJob& j) { return rows_job_ok(j); }
+bool build_job_ok(const DeviceRecordsJob& j) { return records_job_ok(j); }
+uint32_t build_ncols(const DeviceRowsJob&) { return 1; }
+uint32_t build_ncols(const DeviceRecordsJob& j) { return j.ncols; }
+DeviceRecordColumn build_column(const DeviceRowsJob& j, uint32_t) {
+    return DeviceRecordColumn{j.inner, j.kind, j.src, j.count, j.row_ends};
+}
+const DeviceRecordColumn& build_column(const DeviceRecordsJob& j, uint32_t c) { return j.columns[c]; }
+// the row part of the row << 4 | column key: a rows job has one column
+void build_offender(DeviceRowsJob& j, uint32_t row, uint32_t) { j.first_bad = row; }
+void build_offender(DeviceRecordsJob& j, uint32_t row, uint32_t column) {
+    j.first_bad = row;
+    j.bad_column = column;
+}
+void build_count(const DeviceRowsJob& j) {
+    g_built_row_jobs.fetch_add(1, std::memory_order_relaxed);
+    g_built_rows.fetch_add((int64_t)j.rows, std::memory_order_relaxed);
+    g_built_row_bytes.fetch_add((int64_t)j.len, std::memory_order_relaxed);
+}
+void build_count(const DeviceRecordsJob& j) {
+    g_built_record_jobs.fetch_add(1, std::memory_order_relaxed);
+    g_built_records.fetch_add((int64_t)j.rows, std::memory_order_relaxed);
+    g_built_record_bytes.fetch_add((int64_t)j.len, std::memory_order_relaxed);
 }
 
-// On a pool stream of its own, as DeviceBuildRows and for its reason.
-int DeviceBuildRecords(DeviceRecordsJob* jobs, int n, int device) {
+// The builder behind DeviceBuildRows and DeviceBuildRecords. The jobs go to a
+// pool stream of their own rather than into the cross-RPC codec batch: a job
+// brings scratch sized by its rows and groups (a word per row and two per row
+// and column), which the batch's recycled tables do not hold, and its seven
+// launches share nothing with the small codec jobs of other RPCs.
+template <typename Job>
+int build_records(Job* jobs, int n, int device) {
     if (n <= 0) return 0;
     if (!jobs || device < 0) return -1;
     std::vector<int> live;  // the jobs that go to the device, in order
     uint64_t nchunks = 0, nrblocks = 0, ngroups = 0, nrows = 0, ncolrows = 0, ncols = 0;
     for (int i = 0; i < n; ++i) {
-        DeviceRecordsJob& j = jobs[i];
+        Job& j = jobs[i];
         j.len = 0;
-        j.first_bad = j.bad_column = 0xFFFFFFFFu;
+        build_offender(j, 0xFFFFFFFFu, 0xFFFFFFFFu);
         j.err = 0;
-        if (!records_job_ok(j)) {
+        if (!build_job_ok(j)) {
             j.err = 2;
             g_build_err.fetch_add(1, std::memory_order_relaxed);
             continue;
         }
-        for (uint32_t c = 0; c < j.ncols; ++c) {
-            const DeviceRecordColumn& col = j.columns[c];
+        const uint32_t jcols = build_ncols(j);
+        for (uint32_t c = 0; c < jcols; ++c) {
+            const DeviceRecordColumn& col = build_column(j, c);
             nchunks += (col.count + kPbRowsChunkElems - 1) / kPbRowsChunkElems;
             if (pb_rows::IsVarintKind(col.kind)) ngroups += col.count / kPbRowsGroupElems + 2;
         }
         nrblocks += (j.rows + kPbRowsBlockRows - 1) / kPbRowsBlockRows;
         nrows += j.rows;
-        ncolrows += j.rows * j.ncols;
-        ncols += j.ncols;
+        ncolrows += j.rows * jcols;
+        ncols += jcols;
         live.push_back(i);
     }
     if (live.empty()) return 0;
@@ -672,18 +579,18 @@ int DeviceBuildRecords(DeviceRecordsJob* jobs, int n, int device) {
     PbRecordsResult* tr = reinterpret_cast<PbRecordsResult*>(tc + ncols);
     PbRecordsTables t;
     for (size_t k = 0; k < nlive; ++k) {
-        const DeviceRecordsJob& j = jobs[live[k]];
+        const Job& j = jobs[live[k]];
         PbRecordsJob& o = tj[k];
         o.dst = static_cast<uint8_t*>(j.dst);
         o.cap = j.cap;
         o.rows = (uint32_t)j.rows;
         o.number = j.number;
-        o.ncols = j.ncols;
+        o.ncols = build_ncols(j);
         o.first_col = (uint32_t)t.ncols;
         o.first_rblock = t.nrblocks;
         o.first_row = t.nrows;
-        for (uint32_t c = 0; c < j.ncols; ++c) {
-            const DeviceRecordColumn& in = j.columns[c];
+        for (uint32_t c = 0; c < o.ncols; ++c) {
+            const DeviceRecordColumn& in = build_column(j, c);
             PbRowsJob& col = tc[t.ncols++];
             col.src = in.src;
             col.row_ends = in.row_ends;
@@ -721,26 +628,23 @@ int DeviceBuildRecords(DeviceRecordsJob* jobs, int n, int device) {
     t.res = tr;
     if (RunOnPoolStream(device, [&](hipStream_t s) { return LaunchPbRecordsBuild(t, s); }) != 0) return -1;
     for (size_t k = 0; k < nlive; ++k) {
-        DeviceRecordsJob& j = jobs[live[k]];
+        Job& j = jobs[live[k]];
         j.len = tr[k].len;
         j.err = tr[k].err;
-        if (j.err == 1) {
-            j.first_bad = tr[k].first_bad;
-            j.bad_column = tr[k].bad_column;
-        }
+        if (j.err == 1) build_offender(j, tr[k].first_bad, tr[k].bad_column);
         if (j.err) {
             g_build_err.fetch_add(1, std::memory_order_relaxed);
             continue;
         }
-        g_built_record_jobs.fetch_add(1, std::memory_order_relaxed);
-        g_built_records.fetch_add((int64_t)j.rows, std::memory_order_relaxed);
-        g_built_record_bytes.fetch_add((int64_t)j.len, std::memory_order_relaxed);
+        build_count(j);
     }
     return 0;
 }
 
-int BuildDeviceRecords(const DeviceRecordsJob& job, Buf* out, int device) {
-    const uint64_t worst = DeviceRecordsWorstCaseBytes(job);
+// The job's records (or rows) into a fresh arena block of the worst-case
+// size, appended to *out as one DEVICE block.
+template <typename Job>
+int build_into_buf(const Job& job, uint64_t worst, Buf* out, int device) {
     if (!out || worst == 0) {
         g_build_err.fetch_add(1, std::memory_order_relaxed);
         return 2;
@@ -748,10 +652,10 @@ int BuildDeviceRecords(const DeviceRecordsJob& job, Buf* out, int device) {
     const size_t cap = (size_t)std::max<uint64_t>(worst, 16);
     HbmBlock dst(cap, device);
     if (!dst) return -1;
-    DeviceRecordsJob j = job;
+    Job j = job;
     j.dst = dst.p;
     j.cap = cap;
-    const int rc = DeviceBuildRecords(&j, 1, device);
+    const int rc = build_records(&j, 1, device);
     if (rc != 0 || j.err != 0) return rc != 0 ? -1 : j.err;
     ArenaBlock* a = new ArenaBlock{cap, device};
     if (AppendDevice(out, dst.p, (size_t)j.len, device, free_arena_block, a) != 0) {
@@ -760,6 +664,30 @@ int BuildDeviceRecords(const DeviceRecordsJob& job, Buf* out, int device) {
     }
     dst.release();  // the Buf block owns it now
     return 0;
+}
+
+}  // namespace
+
+uint64_t DeviceRowsWorstCaseBytes(const DeviceRowsJob& job) {
+    return pb_rows::WorstCaseBytes(job.number, job.inner, job.kind, job.count, job.rows);
+}
+
+int DeviceBuildRows(DeviceRowsJob* jobs, int n, int device) { return build_records(jobs, n, device); }
+
+int BuildDeviceRows(const DeviceRowsJob& job, Buf* out, int device) {
+    return build_into_buf(job, DeviceRowsWorstCaseBytes(job), out, device);
+}
+
+uint64_t DeviceRecordsWorstCaseBytes(const DeviceRecordsJob& job) {
+    pb_records::Column cols[pb_records::kRecordMaxColumns];
+    pb_records::Job view;
+    return records_view(job, cols, &view) ? pb_records::WorstCaseBytes(view) : 0;
+}
+
+int DeviceBuildRecords(DeviceRecordsJob* jobs, int n, int device) { return build_records(jobs, n, device); }
+
+int BuildDeviceRecords(const DeviceRecordsJob& job, Buf* out, int device) {
+    return build_into_buf(job, DeviceRecordsWorstCaseBytes(job), out, device);
 }
 
 namespace {

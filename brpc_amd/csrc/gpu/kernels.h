@@ -331,127 +331,87 @@ int LaunchPbMsgEncode(const PbMsgTables& t, hipStream_t s);
 // prefix[0, n) in place (device memory), for other kernels' size tables.
 int LaunchPbRunPrefix(uint32_t* prefix, int n, hipStream_t s);
 
-// Row builder: one flat array in device memory plus a table of row ends
-// becomes the occurrences of one repeated field (base/pb_rows.h has the wire
-// rules; pb::SerializeRows is the host twin). A row's header depends on its
-// encoded size, so on every value in it: nothing here takes a size from the
-// host. An array is cut into chunks of kPbRowsChunkElems elements and, for the
-// kinds encoded as varints, into groups of 64 elements; rows are taken 256 to
-// a workgroup. All jobs share seven launches on one stream, ordered by the
-// launches alone (no count or size is read back in between):
-//   init    copies the job table to device memory, resets first_bad
-//   size    varint kinds only: a workgroup per chunk writes the encoded bytes
-//           of each of its groups into groups[] (fixed-width kinds need none:
-//           the bytes before element e are e times the width)
-//   prefix  LaunchPbRunPrefix over groups[]
-//   rows    a lane per row: the bytes before an element are its group's
-//           prefix plus at most 63 element sizes recomputed from the source;
-//           the row's payload size is the difference of two of them. Writes
-//           the row's total size into row_size[], its payload size into
-//           row_pay[] and the bytes before its first element into row_delta[],
-//           and the sum of the workgroup's row sizes into block_off[]; a row
-//           whose end lies before its start, or a last end other than count,
-//           goes into first_bad (atomicMin)
-//   prefix  LaunchPbRunPrefix over block_off[]: one entry per 256 rows (the
-//           one-workgroup scan over an entry per row took 600 us of the 750 us
-//           of 2^20 one-element rows)
-//   heads   a lane per row: a job that is malformed (err 1) or longer than its
-//           cap (err 3) gets nothing written here or later; else the row's
-//           offset is its block's plus a scan of the sizes inside the
-//           workgroup, its header is written there (empty rows are complete
-//           with it) and row_delta[] becomes the distance from "bytes before
-//           element e" to "offset of element e in dst" for the row's elements.
-//           Row 0's lane writes the job's result
-//   place   a workgroup per chunk finds the rows that meet it by binary
-//           search in row_ends. A chunk that meets few rows is encoded into LDS
-//           and leaves per row segment with 16-byte stores; one that meets
-//           many marks the row starts in LDS, spreads the row index over the
-//           elements with a max-scan, and every lane stores its own element.
-//           A chunk whose bytes are not what the size pass measured, or a
-//           store that would leave the message, writes nothing and marks err 4
-// The job table is a device-readable (pinned host) array, res a
-// device-writable one; everything else is device memory.
-constexpr uint32_t kPbRowsChunkElems = kPbRunChunkElems;
-constexpr uint32_t kPbRowsGroupElems = 64;
-constexpr uint32_t kPbRowsBlockRows = 256;
-struct PbRowsJob {
-    const void* src;           // count elements, the kind's vector layout, naturally aligned
-    const uint32_t* row_ends;  // rows entries
-    uint8_t* dst;              // any alignment, never null
-    uint64_t cap;
-    uint32_t count, rows;      // rows >= 1
-    uint32_t number, inner, kind;
-    uint32_t first_chunk, nchunks;  // nchunks = ceil(count / kPbRowsChunkElems)
-    uint32_t first_rblock;          // ceil(rows / kPbRowsBlockRows) row blocks; job k's entries of block_off start
-                                    // at first_rblock + k (its blocks, then one entry for its total)
-    uint32_t first_row;             // in row_size, row_pay and row_delta: rows entries each
-    uint32_t first_group;           // in groups: count / 64 + 2 entries (varint kinds only)
-};
-struct PbRowsResult {
-    uint64_t len;        // serialized size (also when it did not fit)
-    uint32_t first_bad;  // with err 1
-    int32_t err;         // 0, 1, 3, 4
-};
-struct PbRowsTables {
-    const PbRowsJob* jobs = nullptr;
-    int njobs = 0;
-    PbRowsJob* jobs_dev = nullptr;   // njobs
-    uint32_t nchunks = 0, nrblocks = 0, ngroups = 0, nrows = 0;  // of all jobs
-    uint32_t* groups = nullptr;      // ngroups
-    uint32_t* row_size = nullptr;    // nrows
-    uint32_t* row_pay = nullptr;     // nrows
-    uint32_t* row_delta = nullptr;   // nrows
-    uint32_t* block_off = nullptr;   // nrblocks + njobs
-    uint32_t* first_bad = nullptr;   // njobs
-    PbRowsResult* res = nullptr;     // njobs
-};
-int LaunchPbRowsBuild(const PbRowsTables& t, hipStream_t s);
-
 // Record builder: several columns in device memory become the occurrences of
 // one repeated sub-message with several fields (base/pb_records.h has the
-// wire rules; pb::SerializeRecords is the host twin). A column is a
-// PbRowsJob: ragged columns bring a table of row ends, a scalar column has
-// none and element r belongs to record r. The seven launches are the row
-// builder's, over columns where it goes over jobs:
+// wire rules; pb::SerializeRecords is the host twin). A column is one flat
+// array plus a table of row ends; a scalar column has no table and element r
+// belongs to record r. A rows job (one flat array plus row ends -> the
+// occurrences of one repeated field; base/pb_rows.h, host twin
+// pb::SerializeRows) is a record job of one column. Its `repeated bytes`
+// form, inner == 0, is the headerless column of base/pb_records.h: the
+// record header is followed by the payload, with no field header in between.
+// A header depends on the encoded size behind it, so on every value: nothing
+// here takes a size from the host. A column is cut into chunks of
+// kPbRowsChunkElems elements and, for the kinds encoded as varints, into
+// groups of 64 elements; records are taken 256 to a workgroup. All jobs share
+// seven launches on one stream, ordered by the launches alone (no count or
+// size is read back in between):
 //   init     copies the job and column tables to device memory, resets each
 //            job's offender word and zeroes the tail groups of each varint
 //            column
-//   size     the row builder's kernel over the column table: one grid over
-//            the chunks of every column of every job
+//   size     varint kinds only: a workgroup per chunk, one grid over the
+//            chunks of every column of every job, writes the encoded bytes of
+//            each of its groups into groups[] (fixed-width kinds need none:
+//            the bytes before element e are e times the width)
 //   prefix   LaunchPbRunPrefix over groups[]
-//   measure  a lane per record, 256 to a workgroup: for each column the
-//            payload bytes as the difference of two byte prefixes, into
-//            col_pay[] and (the bytes before the row's first element)
-//            col_delta[]; the record's size, header and field headers
-//            included, into row_size[] and the workgroup's sum into
+//   measure  a lane per record: the bytes before an element are its group's
+//            prefix plus at most 63 element sizes recomputed from the source;
+//            a column's payload in the row is the difference of two of them,
+//            into col_pay[], and the bytes before the row's first element go
+//            into col_delta[]. The record's size, header and field headers
+//            included, goes into row_size[] and the workgroup's sum into
 //            block_off[]. A column whose row end lies before its start, or
 //            whose last end is not its count, goes into bad[] through one
 //            atomic min on row << 4 | column: the lowest row, then the lowest
 //            column
-//   prefix   LaunchPbRunPrefix over block_off[]
+//   prefix   LaunchPbRunPrefix over block_off[]: one entry per 256 rows (the
+//            one-workgroup scan over an entry per row took 600 us of the 750 us
+//            of 2^20 one-element rows)
 //   heads    a lane per record: row 0's lane writes the job's result; a job
 //            that is malformed (err 1) or longer than its cap (err 3) gets
-//            nothing written here or later. Else the record's header and
-//            every field's header (for a scalar column: its tag) are written
-//            at their offsets and col_delta[] becomes the distance from
-//            "bytes before element e" to "offset of element e in dst"
-//   place    the row builder's place pass (same code) over every column's
-//            chunks, each with its column's delta; err 4 as there
+//            nothing written here or later. Else the record's offset is its
+//            block's plus a scan of the sizes inside the workgroup; its header
+//            and every field's header (for a scalar column: its tag) are
+//            written there (a record without payload is complete with them)
+//            and col_delta[] becomes the distance from "bytes before element
+//            e" to "offset of element e in dst"
+//   place    a workgroup per chunk of every column finds the rows that meet
+//            it by binary search in row_ends. A chunk that meets few rows is
+//            encoded into LDS and leaves per row segment with 16-byte stores;
+//            one that meets many marks the row starts in LDS, spreads the row
+//            index over the elements with a max-scan, and every lane stores
+//            its own element, each at its column's delta. A chunk whose bytes
+//            are not what the size pass measured, or a store that would leave
+//            the message, writes nothing and marks err 4
 // The job and column tables are device-readable (pinned host) arrays, res a
 // device-writable one; everything else is device memory.
+constexpr uint32_t kPbRowsChunkElems = kPbRunChunkElems;
+constexpr uint32_t kPbRowsGroupElems = 64;
+constexpr uint32_t kPbRowsBlockRows = 256;
+// A column. dst / cap / number / rows are its job's; first_chunk and
+// first_group count over all columns of all jobs.
+struct PbRowsJob {
+    const void* src;           // count elements, the kind's vector layout, naturally aligned
+    const uint32_t* row_ends;  // rows entries; null for a scalar column (count == rows)
+    uint8_t* dst;              // any alignment, never null
+    uint64_t cap;
+    uint32_t count, rows;      // rows >= 1
+    uint32_t number, inner, kind;   // inner 0: the headerless column
+    uint32_t first_chunk, nchunks;  // nchunks = ceil(count / kPbRowsChunkElems)
+    uint32_t first_rblock;          // the index of its record job
+    uint32_t first_row;             // in col_pay and col_delta: rows entries each
+    uint32_t first_group;           // in groups: count / 64 + 2 entries (varint kinds only)
+};
 struct PbRecordsJob {
     uint8_t* dst;  // any alignment, never null
     uint64_t cap;
     uint32_t rows;  // >= 1
     uint32_t number;
     uint32_t ncols, first_col;  // its columns in the column table, 1 .. pb_records::kRecordMaxColumns
-    uint32_t first_rblock;      // as PbRowsJob::first_rblock, with block_off entries at first_rblock + k
+    uint32_t first_rblock;      // ceil(rows / kPbRowsBlockRows) row blocks; job k's entries of block_off start
+                                // at first_rblock + k (its blocks, then one entry for its total)
     uint32_t first_row;         // in row_size: rows entries
 };
-// A column is a PbRowsJob with: row_ends null for a scalar column (count ==
-// rows), dst / cap / number / rows the job's, first_chunk and first_group
-// counted over all columns of all jobs, first_row its rows entries in col_pay
-// and col_delta, and first_rblock the index of its record job.
 struct PbRecordsResult {
     uint64_t len;         // serialized size (also when it did not fit)
     uint32_t first_bad;   // with err 1

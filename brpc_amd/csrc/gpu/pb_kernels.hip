@@ -652,33 +652,17 @@ __global__ void __launch_bounds__(kRunThreads) pb_msg_place_kernel(const PbMsgCh
     wg::copy_out_phased<kRunThreads>(image, sh, dst, total);
 }
 
-// ------------------------------------------------------------- row builder
-// One flat array + row ends -> the occurrences of one repeated field
-// (kernels.h: init, size, prefix, rows, prefix, heads, place; the wire rules
-// are base/pb_rows.h). No lane walks a row: a row's payload size is the
-// difference of two byte prefixes, each a group prefix plus at most 63
-// element sizes.
+// ---------------------------------------------------------- record builder
+// Several columns -> the occurrences of one repeated sub-message with several
+// fields (kernels.h: init, size, prefix, measure, prefix, heads, place; the
+// wire rules are base/pb_records.h). One flat array + row ends -> one
+// repeated field is the job of one column. No lane walks a row: a column's
+// payload in a row is the difference of two byte prefixes, each a group
+// prefix plus at most 63 element sizes. First the parts that see one column,
+// a PbRowsJob, alone: the size pass and the body of the place pass.
 constexpr int kRowsRounds = kPbRowsChunkElems / kRunThreads;
 constexpr uint32_t kRowsFewRows = 16;  // a chunk meeting at most this many rows leaves segment by segment
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;
-
-__global__ void __launch_bounds__(64) pb_rows_init_kernel(const PbRowsJob* __restrict__ jobs, int njobs,
-                                                          PbRowsJob* __restrict__ jobs_dev,
-                                                          uint32_t* __restrict__ groups,
-                                                          uint32_t* __restrict__ first_bad) {
-    const int j = (int)(blockIdx.x * 64 + threadIdx.x);
-    if (j >= njobs) return;
-    const PbRowsJob job = jobs[j];
-    jobs_dev[j] = job;
-    first_bad[j] = kNoRow;
-    if (pb_rows::IsVarintKind(job.kind)) {
-        // the group behind the last element (written again by the size pass
-        // when it holds elements) and the one whose prefix is the total
-        const uint32_t g = job.first_group + job.count / kPbRowsGroupElems;
-        groups[g] = 0;
-        groups[g + 1] = 0;
-    }
-}
 
 __global__ void __launch_bounds__(kRunThreads) pb_rows_size_kernel(const PbRowsJob* __restrict__ jobs, int njobs,
                                                                    uint32_t* __restrict__ groups) {
@@ -713,96 +697,15 @@ __device__ __forceinline__ uint32_t rows_bytes_before(const PbRowsJob& job, cons
     return b;
 }
 
-__global__ void __launch_bounds__(kPbRowsBlockRows) pb_rows_measure_kernel(const PbRowsJob* __restrict__ jobs,
-                                                                           int njobs,
-                                                                           const uint32_t* __restrict__ groups,
-                                                                           uint32_t* __restrict__ row_size,
-                                                                           uint32_t* __restrict__ row_pay,
-                                                                           uint32_t* __restrict__ row_delta,
-                                                                           uint32_t* __restrict__ block_off,
-                                                                           uint32_t* __restrict__ first_bad) {
-    __shared__ uint32_t wave_tot[kPbRowsBlockRows / 64];
-    const int j = wg::job_of<&PbRowsJob::first_rblock>(jobs, njobs, blockIdx.x);
-    const PbRowsJob job = jobs[j];
-    const uint32_t block = blockIdx.x - job.first_rblock;
-    const uint64_t r64 = (uint64_t)block * kPbRowsBlockRows + threadIdx.x;
-    const uint32_t r = (uint32_t)r64;
-    uint32_t size = 0;
-    if (r64 < job.rows) {
-        uint32_t s = r ? job.row_ends[r - 1] : 0, e = job.row_ends[r];
-        if (e < s || (r + 1 == job.rows && e != job.count)) atomicMin(&first_bad[j], r);
-        // a malformed table gets nothing written; until then it must not make
-        // a lane read past the source
-        s = s < job.count ? s : job.count;
-        e = e < job.count ? e : job.count;
-        e = e < s ? s : e;
-        const uint32_t before = rows_bytes_before(job, groups, s);
-        const uint32_t p = rows_bytes_before(job, groups, e) - before;
-        size = p + pb_rows::HeaderBytes(job.number, job.inner, job.kind, e - s, p);
-        const uint32_t at = job.first_row + r;
-        row_size[at] = size;
-        row_pay[at] = p;
-        row_delta[at] = before;
-    }
-    uint32_t sum;
-    wg::block_excl_scan<(int)kPbRowsBlockRows>(size, wave_tot, &sum);
-    if (threadIdx.x == 0) {
-        // the job's blocks, then one entry that becomes its total under the scan
-        const uint32_t at = blockIdx.x + (uint32_t)j;
-        block_off[at] = sum;
-        if ((uint64_t)(block + 1) * kPbRowsBlockRows >= job.rows) block_off[at + 1] = 0;
-    }
-}
-
-// The job's serialized size, from the scanned block sums.
-__device__ __forceinline__ uint32_t rows_job_total(const PbRowsJob& job, int j, const uint32_t* block_off) {
-    const uint32_t first = job.first_rblock + (uint32_t)j;
-    const uint32_t nblocks = (uint32_t)(((uint64_t)job.rows + kPbRowsBlockRows - 1) / kPbRowsBlockRows);
-    return block_off[first + nblocks] - block_off[first];
-}
-
-__global__ void __launch_bounds__(kPbRowsBlockRows) pb_rows_heads_kernel(const PbRowsJob* __restrict__ jobs, int njobs,
-                                                                         const uint32_t* __restrict__ row_size,
-                                                                         const uint32_t* __restrict__ row_pay,
-                                                                         uint32_t* __restrict__ row_delta,
-                                                                         const uint32_t* __restrict__ block_off,
-                                                                         const uint32_t* __restrict__ first_bad,
-                                                                         PbRowsResult* __restrict__ res) {
-    __shared__ uint32_t wave_tot[kPbRowsBlockRows / 64];
-    const int j = wg::job_of<&PbRowsJob::first_rblock>(jobs, njobs, blockIdx.x);
-    const PbRowsJob job = jobs[j];
-    const uint64_t r64 = (uint64_t)(blockIdx.x - job.first_rblock) * kPbRowsBlockRows + threadIdx.x;
-    const bool live = r64 < job.rows;
-    const uint32_t r = (uint32_t)r64;
-    const uint32_t bad = first_bad[j];
-    const uint32_t total = rows_job_total(job, j, block_off);
-    const bool ok = bad == kNoRow && total <= job.cap;
-    if (r64 == 0) res[j] = PbRowsResult{total, bad, bad != kNoRow ? 1 : (total > job.cap ? 3 : 0)};
-    if (!ok) return;  // the whole workgroup
-    const uint32_t at = job.first_row + r;
-    // the row's offset: the blocks before this one, then the rows before it here
-    uint32_t block_size;
-    uint32_t off = wg::block_excl_scan<(int)kPbRowsBlockRows>(live ? row_size[at] : 0u, wave_tot, &block_size);
-    if (!live) return;
-    off += block_off[blockIdx.x + (uint32_t)j] - block_off[job.first_rblock + (uint32_t)j];
-    const uint32_t nelems = job.row_ends[r] - (r ? job.row_ends[r - 1] : 0);
-    const uint32_t p = row_pay[at];
-    const uint32_t hn = pb_rows::HeaderBytes(job.number, job.inner, job.kind, nelems, p);
-    if ((uint64_t)off + hn + p > total) return;  // row_ends changed since the rows pass: nothing leaves the message
-    pb_rows::PutHeader(job.dst + off, job.number, job.inner, job.kind, nelems, p);
-    row_delta[at] = off + hn - row_delta[at];
-}
-
-// Entry r of a table of row ends. A column of the record builder may come
-// without one (kIota): element r is row r.
+// Entry r of a table of row ends. A scalar column comes without one (kIota):
+// element r is row r.
 template <bool kIota>
 __device__ __forceinline__ uint32_t rows_end_at(const uint32_t* ends, uint64_t r) {
     if (kIota && !ends) return (uint32_t)r + 1;
     return ends[r];
 }
 
-// The place pass of one chunk of a job (or of one column of a record job)
-// whose rows were measured and whose message of `total` bytes fits: delta[r]
+// The place pass of one chunk of one column of a record job whose rows were measured and whose message of `total` bytes fits: delta[r]
 // is the distance from "bytes before element e" to "offset of element e in
 // dst" for row r. *err = 4 below: a source (or row_ends) changed under the
 // builder's hands, seen as a size that no longer matches or a store that
@@ -1004,27 +907,8 @@ __device__ __forceinline__ void rows_place_chunk(const PbRowsJob& job, uint32_t 
     if (changed) *err = 4;
 }
 
-__global__ void __launch_bounds__(kRunThreads) pb_rows_place_kernel(const PbRowsJob* __restrict__ jobs, int njobs,
-                                                                    const uint32_t* __restrict__ groups,
-                                                                    const uint32_t* __restrict__ block_off,
-                                                                    const uint32_t* __restrict__ row_delta,
-                                                                    const uint32_t* __restrict__ first_bad,
-                                                                    PbRowsResult* __restrict__ res) {
-    const int j = wg::job_of<&PbRowsJob::first_chunk>(jobs, njobs, blockIdx.x);
-    const PbRowsJob job = jobs[j];
-    if (first_bad[j] != kNoRow) return;
-    const uint32_t total = rows_job_total(job, j, block_off);
-    if (total > job.cap) return;
-    rows_place_chunk<false>(job, blockIdx.x - job.first_chunk, total, groups, row_delta + job.first_row, &res[j].err);
-}
-
-// ---------------------------------------------------------- record builder
-// Several columns -> the occurrences of one repeated sub-message with several
-// fields (kernels.h: init, size, prefix, measure, prefix, heads, place; the
-// wire rules are base/pb_records.h). A column is a PbRowsJob, so the size
-// pass is the row builder's kernel over the column table and the place pass
-// is its body; what is new is that a row's size sums over its columns and
-// that each column has its own delta.
+// The passes that see a record job: a row's size sums over its columns, and
+// each column has its own delta.
 constexpr uint64_t kNoRecord = ~0ull;  // the offender key: row << 4 | column
 
 __global__ void __launch_bounds__(64) pb_records_init_kernel(const PbRecordsJob* __restrict__ jobs, int njobs,
@@ -1042,8 +926,8 @@ __global__ void __launch_bounds__(64) pb_records_init_kernel(const PbRecordsJob*
     const PbRowsJob col = cols[i];
     cols_dev[i] = col;
     if (pb_rows::IsVarintKind(col.kind)) {
-        // as pb_rows_init_kernel: the group behind the last element and the
-        // one whose prefix is the total
+        // the group behind the last element (written again by the size pass
+        // when it holds elements) and the one whose prefix is the total
         const uint32_t g = col.first_group + col.count / kPbRowsGroupElems;
         groups[g] = 0;
         groups[g + 1] = 0;
@@ -1097,6 +981,7 @@ __global__ void __launch_bounds__(kPbRowsBlockRows) pb_records_measure_kernel(
     }
 }
 
+// The job's serialized size, from the scanned block sums.
 __device__ __forceinline__ uint32_t records_job_total(const PbRecordsJob& job, int j, const uint32_t* block_off) {
     const uint32_t first = job.first_rblock + (uint32_t)j;
     const uint32_t nblocks = (uint32_t)(((uint64_t)job.rows + kPbRowsBlockRows - 1) / kPbRowsBlockRows);
@@ -2148,36 +2033,6 @@ int LaunchPbRecordsSplit(const PbRecSplitTables& r, hipStream_t s) {
     return 0;
 }
 #undef SPLIT_LAUNCH
-
-int LaunchPbRowsBuild(const PbRowsTables& t, hipStream_t s) {
-    if (t.njobs <= 0) return 0;
-    if (!t.jobs || !t.jobs_dev || !t.row_size || !t.row_pay || !t.row_delta || !t.block_off || !t.first_bad || !t.res ||
-        t.nrblocks == 0 || (t.ngroups > 0 && !t.groups) || t.ngroups > 0x7FFFFFFFu) {
-        return -1;
-    }
-    hipLaunchKernelGGL(pb_rows_init_kernel, dim3((unsigned)(t.njobs + 63) / 64), dim3(64), 0, s, t.jobs, t.njobs,
-                       t.jobs_dev, t.groups, t.first_bad);
-    if (hipGetLastError() != hipSuccess) return -1;
-    if (t.ngroups > 0) {
-        if (t.nchunks > 0) {
-            hipLaunchKernelGGL(pb_rows_size_kernel, dim3(t.nchunks), dim3(kRunThreads), 0, s, t.jobs_dev, t.njobs,
-                               t.groups);
-            if (hipGetLastError() != hipSuccess) return -1;
-        }
-        if (LaunchPbRunPrefix(t.groups, (int)t.ngroups, s) != 0) return -1;
-    }
-    hipLaunchKernelGGL(pb_rows_measure_kernel, dim3(t.nrblocks), dim3(kPbRowsBlockRows), 0, s, t.jobs_dev, t.njobs,
-                       t.groups, t.row_size, t.row_pay, t.row_delta, t.block_off, t.first_bad);
-    if (hipGetLastError() != hipSuccess) return -1;
-    if (LaunchPbRunPrefix(t.block_off, (int)(t.nrblocks + (uint32_t)t.njobs), s) != 0) return -1;
-    hipLaunchKernelGGL(pb_rows_heads_kernel, dim3(t.nrblocks), dim3(kPbRowsBlockRows), 0, s, t.jobs_dev, t.njobs,
-                       t.row_size, t.row_pay, t.row_delta, t.block_off, t.first_bad, t.res);
-    if (hipGetLastError() != hipSuccess) return -1;
-    if (t.nchunks == 0) return 0;
-    hipLaunchKernelGGL(pb_rows_place_kernel, dim3(t.nchunks), dim3(kRunThreads), 0, s, t.jobs_dev, t.njobs, t.groups,
-                       t.block_off, t.row_delta, t.first_bad, t.res);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
 
 int LaunchPbRecordsBuild(const PbRecordsTables& t, hipStream_t s) {
     if (t.njobs <= 0) return 0;

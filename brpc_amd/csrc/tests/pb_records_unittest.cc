@@ -475,6 +475,47 @@ TEST(PbRecords, bad_jobs_are_refused_before_any_launch) {
     EXPECT_EQ(out.size(), 0u);
 }
 
+// DeviceBuildRows runs a rows job as a record job of one column: the record
+// header rules must give pb_rows' row header for every kind, number, inner
+// and payload size at which a varint grows, the headerless column (inner 0,
+// bytes) and the empty rows included.
+TEST(PbRecords, one_column_headers_are_the_row_headers) {
+    const uint32_t numbers[] = {1, 15, 16, (1u << 29) - 1};
+    const uint64_t pays[] = {0, 1, 127, 128, 16383, 16384, (1u << 21) - 1, 1u << 21, 1u << 28, 0xFFFFFFFFull - 20};
+    int checked = 0;
+    for (uint32_t kind = 0; kind <= 9; ++kind) {
+        for (int ii = 0; ii < 5; ++ii) {
+            if (ii == 4 && kind != pb_rows::kKindBytes) continue;
+            const uint32_t inner = ii == 4 ? 0 : numbers[ii];
+            for (uint32_t number : numbers) {
+                for (uint64_t p : pays) {
+                    // a packed row has no element exactly when it has no byte;
+                    // an empty bytes row is one empty element or none
+                    const int ncounts = kind == pb_rows::kKindBytes && p == 0 ? 2 : 1;
+                    for (int k = 0; k < ncounts; ++k) {
+                        const uint64_t nelems = p == 0 ? (uint64_t)k : (kind == pb_rows::kKindBytes ? p : 1);
+                        const uint32_t fh = pb_records::FieldHeaderBytes(inner, kind, false, p);
+                        const uint32_t want = pb_rows::HeaderBytes(number, inner, kind, nelems, p);
+                        ASSERT_EQ(want, fh + pb_records::RowHeaderBytes(number, fh + p));
+                        uint8_t a[pb_rows::kMaxHeaderBytes + 1], b[pb_rows::kMaxHeaderBytes + 1];
+                        memset(a, 0xEE, sizeof(a));
+                        memset(b, 0xEE, sizeof(b));
+                        ASSERT_EQ(pb_rows::PutHeader(a, number, inner, kind, nelems, p), want);
+                        uint32_t n = pb_records::PutRowHeader(b, number, fh + p);
+                        n += pb_records::PutFieldHeader(b + n, inner, kind, false, p);
+                        ASSERT_EQ(n, want);
+                        ASSERT_EQ(memcmp(a, b, sizeof(a)), 0);
+                        ++checked;
+                    }
+                }
+            }
+        }
+    }
+    // 10 kinds x 4 inners x 4 numbers x 10 sizes, bytes with a fifth inner and
+    // two empty rows per (inner, number)
+    EXPECT_EQ(checked, 10 * 4 * 4 * 10 + 4 * 10 + 5 * 4);
+}
+
 TEST(PbRecords, table_rows_have_the_layout_the_kernels_read) {
     EXPECT_EQ(sizeof(gpu::PbRecordsJob), 40u);
     EXPECT_EQ(sizeof(gpu::PbRecordsResult), 24u);

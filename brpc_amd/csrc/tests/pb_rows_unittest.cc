@@ -327,7 +327,6 @@ TEST(PbRows, bad_jobs_are_refused_before_any_launch) {
 
 TEST(PbRows, table_rows_have_the_layout_the_kernels_read) {
     EXPECT_EQ(sizeof(gpu::PbRowsJob), 72u);
-    EXPECT_EQ(sizeof(gpu::PbRowsResult), 16u);
     EXPECT_EQ(gpu::kDeviceFieldFixed32, pb_rows::kKindFixed32);
     EXPECT_EQ(gpu::kDeviceFieldFixed64, pb_rows::kKindFixed64);
     EXPECT_EQ(gpu::kDeviceFieldBytes, pb_rows::kKindBytes);

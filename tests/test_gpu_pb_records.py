@@ -305,6 +305,8 @@ def test_good_refused_short_and_malformed_jobs_in_one_call(native, dev):
 
 @pytest.mark.parametrize("kind", sorted(W.KINDS))
 def test_one_column_equals_the_row_builder(native, dev, kind):
+    # both sides run the same kernels (a rows job is a one-column record job);
+    # the independent check of the rows is the host twin in test_gpu_pb_rows.py
     sizes = [0, 3, 0, 0, 2045, 1, 2, 700, 0, 64, 63, 65, 0]
     arr = W.values(kind, sum(sizes), 200 + kind)
     ends = np.cumsum(sizes).astype(np.uint32)

@@ -1,5 +1,6 @@
 """Device row builder (gpu/device_codec.h DeviceBuildRows and the kernels
-behind LaunchPbRowsBuild): a flat array in HBM plus a table of row ends
+behind LaunchPbRecordsBuild, which it runs as a record job of one column,
+headerless for inner 0): a flat array in HBM plus a table of row ends
 becomes the occurrences of one repeated field in HBM. Every case compares the
 device's bytes with pb_rows_wire.reference (a numpy serializer written from
 the wire rules), one case per kind also with the project's host serializer;
@@ -115,6 +116,22 @@ def test_chunk_boundaries_and_empty_rows(native, dev, kind, inner):
     assert err == 0 and twin == got
 
 
+@pytest.mark.parametrize("kind,inner", [(1, 2), (W.FIXED32, 2), (W.BYTES, 0), (W.BYTES, 3)])
+def test_rows_around_a_row_block_and_elements_around_a_chunk(native, dev, kind, inner):
+    """255, 256 and 257 rows (a row block is 256) over 2047, 2048 and 2049
+    elements (a chunk is 2048), the first and the last row empty: the smallest
+    shapes that cross a row block and a chunk, each against the host twin."""
+    rng = np.random.default_rng(40 + kind + inner)
+    for rows in (255, 256, 257):
+        for count in (2047, 2048, 2049):
+            arr = W.values(kind, count, 400 + kind)
+            ends = np.concatenate([[0], np.sort(rng.integers(0, count + 1, rows - 3)), [count, count]]).astype(np.uint32)
+            assert ends.size == rows and ends[0] == 0 and ends[-2] == ends[-1] == count
+            got = _check(native, dev, 4, inner, kind, arr, ends)
+            err, _, twin = native.pb_serialize_rows(4, inner, kind, arr.tobytes(), [int(e) for e in ends])
+            assert err == 0 and twin == got, (rows, count)
+
+
 @pytest.mark.parametrize("kind,inner", ALL)
 def test_matches_the_host_serializer_and_parses_back(native, dev, tmp_path, kind, inner):
     """Against the wire bytes of the project's own host serializer (the batch
@@ -184,24 +201,44 @@ def test_every_destination_alignment(native, dev, kind, inner):
 def test_a_refused_and_a_short_job_leave_the_others_alone(native, dev):
     a = W.values(3, 5000, 1)
     b = W.values(W.FIXED64, 3000, 2)
-    a_ends, b_ends = [10, 10, 2500, 5000], np.arange(1, 3001)
+    c = W.values(W.BYTES, 2600, 3)
+    a_ends, b_ends, c_ends = [10, 10, 2500, 5000], np.arange(1, 3001), [0, 2049, 2049, 2600]
     jobs = [dict(number=3, inner=1, kind=3, arr=a, ends=a_ends),
             dict(number=0, inner=1, kind=3, arr=a, ends=a_ends),                      # refused: number 0
             dict(number=3, inner=1, kind=3, arr=a, ends=a_ends, cap=lambda n: n - 1),  # a byte short
             dict(number=3, inner=0, kind=3, arr=a, ends=a_ends),                      # refused: no wrapper, not bytes
-            dict(number=9, inner=4, kind=W.FIXED64, arr=b, ends=b_ends, cap=lambda n: n)]  # cap == len
+            dict(number=9, inner=4, kind=W.FIXED64, arr=b, ends=b_ends, cap=lambda n: n),  # cap == len
+            dict(number=5, inner=0, kind=W.BYTES, arr=c, ends=c_ends),                # no wrapper: repeated bytes
+            dict(number=3, inner=1, kind=3, arr=a, ends=[10, 9, 2500, 5000])]         # row_ends decreases at row 1
     c0 = native.gpu.device_codec_stats()
     res = _run(native, dev, jobs)
     c1 = native.gpu.device_codec_stats()
     want_a = W.reference(3, 1, 3, a, a_ends)
     want_b = W.reference(9, 4, W.FIXED64, b, b_ends)
-    assert [r[1] for r in res] == [0, 2, 3, 2, 0]
-    assert res[0][3] == want_a and res[4][3] == want_b
+    want_c = W.reference(5, 0, W.BYTES, c, c_ends)
+    assert [r[1] for r in res] == [0, 2, 3, 2, 0, 0, 1]
+    assert res[0][3] == want_a and res[4][3] == want_b and res[5][3] == want_c
     assert res[2][0] == len(want_a)  # the size it needs
-    assert c1["built_row_jobs"] - c0["built_row_jobs"] == 2
-    assert c1["built_rows"] - c0["built_rows"] == 4 + 3000
-    assert c1["built_row_bytes"] - c0["built_row_bytes"] == len(want_a) + len(want_b)
-    assert c1["build_errors"] - c0["build_errors"] == 3
+    assert res[6][2] == 1            # the row; _run saw its dst untouched, as the short job's
+    assert [r[2] for r in res[:6]] == [0xFFFFFFFF] * 6
+    assert c1["built_row_jobs"] - c0["built_row_jobs"] == 3
+    assert c1["built_rows"] - c0["built_rows"] == 4 + 3000 + 4
+    assert c1["built_row_bytes"] - c0["built_row_bytes"] == len(want_a) + len(want_b) + len(want_c)
+    assert c1["build_errors"] - c0["build_errors"] == 4
+    for k in ("built_record_jobs", "built_records", "built_record_bytes"):
+        assert c1[k] == c0[k]
+
+
+def test_a_rows_job_counts_as_rows_only(native, dev):
+    arr = W.values(2, 300, 9)
+    ends = [0, 1, 1, 120, 299, 300]
+    c0 = native.gpu.device_codec_stats()
+    got = _check(native, dev, 4, 2, 2, arr, ends)
+    c1 = native.gpu.device_codec_stats()
+    assert "built_record_jobs" in c0 and "build_errors" in c0
+    # the record counters, the error counter and every other one stay
+    moved = {k: c1[k] - c0[k] for k in c1 if c1[k] != c0[k]}
+    assert moved == {"built_row_jobs": 1, "built_rows": len(ends), "built_row_bytes": len(got)}
 
 
 @pytest.mark.parametrize("kind", [1, W.FIXED32])
