@@ -118,6 +118,11 @@ void InputMessenger::OnNewMessages(Socket* m) {
             }
         }
         int64_t ncut = 0;  // messages cut from this read
+        // One clock read per read call, not per message: received_us is
+        // when these bytes were read, so for the later messages of a burst
+        // it is slightly earlier than when each was cut, and spans and
+        // method latency start there. Taken when the first message is cut.
+        int64_t read_us = 0;
         for (;;) {
             size_t index = 0;
             ParseResult pr = messenger->CutInputMessage(m, &index, read_eof);
@@ -141,7 +146,8 @@ void InputMessenger::OnNewMessages(Socket* m) {
             const InputMessageHandler& h = messenger->_handlers[index];
             msg->_process = h.process;
             msg->_arg = h.arg;
-            msg->_received_us = monotonic_us();
+            if (read_us == 0) read_us = monotonic_us();
+            msg->_received_us = read_us;
             if (prepaid == 0) {
                 m->AddRefs(kPrepaidRefs);
                 prepaid = kPrepaidRefs;

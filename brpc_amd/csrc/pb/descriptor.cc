@@ -4,6 +4,7 @@
 
 #include "pb/message.h"
 #include "pb/plan.h"
+#include "pb/wire.h"
 
 namespace mrpc {
 namespace pb {
@@ -11,6 +12,28 @@ namespace pb {
 Descriptor::~Descriptor() {
     if (owns_prototype) delete prototype;
     DeleteCodecPlan(codec_plan.load(std::memory_order_acquire));
+}
+
+static void AppendStringField(std::string* out, int number, const std::string& s) {
+    uint8_t head[16];
+    uint8_t* e = write_tag(head, number, WIRETYPE_LENGTH_DELIMITED);
+    e = write_varint(e, s.size());
+    out->append((const char*)head, e - head);
+    out->append(s);
+}
+
+const MethodWireNames* MethodDescriptor::BuildWireNames() const {
+    MethodWireNames* w = new MethodWireNames;
+    if (service) {
+        AppendStringField(&w->full, 1, service->full_name);
+        AppendStringField(&w->brief, 1, service->name);
+    } else {
+        AppendStringField(&w->full, 1, std::string());
+        AppendStringField(&w->brief, 1, std::string());
+    }
+    AppendStringField(&w->full, 2, name);
+    AppendStringField(&w->brief, 2, name);
+    return wire_names_cache.publish(w);
 }
 
 const char* FieldTypeName(FieldType t) {

@@ -140,6 +140,39 @@ private:
     std::map<std::string, int> _by_name;
 };
 
+// A method's two name fields as a baidu_std request meta carries them
+// (RpcRequestMeta.service_name = 1, method_name = 2), already encoded: once
+// with the service's full name and once with its short one.
+struct MethodWireNames {
+    std::string full;
+    std::string brief;
+};
+
+// Holder of a MethodDescriptor's MethodWireNames: built on first use,
+// published once, freed with the descriptor. A copied descriptor starts
+// without one (descriptors are copied only while they are being built).
+class MethodWireNamesCache {
+public:
+    MethodWireNamesCache() = default;
+    MethodWireNamesCache(const MethodWireNamesCache&) {}
+    MethodWireNamesCache& operator=(const MethodWireNamesCache&) {
+        delete _p.exchange(nullptr, std::memory_order_acq_rel);
+        return *this;
+    }
+    ~MethodWireNamesCache() { delete _p.load(std::memory_order_acquire); }
+    const MethodWireNames* get() const { return _p.load(std::memory_order_acquire); }
+    // Publishes `built` unless another thread got there first; returns the published one.
+    const MethodWireNames* publish(const MethodWireNames* built) const {
+        const MethodWireNames* expected = nullptr;
+        if (_p.compare_exchange_strong(expected, built, std::memory_order_acq_rel, std::memory_order_acquire)) return built;
+        delete built;
+        return expected;
+    }
+
+private:
+    mutable std::atomic<const MethodWireNames*> _p{nullptr};
+};
+
 class MethodDescriptor {
 public:
     std::string name;
@@ -153,6 +186,15 @@ public:
     bool client_streaming = false;
     bool server_streaming = false;
     std::map<std::string, std::string> options;  // e.g. "(brpc.method_timeout)"
+    MethodWireNamesCache wire_names_cache;
+    // The encoded name fields of this method (names and service must be final).
+    const MethodWireNames* wire_names() const {
+        const MethodWireNames* w = wire_names_cache.get();
+        return w ? w : BuildWireNames();
+    }
+
+private:
+    const MethodWireNames* BuildWireNames() const;
 };
 
 class ServiceDescriptor {

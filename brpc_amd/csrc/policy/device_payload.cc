@@ -118,6 +118,13 @@ bool plane_send(int peer, const Buf& piece, int64_t pos, DevicePayloads* descs) 
 
 }  // namespace
 
+bool AttachmentStaysInline(Socket* sock, const Buf& in, bool verify) {
+    if (in.empty()) return true;
+    const int prank = (!verify && sock && in.size() >= (size_t)FLAGS_rccl_min_bytes) ? sock->plane_rank() : -1;
+    const bool host_plane = prank >= 0 && gpu::rccl::Active() && gpu::rccl::HostMemory();
+    return in.all_host_accessible() && !host_plane;
+}
+
 int LendDeviceBlocks(Socket* sock, const Buf& in, const DeviceLendOptions& opt, Buf* host_out,
                      DevicePayloads* descs, std::string* err) {
     // the RCCL plane takes large payloads to a rank of our plane (never the

@@ -90,6 +90,10 @@ struct PackedPayloads {
 // is the inline host part; release descriptors that will not be pulled.
 int LendDeviceBlocks(Socket* sock, const Buf& in, const DeviceLendOptions& opt, Buf* host_out,
                      DevicePayloads* descs, std::string* err);
+// True if LendDeviceBlocks would do no more with `in` than append it to
+// *host_out: nothing to lend and nothing for the RCCL plane, so its message
+// needs no descriptors.
+bool AttachmentStaysInline(Socket* sock, const Buf& in, bool verify);
 // With `index`: the field table of the first payload that asked for pb_scan.
 int PullDeviceBlocks(Socket* sock, const DevicePayloads& descs, Buf* attachment, std::string* err,
                      DevicePayloadIndex* index = nullptr);

@@ -6,6 +6,7 @@
 #include <unistd.h>
 
 #include <cerrno>
+#include <cstring>
 #include <fstream>
 
 #include "base/flags.h"
@@ -124,6 +125,7 @@ int Server::AddServiceInternal(Service* s, bool is_builtin, ServiceOwnership own
         _methods[r.second].http_url = r.first;
         _restful.push_back(r);
     }
+    RebuildMethodIndex();
     return 0;
 }
 
@@ -150,6 +152,7 @@ int Server::RemoveService(Service* service) {
     if (_first_service == service) _first_service = nullptr;
     if (it->second.ownership == SERVER_OWNS_SERVICE) delete it->second.service;
     _services.erase(it);
+    RebuildMethodIndex();
     return 0;
 }
 
@@ -162,6 +165,7 @@ void Server::ClearServices() {
     _services_by_short_name.clear();
     _first_service = nullptr;
     _methods.clear();
+    _method_index.clear();
     _restful.clear();
 }
 
@@ -177,22 +181,43 @@ Service* Server::FindServiceByName(const std::string& name) const {
     return it == _services_by_short_name.end() ? nullptr : it->second;
 }
 
-const Server::MethodProperty* Server::FindMethodPropertyByFullName(const std::string& svc, const std::string& method) const {
+void Server::RebuildMethodIndex() {
+    _method_index.clear();
+    _method_index.reserve(_methods.size());
+    for (auto& kv : _methods) _method_index.emplace(std::string_view(kv.first), &kv.second);
+}
+
+// Looks "service.method" up. The key is put together on the stack (on the
+// heap only beyond kStackKey bytes), so a lookup allocates nothing.
+const Server::MethodProperty* Server::FindMethodByJoinedName(std::string_view svc, std::string_view method) const {
+    static const size_t kStackKey = 256;
+    const size_t n = svc.size() + 1 + method.size();
+    char stack_key[kStackKey];
+    std::string heap_key;
+    char* key = stack_key;
+    if (n > kStackKey) {
+        heap_key.resize(n);
+        key = &heap_key[0];
+    }
+    if (!svc.empty()) memcpy(key, svc.data(), svc.size());
+    key[svc.size()] = '.';
+    if (!method.empty()) memcpy(key + svc.size() + 1, method.data(), method.size());
+    auto it = _method_index.find(std::string_view(key, n));
+    return it == _method_index.end() ? nullptr : it->second;
+}
+
+const Server::MethodProperty* Server::FindMethodPropertyByFullName(std::string_view svc, std::string_view method) const {
     // The method map is immutable while running (only builtin services are
     // added before Start completes), so lookups are lock-free.
-    std::string key;
-    key.reserve(svc.size() + 1 + method.size());
-    key.append(svc).push_back('.');
-    key.append(method);
-    auto it = _methods.find(key);
-    if (it != _methods.end()) return &it->second;
+    if (const MethodProperty* mp = FindMethodByJoinedName(svc, method)) return mp;
     // allow short service names
     auto s = _services_by_short_name.find(svc);
-    if (s != _services_by_short_name.end()) {
-        it = _methods.find(s->second->GetDescriptor()->full_name + "." + method);
-        if (it != _methods.end()) return &it->second;
-    }
+    if (s != _services_by_short_name.end()) return FindMethodByJoinedName(s->second->GetDescriptor()->full_name, method);
     return nullptr;
+}
+
+const Server::MethodProperty* Server::FindMethodPropertyByFullName(const std::string& svc, const std::string& method) const {
+    return FindMethodPropertyByFullName(std::string_view(svc), std::string_view(method));
 }
 
 const Server::MethodProperty* Server::FindMethodPropertyByFullName(const std::string& full) const {

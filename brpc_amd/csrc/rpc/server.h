@@ -7,6 +7,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <string_view>
 #include <unordered_map>
 #include <vector>
 
@@ -101,6 +102,9 @@ public:
     const MethodProperty* FindMethodPropertyByFullName(const std::string& service_full_name,
                                                        const std::string& method_name) const;
     const MethodProperty* FindMethodPropertyByFullName(const std::string& full_method_name) const;
+    // The same lookup for names that are views of received bytes: no key
+    // string is built. The std::string overloads go through it.
+    const MethodProperty* FindMethodPropertyByFullName(std::string_view service_name, std::string_view method_name) const;
     // ServerOptions.http_master_service's method (nullptr when unset).
     const MethodProperty* master_method_property() const { return _master_mp; }
     // restful lookup: returns property and fills unresolved path
@@ -168,9 +172,14 @@ private:
     std::unique_ptr<Acceptor> _internal_am;
     std::shared_ptr<SslContext> _ssl_ctx;  // TLS contexts of the listening port (SNI)
     std::map<std::string, ServiceProperty> _services;           // full name
-    std::map<std::string, Service*> _services_by_short_name;
+    std::map<std::string, Service*, std::less<>> _services_by_short_name;
     Service* _first_service = nullptr;
     std::unordered_map<std::string, MethodProperty> _methods;  // "svc.Method"
+    // _methods by views of its own keys, for lookups whose key is no
+    // std::string; rebuilt by whatever changes _methods
+    std::unordered_map<std::string_view, const MethodProperty*> _method_index;
+    void RebuildMethodIndex();
+    const MethodProperty* FindMethodByJoinedName(std::string_view service_name, std::string_view method_name) const;
     std::vector<std::pair<std::string, std::string>> _restful;  // prefix -> full method name
     const MethodProperty* _master_mp = nullptr;
     // every request of every connection adds and removes itself here: on a
