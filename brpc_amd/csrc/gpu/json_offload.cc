@@ -16,6 +16,7 @@
 
 #include "base/decimal_to_double.h"
 #include "base/flags.h"
+#include "base/json_records.h"
 #include "base/number_print.h"
 #include "base/shortest_double.h"
 #include "base/time.h"
@@ -320,6 +321,230 @@ int DevicePrintNumbers(DeviceNumberPrintJob* jobs, int n, int device) {
     return 0;
 }
 
+namespace {
+
+std::atomic<int64_t> g_record_print_jobs{0}, g_record_print_rows{0};
+
+static_assert(kJsonRecordNumber == json_records::kNumber && kJsonRecordString == json_records::kString &&
+                  kJsonRecordBase64 == json_records::kBase64,
+              "one numbering of the text forms");
+
+// The job as the rules see it (cols: room for kMaxColumns); false when it
+// has no column table to look at.
+bool record_print_view(const DeviceRecordPrintJob& j, json_records::Column* cols, json_records::Job* out) {
+    if (!j.columns || j.ncols < 1 || j.ncols > json_records::kMaxColumns) return false;
+    for (uint32_t c = 0; c < j.ncols; ++c) {
+        const DeviceRecordPrintColumn& in = j.columns[c];
+        cols[c].key = in.key;
+        cols[c].key_len = in.key_len;
+        cols[c].kind = in.kind;
+        cols[c].text = in.text;
+        cols[c].src = in.src;
+        cols[c].count = in.count;
+        cols[c].row_ends = in.row_ends;
+    }
+    out->columns = cols;
+    out->ncols = j.ncols;
+    out->rows = j.rows;
+    out->brackets = j.brackets;
+    return true;
+}
+
+// The job's key prefixes and its worst case (json_records::WorstCaseBytes);
+// false for a job the rules refuse.
+bool record_print_worst(const DeviceRecordPrintJob& j, std::vector<std::string>* prefixes, uint64_t* worst) {
+    namespace jr = json_records;
+    jr::Column cols[jr::kMaxColumns];
+    jr::Job view;
+    if (!record_print_view(j, cols, &view) || !jr::FieldsOk(view) || !json::RecordObjectPrefixes(view, prefixes))
+        return false;
+    uint64_t prefix_bytes = 0;
+    for (const std::string& p : *prefixes) prefix_bytes += p.size();
+    *worst = jr::WorstCaseBytes(view, prefix_bytes);
+    return true;
+}
+
+// Everything the host can say about a job without reading device memory; the
+// prefixes and the worst case come back for a job that passes.
+bool record_print_ok(const DeviceRecordPrintJob& j, std::vector<std::string>* prefixes, uint64_t* worst) {
+    namespace jr = json_records;
+    if (!record_print_worst(j, prefixes, worst) || *worst > 0xFFFFFFFFull || (!j.dst && j.cap > 0)) return false;
+    // a cap above the worst case can claim no more of dst than that
+    const uint64_t reach = j.cap < *worst ? j.cap : *worst;
+    auto overlaps = [](const void* a, uint64_t an, const void* b, uint64_t bn) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return an > 0 && bn > 0 && x < y + bn && y < x + an;
+    };
+    for (uint32_t c = 0; c < j.ncols; ++c) {
+        const DeviceRecordPrintColumn& col = j.columns[c];
+        const uint64_t eb = jr::ElemBytes(col.kind);
+        if ((!col.src && col.count > 0) || ((uintptr_t)col.src & (eb - 1)) != 0 || ((uintptr_t)col.row_ends & 3) != 0 ||
+            overlaps(j.dst, reach, col.src, col.count * eb) || overlaps(j.dst, reach, col.row_ends, j.rows * 4))
+            return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+uint64_t RecordObjectsWorstCaseBytes(const DeviceRecordPrintJob& job) {
+    std::vector<std::string> prefixes;
+    uint64_t worst = 0;
+    return record_print_worst(job, &prefixes, &worst) ? worst : 0;
+}
+
+uint32_t JsonRecordsChunkElems() { return kJsonRecordsChunkElems; }
+uint32_t JsonRecordsBlockRows() { return kJsonRecordsBlockRows; }
+
+int DevicePrintRecordObjects(DeviceRecordPrintJob* jobs, int n, int device) {
+    namespace jr = json_records;
+    namespace np = number_print;
+    if (n <= 0) return 0;
+    if (!jobs || device < 0) return -1;
+    std::vector<int> live;   // the jobs that go to the device, in order
+    std::vector<int> empty;  // those of no row that get "[]"
+    std::vector<std::vector<std::string>> prefixes((size_t)n);
+    uint64_t nchunks = 0, nrblocks = 0, ngroups = 0, nrows = 0, ncolrows = 0, ncols = 0, nelems = 0, ndigits = 0;
+    for (int i = 0; i < n; ++i) {
+        DeviceRecordPrintJob& j = jobs[i];
+        j.len = 0;
+        j.first_bad = j.bad_column = jr::kNone;
+        j.err = 0;
+        uint64_t worst = 0;
+        if (!record_print_ok(j, &prefixes[i], &worst)) {
+            j.err = 2;
+            continue;
+        }
+        if (j.rows == 0) {
+            j.len = worst;  // 2 or 0
+            if (j.len > j.cap) j.err = 3;
+            else if (j.len) empty.push_back(i);
+            continue;
+        }
+        for (uint32_t c = 0; c < j.ncols; ++c) {
+            const DeviceRecordPrintColumn& col = j.columns[c];
+            nchunks += (col.count + kJsonRecordsChunkElems - 1) / kJsonRecordsChunkElems;
+            if (col.text != jr::kBase64) {
+                ngroups += col.count / kJsonRecordsGroupElems + 1;
+                nelems += col.count;
+            }
+            if (np::KindIsFloat(col.kind)) ndigits += col.count;
+        }
+        nrblocks += (j.rows + kJsonRecordsBlockRows - 1) / kJsonRecordsBlockRows;
+        nrows += j.rows;
+        ncolrows += j.rows * j.ncols;
+        ncols += j.ncols;
+        live.push_back(i);
+    }
+    if (live.empty() && empty.empty()) return 0;
+    // one grid per pass, 32-bit table indices
+    if (nchunks > 0x7FFFFFFFull || nrblocks > 0x7FFFFFFFull || ngroups > 0x7FFFFFFFull || ncolrows > 0x7FFFFFFFull ||
+        nelems > 0x7FFFFFFFull) {
+        return -1;
+    }
+    const size_t nlive = live.size();
+    // the most aligned first: digits are 16-byte, jobs, columns and offender words 8-byte
+    const size_t jobs_bytes = nlive * sizeof(JsonRecordsJob), cols_bytes = (size_t)ncols * sizeof(JsonRecordsColumn);
+    const size_t prefix_bytes = (size_t)ncols * kJsonRecordsPrefixStride;
+    PinnedBlock tables(jobs_bytes + cols_bytes + nlive * sizeof(JsonRecordsResult) + prefix_bytes + 4);
+    const size_t digits_bytes = (size_t)ndigits * sizeof(shortest_double::Decimal);
+    const size_t words = (size_t)ngroups + (size_t)nrows + 2 * (size_t)ncolrows + (size_t)nrblocks + nlive;
+    HbmBlock scratch(digits_bytes + jobs_bytes + cols_bytes + nlive * sizeof(uint64_t) + words * sizeof(uint32_t) +
+                         prefix_bytes + (size_t)nelems * sizeof(uint16_t) + 16,
+                     device);
+    if (!tables || !scratch) return -1;
+    JsonRecordsJob* tj = tables.as<JsonRecordsJob>();
+    JsonRecordsColumn* tc = reinterpret_cast<JsonRecordsColumn*>(tj + nlive);
+    JsonRecordsResult* tr = reinterpret_cast<JsonRecordsResult*>(tc + ncols);
+    uint8_t* tp = reinterpret_cast<uint8_t*>(tr + nlive);
+    char* two = reinterpret_cast<char*>(tp + prefix_bytes);  // "[]" for the jobs of no row
+    two[0] = '[';
+    two[1] = ']';
+    memset(tp, 0, prefix_bytes);
+    JsonRecordsTables t;
+    for (size_t k = 0; k < nlive; ++k) {
+        const DeviceRecordPrintJob& j = jobs[live[k]];
+        JsonRecordsJob& o = tj[k];
+        o.dst = static_cast<uint8_t*>(j.dst);
+        o.cap = j.cap;
+        o.rows = (uint32_t)j.rows;
+        o.brackets = j.brackets ? 1 : 0;
+        o.ncols = j.ncols;
+        o.first_col = (uint32_t)t.ncols;
+        o.first_rblock = t.nrblocks;
+        o.first_row = t.nrows;
+        o.fixed = 1;  // '}'
+        o.pad = 0;
+        for (uint32_t c = 0; c < o.ncols; ++c) {
+            const DeviceRecordPrintColumn& in = j.columns[c];
+            const std::string& prefix = prefixes[live[k]][c];
+            memcpy(tp + (size_t)t.ncols * kJsonRecordsPrefixStride, prefix.data(), prefix.size());
+            o.fixed += (uint32_t)prefix.size();
+            JsonRecordsColumn& col = tc[t.ncols++];
+            col.src = in.src;
+            col.row_ends = in.row_ends;
+            col.count = (uint32_t)in.count;
+            col.kind = in.kind;
+            col.text = in.text;
+            col.job = (uint32_t)k;
+            col.first_chunk = t.nchunks;
+            col.nchunks = (uint32_t)((in.count + kJsonRecordsChunkElems - 1) / kJsonRecordsChunkElems);
+            col.first_row = t.ncolrows;
+            col.first_group = t.ngroups;
+            col.first_elem = t.nelems;
+            col.first_digit = t.ndigits;
+            col.prefix_len = (uint32_t)prefix.size();
+            col.pad = 0;
+            t.nchunks += col.nchunks;
+            t.ncolrows += o.rows;
+            if (in.text != jr::kBase64) {
+                t.ngroups += col.count / kJsonRecordsGroupElems + 1;
+                t.nelems += col.count;
+            }
+            if (np::KindIsFloat(in.kind)) t.ndigits += col.count;
+        }
+        t.nrblocks += (uint32_t)((j.rows + kJsonRecordsBlockRows - 1) / kJsonRecordsBlockRows);
+        t.nrows += o.rows;
+        tr[k] = JsonRecordsResult{0, jr::kNone, jr::kNone, 0};
+    }
+    t.jobs = tj;
+    t.njobs = (int)nlive;
+    t.cols = tc;
+    t.prefixes = tp;
+    t.digits = scratch.p;
+    t.jobs_dev = reinterpret_cast<JsonRecordsJob*>(static_cast<char*>(scratch.p) + digits_bytes);
+    t.cols_dev = reinterpret_cast<JsonRecordsColumn*>(t.jobs_dev + nlive);
+    t.bad = reinterpret_cast<unsigned long long*>(t.cols_dev + t.ncols);
+    t.groups = reinterpret_cast<uint32_t*>(t.bad + nlive);
+    t.row_size = t.groups + t.ngroups;
+    t.col_cell = t.row_size + t.nrows;
+    t.col_delta = t.col_cell + t.ncolrows;
+    t.block_off = t.col_delta + t.ncolrows;
+    t.prefixes_dev = reinterpret_cast<uint8_t*>(t.block_off + t.nrblocks + nlive);
+    t.elem_incl = reinterpret_cast<uint16_t*>(t.prefixes_dev + prefix_bytes);
+    t.res = tr;
+    const int rc = RunOnPoolStream(device, [&](hipStream_t s) {
+        for (int i : empty) {
+            if (hipMemcpyAsync(jobs[i].dst, two, 2, hipMemcpyDefault, s) != hipSuccess) return -1;
+        }
+        return LaunchJsonRecordsPrint(t, s);
+    });
+    if (rc != 0) return -1;
+    for (size_t k = 0; k < nlive; ++k) {
+        DeviceRecordPrintJob& j = jobs[live[k]];
+        j.len = tr[k].len;
+        j.err = tr[k].err;
+        if (j.err == 1) {
+            j.first_bad = tr[k].first_bad;
+            j.bad_column = tr[k].bad_column;
+        }
+        if (j.err) continue;
+        g_record_print_jobs.fetch_add(1, std::memory_order_relaxed);
+        g_record_print_rows.fetch_add((int64_t)j.rows, std::memory_order_relaxed);
+    }
+    return 0;
+}
+
 int DeviceParseNumberArrays(DeviceNumberParseJob* jobs, int n, int device) {
     if (n <= 0) return 0;
     if (!jobs || device < 0) return -1;
@@ -619,6 +844,8 @@ GpuJsonStats GetGpuJsonStats() {
     s.number_elems = g_number_elems.load();
     s.number_array_fallbacks = g_number_array_fallbacks.load();
     s.number_redo_elems = g_number_redo_elems.load();
+    s.record_print_jobs = g_record_print_jobs.load();
+    s.record_print_rows = g_record_print_rows.load();
     return s;
 }
 

@@ -205,7 +205,69 @@ int DevicePrintNumbers(DeviceNumberPrintJob* jobs, int n, int device);
 // Elements one workgroup takes, and rows (tests aim at its edges).
 uint32_t JsonNumberPrintChunkElems();
 
+// ---- records as JSON objects: the columns DeviceSplitRecords gives (or
+// DeviceBuildRecords takes), each with a key, become
+//   [{"k0":cell,"k1":cell,...},{...},...]
+// in device memory, the shape http+json model APIs return. Every key appears
+// in every record, in column order; nothing is omitted (this is not pb2json's
+// omission rule). No whitespace; without brackets the records are only joined
+// by ','. The cell of record r:
+//   kinds 0..6, 8, 9 without row_ends (count == rows)   element r, as DevicePrintNumbers prints it
+//   the same kinds with row_ends                        [v,v,...,v], [] for a row of no element
+//   kind 7 with row_ends, text kJsonRecordString        the row's bytes as DeviceEscapeJsonStrings escapes them, quoted
+//   kind 7 with row_ends, text kJsonRecordBase64        the row as padded base64, quoted
+// Empty rows are legal. base/json_records.h has the rules,
+// json::FormatRecordObjects is the host twin: the same bytes, the same codes.
+constexpr uint32_t kJsonRecordNumber = 0, kJsonRecordString = 1, kJsonRecordBase64 = 2;  // json_records::Text
+struct DeviceRecordPrintColumn {
+    const void* key = nullptr;  // host memory, key_len raw bytes; escaped once per job
+    uint32_t key_len = 0;
+    uint32_t kind = 0;
+    uint32_t text = kJsonRecordNumber;
+    const void* src = nullptr;  // device or pinned host; naturally aligned (1 / 4 / 8 bytes)
+    uint64_t count = 0;         // elements (bytes for kind 7)
+    const uint32_t* row_ends = nullptr;  // device or pinned host, `rows` entries, 4-byte aligned; null: a scalar column
+};
+struct DeviceRecordPrintJob {
+    const DeviceRecordPrintColumn* columns = nullptr;
+    uint32_t ncols = 0;  // 1 .. 8
+    uint64_t rows = 0;
+    bool brackets = false;
+    void* dst = nullptr;  // device-writable, cap bytes, any alignment
+    uint64_t cap = 0;
+    uint64_t len = 0;  // out: text size (with err 3: the size it needs; 0 with err 1)
+    // out, with err 1: the lowest row whose end lies below its predecessor or
+    // above count, or is the last and not count, over all columns, and the
+    // lowest column that offends there. Found on the device.
+    uint32_t first_bad = 0xFFFFFFFFu, bad_column = 0xFFFFFFFFu;
+    // out: 0 printed; 1 a bad table (dst untouched); 2 refused before any
+    // launch (a null pointer with a nonzero size, a misaligned src or
+    // row_ends, a kind or text form there is not, kind 7 without row_ends, a
+    // text form on a number kind, ncols 0 or above 8, a scalar column whose
+    // count is not rows, a key whose escaped form is above 255 bytes, two
+    // equal keys, a dst that overlaps a source or a table, a worst case above
+    // 2^32 - 1); 3 longer than cap (dst untouched); 4 a source or table
+    // changed between the passes (nothing of that chunk is written). 1 wins
+    // over 3.
+    int err = 0;
+};
+// Most bytes the job's text can take for any values and tables (dst and cap
+// are not looked at); always suffices as a cap. 0 for a job that is refused,
+// ~0 when it is above 2^32 - 1.
+uint64_t RecordObjectsWorstCaseBytes(const DeviceRecordPrintJob& job);
+// All jobs share one launch sequence (init, size, prefix, measure, prefix,
+// heads, place: kernels.h) on a pool stream and one fiber-friendly wait; the
+// host reads no table and no value, only the result words. Returns -1 only on
+// a device error; per-job codes in jobs[i].err. A job of no row launches
+// nothing: its text is "[]" (copied to dst) or nothing.
+int DevicePrintRecordObjects(DeviceRecordPrintJob* jobs, int n, int device);
+// Elements one workgroup of the element passes takes, and records one of the
+// record passes takes (tests aim at their edges).
+uint32_t JsonRecordsChunkElems();
+uint32_t JsonRecordsBlockRows();
+
 struct GpuJsonStats {
+    int64_t record_print_jobs = 0, record_print_rows = 0;  // DevicePrintRecordObjects: jobs and records printed
     // json2pb number arrays (floats) parsed on the device; fallbacks: arrays the device declined
     int64_t number_arrays = 0, number_elems = 0, number_array_fallbacks = 0, number_redo_elems = 0;
     int64_t indexed_bodies = 0, indexed_bytes = 0, failures = 0;

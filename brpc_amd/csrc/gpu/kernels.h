@@ -756,6 +756,116 @@ struct JsonNumberPrintTables {
 };
 int LaunchJsonNumberPrint(const JsonNumberPrintTables& t, hipStream_t s);
 
+// Records as JSON objects (gpu/json_records_kernels.hip): the columns of the
+// record builder, each with a key, become [{"k0":cell,"k1":cell,...},...] in
+// device memory (base/json_records.h has the rules, json::FormatRecordObjects
+// is the host twin). The shape is the record builder's and easier: a key
+// prefix does not depend on what follows it. A column is cut into chunks of
+// kJsonRecordsChunkElems elements (a string column's element is a byte) and
+// into groups of 64, a wave each; records are taken 256 to a workgroup. All
+// jobs share seven launches on one stream, ordered by the launches alone:
+//   init     copies the job and column tables and the key prefixes to device
+//            memory, resets each job's offender word and zeroes the group
+//            behind each column's last element
+//   size     number and string columns (a base64 cell follows from the row
+//            length alone): a lane per element, a grid over the chunks of
+//            every column of every job. A wave scans the text lengths of its
+//            group: elem_incl[e] becomes the text bytes of the group's
+//            elements up to and including e (two bytes: a group holds at most
+//            64 * 25), groups[] the group's sum, and a float's digits are kept
+//            as a 16-byte Decimal so that no later pass formats it again
+//   prefix   LaunchPbRunPrefix over groups[]. The text before element e is
+//            then its group's prefix plus elem_incl[e - 1] inside the group:
+//            two loads, no walk
+//   measure  a lane per record: a cell's inner bytes are the difference of two
+//            such texts plus the commas between a number row's elements (a
+//            base64 cell: 4 * ceil(len / 3)), into col_cell[]; the text before
+//            the row's first element goes into col_delta[]. The record's size
+//            with the punctuation in front of and behind it goes into
+//            row_size[], the workgroup's sum into block_off[]. A bad table
+//            goes into bad[] through one atomic min on row << 4 | column
+//   prefix   LaunchPbRunPrefix over block_off[]: an entry per 256 records and
+//            one per job for its total
+//   heads    a lane per record: row 0's lane writes the job's result; a job
+//            with a bad table (err 1) or longer than its cap (err 3) gets
+//            nothing written here or later. Else the record's offset is its
+//            block's plus a scan inside the workgroup; the lane writes the ','
+//            or '[' in front, every key prefix, every cell's opening and
+//            closing [ ] or " ", the '}' and the outer ']' (an empty cell is
+//            complete with that), and col_delta[] becomes the distance from
+//            "text before element e" to "offset of element e in dst"
+//   place    a lane per element, a workgroup per chunk of every column. The
+//            rows that meet the chunk lie between two lower-bound searches of
+//            row_ends that are the same in every lane; a lane finds its own
+//            row between them. It stores its element's text at the column's
+//            delta, and the ',' in front of an element that does not start a
+//            row; a base64 column stores the four symbols of the group that
+//            begins at each row offset divisible by 3. A chunk with an
+//            element whose text is not the size measured, or with a store
+//            that would leave the text, writes nothing and marks err 4
+// No workgroup waits for another; a record's lane does work bounded by the
+// column count and the longest prefix, an element's lane by the logarithm of
+// the rows; every store is compared with the job's size, which is at most
+// its cap. The job and column tables and the prefixes are device-readable
+// (pinned host) arrays, res a device-writable one; the rest is device memory.
+constexpr uint32_t kJsonRecordsChunkElems = 256;
+constexpr uint32_t kJsonRecordsGroupElems = 64;
+constexpr uint32_t kJsonRecordsBlockRows = 256;
+constexpr uint32_t kJsonRecordsPrefixStride = 260;  // json_records::kMaxPrefixBytes, in whole words
+struct JsonRecordsColumn {
+    const void* src;           // count elements, naturally aligned
+    const uint32_t* row_ends;  // rows entries; null for a scalar column (count == rows)
+    uint32_t count;
+    uint32_t kind, text;       // number_print::Kind or 7; json_records::Text
+    uint32_t job;              // its record job
+    uint32_t first_chunk, nchunks;  // nchunks = ceil(count / kJsonRecordsChunkElems); over all columns of all jobs
+    uint32_t first_row;        // in col_cell and col_delta: rows entries
+    uint32_t first_group;      // in groups: count / 64 + 1 entries (not for base64)
+    uint32_t first_elem;       // in elem_incl: count entries (not for base64)
+    uint32_t first_digit;      // in digits: count entries (float kinds only)
+    uint32_t prefix_len;       // of its kJsonRecordsPrefixStride bytes in the prefix table
+    uint32_t pad;
+};
+struct JsonRecordsJob {
+    uint8_t* dst;  // any alignment; null only with cap 0
+    uint64_t cap;
+    uint32_t rows;  // >= 1
+    uint32_t brackets;
+    uint32_t ncols, first_col;
+    uint32_t first_rblock;  // ceil(rows / kJsonRecordsBlockRows) row blocks; job k's entries of block_off start at
+                            // first_rblock + k (its blocks, then one entry for its total)
+    uint32_t first_row;     // in row_size
+    uint32_t fixed;         // per record: the prefixes and '}'
+    uint32_t pad;
+};
+struct JsonRecordsResult {
+    uint64_t len;         // text size (also when it did not fit)
+    uint32_t first_bad;   // with err 1
+    uint32_t bad_column;  // with err 1
+    int32_t err;          // 0, 1, 3, 4
+};
+struct JsonRecordsTables {
+    const JsonRecordsJob* jobs = nullptr;
+    int njobs = 0;
+    const JsonRecordsColumn* cols = nullptr;
+    int ncols = 0;                           // of all jobs
+    const uint8_t* prefixes = nullptr;       // ncols * kJsonRecordsPrefixStride, 4-byte aligned
+    JsonRecordsJob* jobs_dev = nullptr;      // njobs
+    JsonRecordsColumn* cols_dev = nullptr;   // ncols
+    uint8_t* prefixes_dev = nullptr;         // ncols * kJsonRecordsPrefixStride, 4-byte aligned
+    uint32_t nchunks = 0, nrblocks = 0, ngroups = 0, nrows = 0, ncolrows = 0, nelems = 0, ndigits = 0;  // of all jobs
+    uint32_t* groups = nullptr;          // ngroups
+    uint16_t* elem_incl = nullptr;       // nelems
+    void* digits = nullptr;              // ndigits * 16 bytes, 16-byte aligned
+    uint32_t* row_size = nullptr;        // nrows
+    uint32_t* col_cell = nullptr;        // ncolrows
+    uint32_t* col_delta = nullptr;       // ncolrows
+    uint32_t* block_off = nullptr;       // nrblocks + njobs
+    unsigned long long* bad = nullptr;   // njobs
+    JsonRecordsResult* res = nullptr;    // njobs
+};
+int LaunchJsonRecordsPrint(const JsonRecordsTables& t, hipStream_t s);
+
 // JSON structural index (gpu/json_kernels.hip): out_pos receives, in order,
 // the byte offsets of every unescaped '"' and of every { } [ ] : , outside
 // strings; count_dev the number found (positions past max_out are dropped

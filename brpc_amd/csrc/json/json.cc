@@ -12,6 +12,7 @@
 
 #include "base/base64_rows.h"
 #include "base/decimal_to_double.h"
+#include "base/json_records.h"
 #include "base/json_string.h"
 #include "base/json_string_rows.h"
 #include "base/number_print.h"
@@ -699,6 +700,88 @@ int FormatNumberRows(const void* values, uint64_t count, uint32_t kind, const ui
         used = (size_t)(o - out->data());
     }
     out->resize(used);
+    return 0;
+}
+
+bool RecordObjectPrefixes(const json_records::Job& job, std::vector<std::string>* prefixes) {
+    namespace jr = json_records;
+    prefixes->clear();
+    if (!job.columns || job.ncols < 1 || job.ncols > jr::kMaxColumns) return false;
+    for (uint32_t c = 0; c < job.ncols; ++c) {
+        const jr::Column& col = job.columns[c];
+        if (!col.key && col.key_len > 0) return false;
+        for (uint32_t d = 0; d < c; ++d) {
+            const jr::Column& other = job.columns[d];
+            if (other.key_len == col.key_len && (col.key_len == 0 || memcmp(other.key, col.key, col.key_len) == 0))
+                return false;
+        }
+        std::string escaped;
+        EscapeStringBody(static_cast<const char*>(col.key), col.key_len, &escaped);
+        if (escaped.size() > jr::kMaxEscapedKey) return false;
+        uint8_t buf[jr::kMaxPrefixBytes];
+        const uint32_t n = jr::PutPrefix(c, escaped.data(), (uint32_t)escaped.size(), buf);
+        prefixes->emplace_back(reinterpret_cast<const char*>(buf), n);
+    }
+    return true;
+}
+
+int FormatRecordObjects(const json_records::Job& job, std::string* out, uint32_t* first_bad, uint32_t* bad_column) {
+    namespace jr = json_records;
+    if (first_bad) *first_bad = jr::kNone;
+    if (bad_column) *bad_column = jr::kNone;
+    std::vector<std::string> prefixes;
+    if (!jr::FieldsOk(job) || !RecordObjectPrefixes(job, &prefixes)) return 2;
+    uint64_t prefix_bytes = 0;
+    for (const std::string& p : prefixes) prefix_bytes += p.size();
+    if (jr::WorstCaseBytes(job, prefix_bytes) > 0xFFFFFFFFull) return 2;
+    for (uint32_t c = 0; c < job.ncols; ++c) {
+        const jr::Column& col = job.columns[c];
+        if ((!col.src && col.count > 0) || ((uintptr_t)col.src & (jr::ElemBytes(col.kind) - 1)) != 0 ||
+            ((uintptr_t)col.row_ends & 3) != 0)
+            return 2;
+    }
+    if (job.rows == 0) {
+        if (job.brackets) out->append("[]");
+        return 0;
+    }
+    const size_t before = out->size();
+    char num[number_print::kMaxElemChars];
+    for (uint64_t r = 0; r < job.rows; ++r) {  // in row order, columns inside: the first offender is the lowest
+        if (jr::LeadBytes(r, job.brackets)) out->push_back(r > 0 ? ',' : '[');
+        for (uint32_t c = 0; c < job.ncols; ++c) {
+            const jr::Column& col = job.columns[c];
+            out->append(prefixes[c]);
+            if (!col.row_ends) {
+                out->append(num, jr::FormatElem(col.src, r, col.kind, num));
+                continue;
+            }
+            const uint32_t s = r ? col.row_ends[r - 1] : 0u, e = col.row_ends[r];
+            if (jr::RowEndBad(s, e, r, job.rows, col.count)) {
+                out->resize(before);
+                if (first_bad) *first_bad = (uint32_t)r;
+                if (bad_column) *bad_column = c;
+                return 1;
+            }
+            if (col.text == jr::kBase64) {
+                out->push_back('"');
+                for (uint32_t k = 0; k < e - s; k += 3) {
+                    const uint32_t sym = jr::Base64Group(static_cast<const uint8_t*>(col.src) + s, k, e - s);
+                    for (int b = 0; b < 4; ++b) out->push_back((char)(sym >> (8 * b)));
+                }
+                out->push_back('"');
+                continue;
+            }
+            const bool str = col.text == jr::kString;
+            out->push_back(str ? '"' : '[');
+            for (uint32_t i = s; i < e; ++i) {
+                if (!str && i > s) out->push_back(',');
+                out->append(num, jr::FormatElem(col.src, i, col.kind, num));
+            }
+            out->push_back(str ? '"' : ']');
+        }
+        out->push_back('}');
+        if (jr::TrailBytes(r, job.rows, job.brackets)) out->push_back(']');
+    }
     return 0;
 }
 

@@ -11,6 +11,9 @@
 #include <vector>
 
 namespace mrpc {
+namespace json_records {
+struct Job;  // base/json_records.h
+}
 namespace json {
 
 class Value {
@@ -287,6 +290,23 @@ bool EncodeBase64Rows(const char* bytes, const uint32_t* row_ends, size_t rows, 
 // not decided here (json::Reader and base64_decode are laxer): first_bad is
 // set, everything else empty and 0. One sequential walk.
 int DecodeBase64Rows(const char* text, size_t n, StringRows* out);
+// The host twin of gpu::DevicePrintRecordObjects (gpu/json_offload.h): the
+// job's columns as [{"k0":cell,"k1":cell,...},...] appended to *out, every key
+// in every record (this is not pb2json's omission rule), no whitespace; without
+// brackets the records are only joined by ','. No row: "[]" or nothing. The
+// rules are base/json_records.h for both; one sequential walk. Returns the
+// device's codes: 0 printed; 1 a bad table of row ends, *first_bad the lowest
+// offending row over all columns and *bad_column the lowest column that
+// offends there; 2 refused (a column count, kind, text form or shape there is
+// not, a null or misaligned source, a key whose escaped form is above 255
+// bytes, two equal keys, a worst case above 2^32 - 1). Nothing is appended on
+// a code other than 0.
+int FormatRecordObjects(const json_records::Job& job, std::string* out, uint32_t* first_bad = nullptr,
+                        uint32_t* bad_column = nullptr);
+// The fixed per-column prefixes of such a job ({"k": for column 0, ,"k":
+// behind it), the keys escaped with EscapeStringBody. False when a key is
+// missing, its escaped form is above 255 bytes, or two keys are equal.
+bool RecordObjectPrefixes(const json_records::Job& job, std::vector<std::string>* prefixes);
 // The first offset at which no well-formed UTF-8 sequence starts on the walk
 // from 0 (what Python reports as UnicodeDecodeError.start), n when the text
 // is well-formed.

@@ -89,6 +89,27 @@ typedef std::tuple<uint32_t, std::vector<RecordColumnRow>, uint64_t, uintptr_t, 
 // msg, n, row_cap) rows of device_split_records
 typedef std::tuple<uint32_t, uint32_t, bool, uintptr_t, uint64_t, uintptr_t> RecordSplitColumnRow;
 typedef std::tuple<uint32_t, std::vector<RecordSplitColumnRow>, uintptr_t, uint64_t, uint64_t> RecordsSplitJobRow;
+// (key, kind, text form, src, count, row_ends) columns and (columns, rows,
+// brackets, dst, cap) rows of device_json_print_records
+typedef std::tuple<py::bytes, uint32_t, uint32_t, uintptr_t, uint64_t, uintptr_t> RecordPrintColumnRow;
+typedef std::tuple<std::vector<RecordPrintColumnRow>, uint64_t, bool, uintptr_t, uint64_t> RecordPrintJobRow;
+// the keys are copied to *keys, which must outlive the columns
+std::vector<gpu::DeviceRecordPrintColumn> record_print_columns(const std::vector<RecordPrintColumnRow>& rows,
+                                                               std::vector<std::string>* keys) {
+    std::vector<gpu::DeviceRecordPrintColumn> cs(rows.size());
+    keys->resize(rows.size());
+    for (size_t i = 0; i < rows.size(); ++i) {
+        (*keys)[i] = std::get<0>(rows[i]);
+        cs[i].key = (*keys)[i].data();
+        cs[i].key_len = (uint32_t)(*keys)[i].size();
+        cs[i].kind = std::get<1>(rows[i]);
+        cs[i].text = std::get<2>(rows[i]);
+        cs[i].src = (const void*)std::get<3>(rows[i]);
+        cs[i].count = std::get<4>(rows[i]);
+        cs[i].row_ends = (const uint32_t*)std::get<5>(rows[i]);
+    }
+    return cs;
+}
 std::vector<gpu::DeviceMessageField> message_fields(const std::vector<MessageFieldRow>& rows) {
     std::vector<gpu::DeviceMessageField> fs(rows.size());
     for (size_t i = 0; i < rows.size(); ++i) {
@@ -524,6 +545,47 @@ void bind_gpu_ops(py::module_& g) {
     g.def("json_number_print_worst_case", &gpu::NumberPrintWorstCaseBytes, py::arg("kind"), py::arg("count"),
           py::arg("rows") = 0);
     g.def("json_number_print_chunk_elems", &gpu::JsonNumberPrintChunkElems);
+    // Records as JSON objects: table = [([(key, kind, text_form, src, count,
+    // row_ends)], rows, brackets, dst, cap)], key raw bytes, text_form 0 (a
+    // number kind), 1 (string) or 2 (base64), src / row_ends / dst device
+    // pointers, row_ends 0 for a scalar column -> [(len, err, first_bad,
+    // bad_column)] (gpu::DevicePrintRecordObjects; all jobs share one launch
+    // sequence).
+    g.def("device_json_print_records", [](const std::vector<RecordPrintJobRow>& table, int device) {
+        std::vector<gpu::DeviceRecordPrintJob> js(table.size());
+        std::vector<std::vector<std::string>> keys(table.size());
+        std::vector<std::vector<gpu::DeviceRecordPrintColumn>> cols(table.size());
+        for (size_t i = 0; i < table.size(); ++i) {
+            cols[i] = record_print_columns(std::get<0>(table[i]), &keys[i]);
+            js[i].columns = cols[i].data();
+            js[i].ncols = (uint32_t)cols[i].size();
+            js[i].rows = std::get<1>(table[i]);
+            js[i].brackets = std::get<2>(table[i]);
+            js[i].dst = (void*)std::get<3>(table[i]);
+            js[i].cap = std::get<4>(table[i]);
+        }
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = gpu::DevicePrintRecordObjects(js.data(), (int)js.size(), device);
+        }
+        check(rc, "device_json_print_records");
+        py::list out;
+        for (const gpu::DeviceRecordPrintJob& j : js) out.append(py::make_tuple(j.len, j.err, j.first_bad, j.bad_column));
+        return out;
+    }, py::arg("table"), py::arg("device") = 0);
+    g.def("json_records_worst_case", [](const std::vector<RecordPrintColumnRow>& columns, uint64_t rows, bool brackets) {
+        std::vector<std::string> keys;
+        const std::vector<gpu::DeviceRecordPrintColumn> cols = record_print_columns(columns, &keys);
+        gpu::DeviceRecordPrintJob j;
+        j.columns = cols.data();
+        j.ncols = (uint32_t)cols.size();
+        j.rows = rows;
+        j.brackets = brackets;
+        return gpu::RecordObjectsWorstCaseBytes(j);
+    }, py::arg("columns"), py::arg("rows"), py::arg("brackets") = true);
+    g.def("json_records_chunk_elems", &gpu::JsonRecordsChunkElems);
+    g.def("json_records_block_rows", &gpu::JsonRecordsBlockRows);
     // Host floats / doubles (their memory image) -> the same text through the
     // device (gpu::PrintFloatsOnDevice: pinned stage, one wait).
     g.def("json_print_floats", [](py::bytes values, uint64_t n, uint32_t kind, int device) {

@@ -9,6 +9,7 @@
 #include "base/base64.h"
 #include "base/crc32c.h"
 #include "base/decimal_to_double.h"
+#include "base/json_records.h"
 #include "base/number_print.h"
 #include "base/util.h"
 #include "builtin/cpu_profiler.h"
@@ -912,6 +913,59 @@ PYBIND11_MODULE(_native, m) {
         const int err = pb::SerializeRecords(job, &out, &first_bad, &bad_column);
         return py::make_tuple(err, first_bad, bad_column, py::bytes(out));
     }, py::arg("number"), py::arg("columns"), py::arg("rows"));
+    // The host twin of gpu::DevicePrintRecordObjects
+    // (json::FormatRecordObjects): columns = [(key, kind, text_form, values,
+    // row_ends)], key raw bytes, text_form 0 (a number kind), 1 (string) or 2
+    // (base64), values and row_ends as in pb_serialize_records ->
+    // (err, first_bad, bad_column, text); the text is empty on a code other
+    // than 0.
+    m.def("json_format_record_objects", [](const std::vector<std::tuple<py::bytes, uint32_t, uint32_t, py::bytes, py::object>>& columns,
+                                           uint64_t rows, bool brackets) {
+        const size_t n = columns.size();
+        std::vector<std::string> keys(n);
+        std::vector<std::vector<uint64_t>> values(n);
+        std::vector<std::vector<uint32_t>> ends(n);
+        std::vector<json_records::Column> cols(n);
+        for (size_t c = 0; c < n; ++c) {
+            keys[c] = std::get<0>(columns[c]);
+            cols[c].key = keys[c].data();
+            cols[c].key_len = (uint32_t)keys[c].size();
+            cols[c].kind = std::get<1>(columns[c]);
+            cols[c].text = std::get<2>(columns[c]);
+            const std::string data = std::get<3>(columns[c]);
+            // a kind there is not is the twin's to refuse
+            const size_t eb = cols[c].kind == json_records::kKindBytes || !number_print::KindValid(cols[c].kind)
+                                  ? 1
+                                  : number_print::ElemBytes(cols[c].kind);
+            if (data.size() % eb) throw std::invalid_argument("values must hold whole elements");
+            values[c].resize(data.size() / 8 + 1);  // aligned for 8-byte elements, never null
+            if (!data.empty()) memcpy(values[c].data(), data.data(), data.size());
+            cols[c].src = values[c].data();
+            cols[c].count = data.size() / eb;
+            const py::object& re = std::get<4>(columns[c]);
+            if (re.is_none()) continue;
+            if (py::isinstance<py::bytes>(re)) {
+                const std::string image = re.cast<std::string>();
+                if (image.size() % 4) throw std::invalid_argument("row_ends must hold whole uint32 entries");
+                ends[c].resize(image.size() / 4);
+                if (!image.empty()) memcpy(ends[c].data(), image.data(), image.size());
+            } else {
+                ends[c] = re.cast<std::vector<uint32_t>>();
+            }
+            if (ends[c].size() != rows) throw std::invalid_argument("every row_ends must hold `rows` entries");
+            ends[c].push_back(0);  // data() of an empty table is still a table
+            cols[c].row_ends = ends[c].data();
+        }
+        json_records::Job job;
+        job.columns = cols.data();
+        job.ncols = (uint32_t)n;
+        job.rows = rows;
+        job.brackets = brackets;
+        std::string out;
+        uint32_t first_bad = 0xFFFFFFFFu, bad_column = 0xFFFFFFFFu;
+        const int err = json::FormatRecordObjects(job, &out, &first_bad, &bad_column);
+        return py::make_tuple(err, first_bad, bad_column, py::bytes(out));
+    }, py::arg("columns"), py::arg("rows"), py::arg("brackets") = true);
     // The host twin of gpu::DeviceSplitRows (pb::SplitRows): the message's
     // rows of field `number` -> (err, count, rows, others, first_bad, values
     // bytes, row_ends list). max_elems / max_rows are the outputs' capacities
@@ -1546,6 +1600,8 @@ PYBIND11_MODULE(_native, m) {
         d["pb2json_elems"] = s.pb2json_elems;
         d["pb2json_failures"] = s.pb2json_failures;
         d["pb2json_float_arrays"] = s.pb2json_float_arrays;
+        d["record_print_jobs"] = s.record_print_jobs;
+        d["record_print_rows"] = s.record_print_rows;
         d["pb2json_float_elems"] = s.pb2json_float_elems;
         d["int_arrays"] = s.int_arrays;
         d["int_array_fallbacks"] = s.int_array_fallbacks;

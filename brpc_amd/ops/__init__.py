@@ -11,3 +11,4 @@ from .json import base64_decode, base64_decode_rows, base64_encode, base64_encod
 from .json import json_escape_string, json_unescape_string, json_unescape_string_rows, utf8_validate  # noqa: F401
 from .json import json_index, json_index_host, json_parse_float_rows, json_parse_floats, json_print_floats  # noqa: F401
 from .json import json_parse_int_rows, json_parse_ints, json_print_numbers  # noqa: F401
+from .json import json_print_records  # noqa: F401

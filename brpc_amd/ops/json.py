@@ -370,6 +370,116 @@ def json_print_numbers(values, row_ends=None, brackets=True):
     return out[:length]
 
 
+# kind_name -> (kind, text form, dtypes): the names ops.pb uses for its
+# columns, plus the two text forms of uint8 data. fixed32 / fixed64 and bytes
+# are wire notions: a JSON cell needs to know what the bits mean.
+_RECORD_KINDS = {
+    "int32": (0, 0, (torch.int32,)),
+    "uint32": (1, 0, (torch.int32, getattr(torch, "uint32", torch.int32))),
+    "sint32": (2, 0, (torch.int32,)),
+    "int64": (3, 0, (torch.int64,)),
+    "uint64": (4, 0, (torch.int64, getattr(torch, "uint64", torch.int64))),
+    "sint64": (5, 0, (torch.int64,)),
+    "bool": (6, 0, (torch.bool, torch.uint8)),
+    "float32": (8, 0, (torch.float32,)),
+    "float64": (9, 0, (torch.float64,)),
+    "string": (7, 1, (torch.uint8,)),
+    "base64": (7, 2, (torch.uint8,)),
+}
+RECORD_PRINT_ERRORS = dict(PRINT_ERRORS)
+RECORD_PRINT_ERRORS[2] = "refused (columns, kinds, a scalar column's length, keys, alignment or size)"
+
+
+def json_print_records(columns, brackets=True):
+    """Columns of a batch in device memory -> uint8 device tensor of the JSON
+    text ``[{"k0":cell,"k1":cell,...},...]`` (``gpu::DevicePrintRecordObjects``),
+    the shape http+json model APIs return; no column and no table leaves HBM.
+
+    columns: [(key, values, row_ends_or_None, kind_name)], at most 8, printed
+    into every record in this order: every key appears in every record and
+    nothing is omitted (this is not pb2json's omission rule). ``key`` is str
+    (its UTF-8) or bytes. ``kind_name`` is one of the names ``pb_build_records``
+    uses for numbers (int32, uint32, sint32, int64, uint64, sint64, bool,
+    float32, float64), or ``"string"`` / ``"base64"`` for uint8 data. The
+    ``(values, row_ends)`` pairs of ``pb_split_records`` are taken unchanged: an
+    int64 ``row_ends`` is narrowed on the device, rows may be empty. With
+    ``row_ends=None`` a 1-D tensor is a scalar column (one element per record),
+    a 2-D one means equal rows.
+
+    A cell is the element as ``json_print_numbers`` prints it, ``[v,...,v]``
+    for a ragged number column, the escaped row in quotes for ``"string"``
+    (no UTF-8 verdict) and the padded base64 of the row in quotes for
+    ``"base64"``. ``brackets=False`` leaves the outer ``[`` ``]`` away.
+
+    Raises ValueError naming the lowest bad row and its column when a table of
+    row ends is malformed. Stream discipline as in ``json_print_numbers``."""
+    name = "json_print_records"
+    if not columns:
+        raise ValueError("no columns")
+    dev = columns[0][1].device
+    rows, cols, keep = None, [], []
+    for c, (key, values, row_ends, kind_name) in enumerate(columns):
+        if kind_name not in _RECORD_KINDS:
+            raise ValueError("column %d: unknown kind %r (one of %s)" % (c, kind_name, ", ".join(_RECORD_KINDS)))
+        kind, text, dtypes = _RECORD_KINDS[kind_name]
+        require_gpu_tensor(values, "column %d" % c)
+        if values.device != dev:
+            raise ValueError("all columns must live on one device (%s vs %s)" % (values.device, dev))
+        if values.dtype not in dtypes:
+            raise TypeError("column %d: kind %s takes a tensor of %s, not %s" % (c, kind_name, dtypes[0], values.dtype))
+        if row_ends is None and values.dim() == 2:
+            per = values.shape[1]
+            row_ends = torch.arange(1, values.shape[0] + 1, dtype=torch.int32, device=dev) * per
+        elif row_ends is None and values.dim() != 1:
+            raise ValueError("column %d: values must be 1-D, or 2-D without row_ends" % c)
+        values = values.contiguous()
+        count = values.numel()
+        ends_ptr, nrows = 0, count
+        if row_ends is not None:
+            require_gpu_tensor(row_ends, "column %d row_ends" % c)
+            if row_ends.device != dev:
+                raise ValueError("column %d: row_ends must live on the same device as values" % c)
+            if row_ends.dtype == torch.int64:
+                # as uint32: what does not fit becomes an end the device refuses
+                row_ends = row_ends.clamp(0, 0xFFFFFFFF).to(torch.int32)
+            if row_ends.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or row_ends.dim() != 1:
+                raise TypeError("column %d: row_ends must be a 1-D int32, uint32 or int64 tensor, not %s"
+                                % (c, row_ends.dtype))
+            row_ends = row_ends.contiguous()
+            nrows = row_ends.numel()
+            ends_ptr = row_ends.data_ptr() if nrows else 0
+            if nrows == 0 and count:
+                raise ValueError("column %d: %d values in no rows" % (c, count))
+            keep.append(row_ends)
+        elif kind == 7:
+            raise ValueError("column %d: a %s column needs row_ends" % (c, kind_name))
+        if rows is None:
+            rows = nrows
+        elif nrows != rows:
+            raise ValueError("column %d holds %d records, the columns before it %d" % (c, nrows, rows))
+        keep.append(values)
+        key = key.encode("utf-8") if isinstance(key, str) else bytes(key)
+        cols.append((key, kind, text, values.data_ptr() if count else 0, count, ends_ptr))
+    if rows == 0:  # no record: "[]" or nothing, and nothing to launch
+        return torch.tensor(list(b"[]" if brackets else b""), dtype=torch.uint8, device=dev)
+    cap = native.gpu.json_records_worst_case(cols, rows, bool(brackets))
+    if cap == 0:
+        raise ValueError(name + ": " + RECORD_PRINT_ERRORS[2])
+    if cap >= 1 << 32:
+        raise ValueError(name + " handles outputs below 4 GiB")
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream(dev).synchronize()
+        (length, err, first_bad, bad_column), = native.gpu.device_json_print_records(
+            [(cols, rows, bool(brackets), out.data_ptr(), cap)], dev.index or 0)
+    if err == 1:
+        raise ValueError("%s: column %d: row_ends[%d] does not ascend to the column's %d values"
+                         % (name, bad_column, first_bad, cols[bad_column][4]))
+    if err:
+        raise ValueError(name + ": " + RECORD_PRINT_ERRORS.get(err, "code %d" % err))
+    return out[:length]
+
+
 def base64_encode(data):
     """Any contiguous device tensor -> uint8 device tensor of the base64 text
     of its bytes (standard alphabet, ``=`` padded): the form pb2json gives a
